@@ -31,6 +31,18 @@ that table of omega-independent node data, which depends on the parameter set on
 
 `python bench.py --gpus N` launches its own N ranks (torch.distributed.run, one per GPU) when it is
 not already running under a launcher.  Prints ONE JSON line on rank 0.
+
+A plain run prepares the context, warms up, times the steps and prints the line: `metric`, `value`, `unit`,
+`higher_is_better`, `dtype`, `ms_per_step` (wall time of one timed step) and what the timed steps report about
+themselves.  `--full` adds everything else the bench measures and checks: the per-launch profile of the timed steps
+with the roofline blocks built from it and the committed PMC summaries, the cold call in a child process without
+torch, the search without the node cache, the parity of the roots against tests/golden/cfg3_chains.npz and the
+CPU baseline with its live parity sample (exit code 3 on a parity failure).
+
+`--dump-outputs DIR` writes what the last timed step returned to its caller (rank 0: the roots of all ranks) as
+DIR/roots.npy (float64, [Re, Im] per chain; a non-finite value, as a failed chain can end on, is written as 0 and
+marked 0 in DIR/roots_finite.npy, 1 elsewhere), DIR/iters.npy and DIR/info.npy (float64); the guesses depend only
+on the arguments, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -313,7 +325,7 @@ def free_port():
 def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=5)
+    ap.add_argument("--steps", type=int, default=5, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--config", type=int, default=3, choices=[3, 4, 5])
     ap.add_argument("--npoints", type=int, default=None)
@@ -322,7 +334,15 @@ def parse_args():
     ap.add_argument("--no-cold", action="store_true", help="skip the no-cache / cold-start side measurements")
     ap.add_argument("--require-c-abi-gather", action="store_true",
                     help="exit with code 4 instead of falling back to torch.distributed when emme_gather_roots cannot be used")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also profile the timed steps (roofline), run the cold and no-cache side measurements, the golden "
+                         "parity check and the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the roots, iteration counts and info codes of the last timed step to DIR/*.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def main():
@@ -346,7 +366,7 @@ def main():
     # -- node_cache_alloc_ms -- is 2 ms for the cache's 72 GiB most of the time and has been 1.4-6 s on freshly leased
     # boxes, with and without torch; DESIGN.md 8.  Reporting both processes shows which part is whose.)
     cold_child = None
-    if world == 1 and args.config == 3 and not args.no_cold and not args.npoints:
+    if args.full and world == 1 and args.config == 3 and not args.no_cold and not args.npoints:
         import subprocess
         try:
             cp = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "cold_probe.py"), "plain", "--json"],
@@ -438,6 +458,7 @@ def main():
         torch.cuda.synchronize()
         first_s = time.perf_counter() - t0
         pr0 = ctx.profile_read(reset=True)
+        ctx.profile(args.full)
         ok0 = f0 == 0
         cold = {"first_call_s": first_s,
                 "first_call_omega_points_per_s": float(i0[ok0].sum()) / first_s,
@@ -449,8 +470,8 @@ def main():
                         "cache, its build kernels and cache growth included); the timed steps below run on the prepared "
                         "context.  node_cache_alloc_ms = the driver's time inside hipMalloc for the cache's 72 GiB: 2 ms "
                         "most of the time, 1.4-6 s on freshly leased boxes / right after other processes released the "
-                        "memory (cause not established, DESIGN.md 8).  process_without_torch = the same first search in a "
-                        "child process that never loads torch (tools/cold_probe.py, run before this process touched the GPU)"}
+                        "memory (cause not established, DESIGN.md 8).  process_without_torch (--full) = the same first search "
+                        "in a child process that never loads torch (tools/cold_probe.py, run before this process touched the GPU)"}
 
     class ProfSum:  # configs[4]: a context per k_rho -- their profiles added up
         FIELDS = [f[0] for f in emme_amd.Profile._fields_]
@@ -487,10 +508,9 @@ def main():
 
     for _ in range(args.warmup):
         step()
-    if ctx is not None:
-        ctx.profile(True)
+    if ctx is not None and args.full:
         ctx.profile_read(reset=True)
-    prof5["on"] = True
+    prof5["on"] = args.full
     barrier()
     t0 = time.perf_counter()
     points = 0
@@ -499,10 +519,12 @@ def main():
         points += int(iters[info == 0].sum())
     barrier()
     dt = time.perf_counter() - t0
-    prof = ctx.profile_read() if ctx is not None else prof5["sum"]
-    fill_symbol = ctx.fill_kernel_symbol() if ctx is not None else prof5["kernel"]
-    mat_dim = ctx.dim if ctx is not None else prof5["dim"]
-    cache_gib = ctx.node_cache_gib() if ctx is not None else prof5["gib"]
+    prof = None
+    if args.full:
+        prof = ctx.profile_read() if ctx is not None else prof5["sum"]
+        fill_symbol = ctx.fill_kernel_symbol() if ctx is not None else prof5["kernel"]
+        mat_dim = ctx.dim if ctx is not None else prof5["dim"]
+        cache_gib = ctx.node_cache_gib() if ctx is not None else prof5["gib"]
 
     stats = torch.tensor([dt, float(points), float((info == 0).sum()), float(len(roots)),
                           float(iters[info != 0].sum())], dtype=torch.float64, device="cuda")
@@ -516,7 +538,7 @@ def main():
     total_points = float(stats[1])
 
     # ---- side measurement (rank 0, cfg 3): the same search without the node cache (a one-shot caller)
-    if rank == 0 and cfg == 3 and not args.no_cold and world == 1:
+    if args.full and rank == 0 and cfg == 3 and not args.no_cold and world == 1:
         with emme_amd.Context(emme_amd.params_from_dict(d), device=local_rank, node_cache_gb=0.0) as c0:
             c0.set_stream(stream.cuda_stream)
             c0.solve_roots(guesses)
@@ -528,6 +550,17 @@ def main():
             cold["no_cache_omega_points_per_s"] = float(inn[fn == 0].sum()) / tn
             cold["no_cache_ms_per_step"] = tn * 1e3
             cold["no_cache_fill_kernel"] = c0.fill_kernel()
+
+    if rank == 0 and args.dump_outputs:
+        r_all, it_all, inf_all = allroots
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        ri = np.stack([np.real(r_all), np.imag(r_all)], axis=-1).astype(np.float64)
+        # a chain that fails (info != 0) can end on a non-finite omega: stored as 0, flagged in roots_finite
+        fin = np.isfinite(ri)
+        np.save(os.path.join(args.dump_outputs, "roots.npy"), np.where(fin, ri, 0.0))
+        np.save(os.path.join(args.dump_outputs, "roots_finite.npy"), fin.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "iters.npy"), np.asarray(it_all, dtype=np.float64))
+        np.save(os.path.join(args.dump_outputs, "info.npy"), np.asarray(inf_all, dtype=np.float64))
 
     if rank == 0:
         out = {
@@ -674,11 +707,11 @@ def main():
                 "host_gaps_and_copies": dt / args.steps * 1e3 - (prof.assemble_ms + prof.deferred_ms + prof.linstep_ms
                                                                   + prof.other_ms) / args.steps,
             }
-        if cfg == 3 and world == 1 and args.per_gpu == 128 and npoints == 256:
+        if args.full and cfg == 3 and world == 1 and args.per_gpu == 128 and npoints == 256:
             gp = golden_parity(roots, iters, info)
             if gp is not None:
                 out["parity_golden"] = gp
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             if cfg == 3:
                 sample = list(range(7, len(guesses), 16))
                 out["cpu_baseline"], par = cpu_baseline(d, guesses[7::16], roots, iters, sample)

@@ -19,15 +19,6 @@ def oracle():
 
 
 @pytest.fixture(scope="session")
-def reference():
-    """The reference's own kappa sources compiled by oracle/Makefile (oracle/_ref)."""
-    from oracle.binding import Reference
-    if not Reference.available():
-        pytest.skip("oracle/_ref/libemme_ref.so not built (needs /root/reference at build time)")
-    return Reference()
-
-
-@pytest.fixture(scope="session")
 def emme():
     import emme_amd
     if not os.path.exists(emme_amd.lib_path()):

@@ -1,6 +1,6 @@
 """CPU tests of the measurement code in bench.py (no GPU, no oracle): the executed-work roofline arithmetic on a
 synthetic counter summary, the committed round-3 PMC summaries and bench lines (their roofline blocks must be
-reproducible by hand from the summaries), and the source stamp."""
+reproducible by hand from the summaries), the source stamp and the command line."""
 import json
 import os
 
@@ -67,3 +67,16 @@ def test_source_stamp_matches_the_committed_summaries():
     h = bench.kernel_source_sha16()
     for cfg, path in bench.PMC_SUMMARIES.items():
         assert json.load(open(path))["source_sha16"] == h, (cfg, path)
+
+
+def test_command_line_plain_full_and_dump(monkeypatch):
+    """A plain run is lean (--full off), --dump-outputs takes a directory, and --steps sets at least one timed step."""
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "2"])
+    a = bench.parse_args()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (3, 2, False, None)
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "1", "--full", "--dump-outputs", "out"])
+    a = bench.parse_args()
+    assert (a.steps, a.full, a.dump_outputs) == (1, True, "out")
+    monkeypatch.setattr("sys.argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse_args()
