@@ -557,10 +557,7 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
 
 }  // namespace
 
-hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream, const NodeCacheGeom* g,
-                           const void* const recs[2],
-                           const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                           const void* const ttab[2], const void* const wtab[2]) {
+hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream) {
     AsmArgs A;
     A.tiled = 0;
     A.tile_poison[0] = A.tile_poison[1] = nullptr;
@@ -580,13 +577,12 @@ hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream, const No
     A.worklist = nullptr;
     A.worklist_count = nullptr;
     A.folded = 0;
-    A.geom = g ? make_geom(*g) : CacheGeom{};
+    A.geom = CacheGeom{};
     for (int c = 0; c < 2; ++c) {
-        A.recs[c] = g ? (const NodeRec*)recs[c] : nullptr;
-        A.ttab[c] = g ? (const double2*)ttab[c] : nullptr;
-        A.wtab[c] = (g && wtab) ? (const double2*)wtab[c] : nullptr;
-        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k)
-            A.recs_ext[c][k] = g ? (const NodeRec*)recs_ext[c][k] : nullptr;
+        A.recs[c] = nullptr;
+        A.ttab[c] = nullptr;
+        A.wtab[c] = nullptr;
+        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = nullptr;
     }
     const int gw = L.gk_points == 15 ? 16 : 32;
     const int groups_per_block = 256 / gw;
@@ -611,14 +607,11 @@ hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream, const No
 // recomputed whole by the lanes-are-nodes kernel from a device-side list whose length the
 // host does not know -- a fixed grid strides over it and exits at once when it is empty.
 hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long long* worklist,
-                                const unsigned int* count, const NodeCacheGeom* g,
-                                const void* const recs[2],
-                                const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                const void* const ttab[2], const void* const wtab[2], bool folded,
-                                hipStream_t stream, bool tiled, const unsigned char* const tile_poison[2]) {
+                                const unsigned int* count, const NodeCacheView* cache, bool folded,
+                                hipStream_t stream, bool tiled) {
     AsmArgs A;
-    A.tile_poison[0] = (tiled && tile_poison) ? tile_poison[0] : nullptr;
-    A.tile_poison[1] = (tiled && tile_poison) ? tile_poison[1] : nullptr;
+    A.tile_poison[0] = (tiled && cache) ? cache->tile_poison[0] : nullptr;
+    A.tile_poison[1] = (tiled && cache) ? cache->tile_poison[1] : nullptr;
     A.tiled = tiled ? 1 : 0;
     A.P = L.P;
     A.tab = L.tab;
@@ -636,13 +629,13 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
     A.worklist = worklist;
     A.worklist_count = count;
     A.folded = folded ? 1 : 0;
-    A.geom = g ? make_geom(*g) : CacheGeom{};
+    A.geom = cache ? make_geom(*cache->geom) : CacheGeom{};
     for (int c = 0; c < 2; ++c) {
-        A.recs[c] = g ? (const NodeRec*)recs[c] : nullptr;
-        A.ttab[c] = g ? (const double2*)ttab[c] : nullptr;
-        A.wtab[c] = (g && wtab) ? (const double2*)wtab[c] : nullptr;
+        A.recs[c] = cache ? (const NodeRec*)cache->recs[c] : nullptr;
+        A.ttab[c] = cache ? (const double2*)cache->ttab[c] : nullptr;
+        A.wtab[c] = cache ? (const double2*)cache->wtab[c] : nullptr;
         for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k)
-            A.recs_ext[c][k] = g ? (const NodeRec*)recs_ext[c][k] : nullptr;
+            A.recs_ext[c][k] = cache ? (const NodeRec*)cache->recs_ext[c][k] : nullptr;
     }
     const int gw = L.gk_points == 15 ? 16 : 32;
     const int groups_per_block = 256 / gw;

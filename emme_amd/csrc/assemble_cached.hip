@@ -958,10 +958,7 @@ hipError_t launch_node_cache(const AssembleLaunch& L, const NodeCacheGeom& g, in
     return hipGetLastError();
 }
 
-hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheGeom& g,
-                                  const void* const recs[2],
-                                  const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                  const void* const ttab[2], const double* scale, const void* etab,
+hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheView& cache, const void* etab,
                                   unsigned long long* worklist, unsigned int* worklist_count,
                                   unsigned long long* defer_info, const int* act_idx, int n_act,
                                   const void* chunks, int nchunks, hipStream_t stream) {
@@ -971,14 +968,14 @@ hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheGeom& 
     A.tab = L.tab;
     A.pairs = (const ushort2*)L.pairs;
     A.npairs = L.npairs;
-    A.geom = make_geom(g);
+    A.geom = make_geom(*cache.geom);
     for (int c = 0; c < 2; ++c) {
-        A.recs[c] = (const NodeRec*)recs[c];
-        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const NodeRec*)recs_ext[c][k];
-        A.ttab[c] = (const double2*)ttab[c];
+        A.recs[c] = (const NodeRec*)cache.recs[c];
+        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const NodeRec*)cache.recs_ext[c][k];
+        A.ttab[c] = (const double2*)cache.ttab[c];
         A.wtab[c] = nullptr;
     }
-    A.scale = scale;
+    A.scale = cache.scale;
     A.etab = (const double2*)etab;
     A.worklist = worklist;
     A.worklist_count = worklist_count;
@@ -1031,27 +1028,24 @@ hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheGeom& 
     return hipGetLastError();
 }
 
-hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheGeom& g,
-                                  const void* const recs[2],
-                                  const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                  const void* const ttab[2], const void* const wtab[2], const double* scale,
-                                  const void* etab, unsigned long long* worklist, unsigned int* worklist_count,
-                                  unsigned long long* defer_info, const int* act_idx, int n_act,
-                                  const void* chunks, int nchunks, hipStream_t stream) {
+hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheView& cache, const void* etab,
+                                     unsigned long long* worklist, unsigned int* worklist_count,
+                                     unsigned long long* defer_info, const int* act_idx, int n_act,
+                                     const void* chunks, int nchunks, hipStream_t stream) {
     AsmCachedArgs A;
     A.chunks = (const int2*)chunks;
     A.P = L.P;
     A.tab = L.tab;
     A.pairs = (const ushort2*)L.pairs;
     A.npairs = L.npairs;
-    A.geom = make_geom(g);
+    A.geom = make_geom(*cache.geom);
     for (int c = 0; c < 2; ++c) {
-        A.recs[c] = (const NodeRec*)recs[c];
-        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const NodeRec*)recs_ext[c][k];
-        A.ttab[c] = (const double2*)ttab[c];
-        A.wtab[c] = (const double2*)wtab[c];
+        A.recs[c] = (const NodeRec*)cache.recs[c];
+        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const NodeRec*)cache.recs_ext[c][k];
+        A.ttab[c] = (const double2*)cache.ttab[c];
+        A.wtab[c] = (const double2*)cache.wtab[c];
     }
-    A.scale = scale;
+    A.scale = cache.scale;
     A.etab = (const double2*)etab;
     A.worklist = worklist;
     A.worklist_count = worklist_count;
@@ -1086,11 +1080,11 @@ hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheGeo
     return hipGetLastError();
 }
 
-hipError_t launch_phase_table(int gk_points, int n_intervals, const void* const ttab[2],
+hipError_t launch_phase_table(int gk_points, int n_intervals, const NodeCacheView& cache,
                               const double* omega, const int* act_idx, int n_act, void* etab,
                               hipStream_t stream) {
     PhaseArgs A;
-    A.ttab[0] = (const double2*)ttab[0], A.ttab[1] = (const double2*)ttab[1];
+    A.ttab[0] = (const double2*)cache.ttab[0], A.ttab[1] = (const double2*)cache.ttab[1];
     A.omega = (const double2*)omega;
     A.act_idx = act_idx;
     A.n_act = n_act;

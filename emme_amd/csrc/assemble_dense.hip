@@ -874,12 +874,11 @@ hipError_t launch_node_cache_tiled(const AssembleLaunch& L, const NodeCacheGeom&
     return hipGetLastError();
 }
 
-hipError_t launch_btab(int gk_points, int nm, int nslots, const void* const ttab[2], const void* const wtab[2],
-                       const double* omega, const int* act_idx, int n_act, const int* wmap, int nchunks, void* btab,
-                       hipStream_t stream) {
+hipError_t launch_btab(int gk_points, int nm, int nslots, const NodeCacheView& cache, const double* omega,
+                       const int* act_idx, int n_act, const int* wmap, int nchunks, void* btab, hipStream_t stream) {
     BtabArgs A;
-    A.ttab[0] = (const double2*)ttab[0], A.ttab[1] = (const double2*)ttab[1];
-    A.wtab[0] = wtab ? (const double2*)wtab[0] : nullptr, A.wtab[1] = wtab ? (const double2*)wtab[1] : nullptr;
+    A.ttab[0] = (const double2*)cache.ttab[0], A.ttab[1] = (const double2*)cache.ttab[1];
+    A.wtab[0] = (const double2*)cache.wtab[0], A.wtab[1] = (const double2*)cache.wtab[1];
     A.omega = (const double2*)omega;
     A.act_idx = act_idx;
     A.wmap = wmap;
@@ -904,26 +903,25 @@ hipError_t launch_btab(int gk_points, int nm, int nslots, const void* const ttab
     return hipGetLastError();
 }
 
-hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheGeom& g, const void* const recs[2],
-                                 const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1], const double* scale,
-                                 const void* btab, unsigned long long* worklist, unsigned int* worklist_count,
+hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& cache, const void* btab,
+                                 unsigned long long* worklist, unsigned int* worklist_count,
                                  unsigned long long* defer_info, const int* act_idx, int n_act,
                                  const void* chunks, int nchunks, unsigned long long* stats, hipStream_t stream,
-                                 const unsigned char* const tile_poison[2], int n_wide, unsigned int* overflow) {
+                                 int n_wide, unsigned int* overflow) {
     DenseArgs A;
-    A.tile_poison[0] = tile_poison ? tile_poison[0] : nullptr;
-    A.tile_poison[1] = tile_poison ? tile_poison[1] : nullptr;
+    A.tile_poison[0] = cache.tile_poison[0];
+    A.tile_poison[1] = cache.tile_poison[1];
     A.P = L.P;
     A.tab = L.tab;
     A.pairs = (const ushort2*)L.pairs;
     A.npairs = L.npairs;
-    A.geom = make_geom(g);
+    A.geom = make_geom(*cache.geom);
     for (int c = 0; c < 2; ++c) {
-        A.recs[c] = (const double*)recs[c];
-        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const double*)recs_ext[c][k];
+        A.recs[c] = (const double*)cache.recs[c];
+        for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = (const double*)cache.recs_ext[c][k];
     }
     A.btab = (const double*)btab;
-    A.scale = scale;
+    A.scale = cache.scale;
     A.worklist = worklist;
     A.worklist_count = worklist_count;
     A.defer_info = defer_info;

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../include/emme_hip.h"
+#include "buffers.hpp"
 #include "launch.hpp"
 
 
@@ -34,12 +35,24 @@ void set_error(const std::string& msg);
 
 enum Kind { K_ASM = 0, K_LIN = 1, K_OTHER = 2, K_DEFER = 3, K_CACHE = 4, K_NULL = 5 };
 
+// HBM node cache of one contour class (omi = +1, -1)
+struct NodeCacheClass {
+    PooledBuffer recs;                                // main part
+    PooledBuffer recs_ext[NODE_CACHE_MAX_SUB - 1];    // run-time subtrees
+    DeviceBuffer<> ttab;                              // T table
+    DeviceBuffer<> wtab;                              // moment-factor table (shared EM layout, tiled EM)
+    DeviceBuffer<unsigned char> tile_poison;          // tiled layout: tiles that hold a poisoned block
+};
+
 }  // namespace emme
 
 // (the C ABI's opaque context type lives at global scope; its members are types of namespace emme)
 using emme::DevParams;
+using emme::DeviceBuffer;
+using emme::NodeCacheClass;
 using emme::NodeCacheGeom;
 using emme::NODE_CACHE_MAX_SUB;
+using emme::PinnedBuffer;
 
 struct emme_ctx {
     emme_params_t p;
@@ -47,71 +60,52 @@ struct emme_ctx {
     hipStream_t stream = nullptr;
     DevParams P;
     int N = 0, dim = 0, nm = 1, npairs = 0;
-    double* d_tab = nullptr;
-    ushort2* d_pairs = nullptr;
+    DeviceBuffer<double> d_tab;
+    DeviceBuffer<ushort2> d_pairs;
     // batch scratch
-    int cap = 0;
-    double *d_omega = nullptr, *d_domega = nullptr, *d_tr = nullptr;
-    int *d_active = nullptr, *d_iters = nullptr, *d_info = nullptr, *d_status = nullptr;
-    unsigned long long* d_intervals = nullptr;
-    unsigned long long* d_rounds = nullptr;  // diagnostic counter of the omega-lane kernel
-    int* d_actidx = nullptr;   // compacted list of batch items for the omega-lane kernel
-    int* d_chunks = nullptr;   // (first, size) of every omega chunk of the cached kernel
+    DeviceBuffer<double> d_omega, d_domega, d_tr;
+    DeviceBuffer<int> d_active, d_iters, d_info, d_status;
+    DeviceBuffer<unsigned long long> d_intervals;
+    DeviceBuffer<unsigned long long> d_rounds;  // diagnostic counter of the omega-lane kernel
+    DeviceBuffer<int> d_actidx;   // compacted list of batch items for the omega-lane kernel
+    DeviceBuffer<int> d_chunks;   // (first, size) of every omega chunk of the cached kernel
     std::vector<int> h_chunks;
-    std::vector<int> h_actidx; // its host image (kept alive across the async upload)
+    std::vector<int> h_actidx; // its host image
     int last_fill_mode = -1;   // kernel family of the last fill: 0 nodes, 1 omega-lane, 2 cached
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
     // HBM cache of omega-independent node records, per contour class (omi = +1, -1)
     int cache_depth = -1;      // -1: not decided yet, -2: disabled / does not fit, else dfull
     NodeCacheGeom cache_geom{};
     int cache_max_intervals = 0;  // capacity of the T / scale tables
-    void* d_recs[2] = {nullptr, nullptr};      // main part per contour class
-    size_t recs_bytes[2] = {0, 0};
-    size_t recs_ext_bytes[2][NODE_CACHE_MAX_SUB - 1] = {};
-    void* d_recs_ext[2][NODE_CACHE_MAX_SUB - 1] = {};  // run-time subtrees per class
-    void* d_ttab[2] = {nullptr, nullptr};      // T table per class
-    void* d_wtab[2] = {nullptr, nullptr};      // moment-factor table per class (shared EM layout)
-    unsigned char* d_tile_poison[2] = {nullptr, nullptr};  // tiled layout: tiles that hold a poisoned block, per class
+    NodeCacheClass cache[2];
     bool em_shared = false;    // nm == 3: one record per (pair, interval, node), three moments per lane
     bool folded = true;        // records carry exp(A0); exp(T omega) comes from a per-launch phase table
     bool tiled = false;        // electrostatic GK15: tiled record layout + dense (matrix-core) fill
-    void* d_btab = nullptr;    // weighted phase tables of the current launch (dense fill)
-    size_t btab_cap = 0;
-    void* d_etab = nullptr;    // phase table of the current launch
-    size_t etab_bytes = 0;
-    int* h_lu_items = nullptr;     // blocked LU: the live matrices of the launch (pinned host / device)
-    int* d_lu_items = nullptr;
-    int lu_items_cap = 0;
-    void* d_lu_scratch = nullptr;  // blocked LU: diagonal of X, hand-over flags, row-map snapshots
-    size_t lu_scratch_bytes = 0;
+    DeviceBuffer<> d_btab;     // weighted phase tables of the current launch (dense fill)
+    DeviceBuffer<> d_etab;     // phase table of the current launch
+    DeviceBuffer<int> d_lu_items;  // blocked LU: the live matrices of the launch
+    DeviceBuffer<> d_lu_scratch;   // blocked LU: diagonal of X, hand-over flags, row-map snapshots
     int n_cu = 256;                // compute units of the device
     int last_lu_nwg = 1;           // workgroups per matrix of the last LU launch
     bool lu_one_wg = false;        // a hand-over of the multi-workgroup LU timed out once: never again
-    int* p_act = nullptr;          // pinned host copies of d_active / d_intervals / omega / the deferred
-    unsigned long long* p_iv = nullptr;  // count, WRITTEN BY KERNELS (k_retire, k_newton_update): the
-    double* p_w = nullptr;         // Newton loop reads them after its one synchronisation per step
-    unsigned int* p_deferred = nullptr;
-    unsigned int* d_overflow = nullptr;  // per item: integrals that left the dense fill because a level list was full
-    unsigned int* p_overflow = nullptr;  // ... published by k_retire
+    PinnedBuffer<int> p_act;       // pinned host copies of d_active / d_intervals / omega / the deferred
+    PinnedBuffer<unsigned long long> p_iv;  // count, WRITTEN BY KERNELS (k_retire, k_newton_update): the
+    PinnedBuffer<double> p_w;      // Newton loop reads them after its one synchronisation per step
+    PinnedBuffer<unsigned int> p_deferred;
+    DeviceBuffer<unsigned int> d_overflow;  // per item: integrals that left the dense fill because a level list was full
+    PinnedBuffer<unsigned int> p_overflow;  // ... published by k_retire
     std::vector<unsigned char> h_wide;   // items whose chunks take the 128-entry build of the dense fill (root search)
-    int p_cap = 0;
     bool pub_valid = false;        // last_deferred holds the previous fill's count (from p_deferred)
-    int* p_lists = nullptr;        // pinned staging of the per-launch lists (omega order | chunks), two
-    int p_lists_cap = 0;           // slots used in turn; k_stage_ints moves a slot to device memory
-    unsigned int p_lists_turn = 0;
-    unsigned int lu_items_turn = 0;
+    emme::StagingRing lists;       // per-launch index lists (omega order | chunks; LU items) on their way to the device
     bool ext_failed = false;
-    unsigned long long* d_defer_info = nullptr;  // missing interval of every deferred integral
+    DeviceBuffer<unsigned long long> d_defer_info;  // missing interval of every deferred integral
     double cache_bytes_used = 0.0;
     unsigned int last_deferred = 0;            // integrals the previous cached fill deferred
-    double* d_scale = nullptr;  // half-widths of the cached intervals
-    unsigned long long* d_worklist = nullptr;  // integrals deferred to the cooperative kernel
-    unsigned int* d_worklist_count = nullptr;
-    size_t worklist_cap = 0;
-    int mat_cap = 0;  // matrices per set
-    double *d_M = nullptr, *d_Mold = nullptr, *d_Mp = nullptr, *d_work = nullptr;
-    double* d_iterates = nullptr;
-    size_t iterates_cap = 0;
+    DeviceBuffer<double> d_scale;  // half-widths of the cached intervals
+    DeviceBuffer<unsigned long long> d_worklist;  // integrals deferred to the cooperative kernel
+    DeviceBuffer<unsigned int> d_worklist_count;
+    DeviceBuffer<double> d_M, d_Mold, d_Mp, d_work;  // matrix sets
+    DeviceBuffer<double> d_iterates;
     int last_n = 0;
     // profiling
     bool prof = false;
@@ -122,15 +116,33 @@ struct emme_ctx {
     };
     std::vector<Span> spans;
     std::vector<hipEvent_t> free_events;
+
+    // what the fill kernels read of the node cache
+    emme::NodeCacheView cache_view() const {
+        emme::NodeCacheView v{&cache_geom, {}, {}, {}, {}, {}, d_scale};
+        for (int k = 0; k < 2; ++k) {
+            v.recs[k] = cache[k].recs;
+            for (int e = 0; e < NODE_CACHE_MAX_SUB - 1; ++e) v.recs_ext[k][e] = cache[k].recs_ext[e];
+            v.ttab[k] = cache[k].ttab, v.wtab[k] = cache[k].wtab, v.tile_poison[k] = cache[k].tile_poison;
+        }
+        return v;
+    }
+    ~emme_ctx() {
+        // the records go back to the pool in this order (class 0 main, its subtrees, class 1 ...): the pool evicts
+        // its oldest entries first
+        for (auto& k : cache) {
+            k.recs.reset();
+            for (auto& e : k.recs_ext) e.reset();
+        }
+        for (auto& s : spans) (void)hipEventDestroy(s.a), (void)hipEventDestroy(s.b);
+        for (auto e : free_events) (void)hipEventDestroy(e);
+    }
 };
 
 namespace emme {
 
-// ---- ctx_cache.hip: buffer pool and node cache --------------------------------------------------------
+// ---- ctx_cache.hip: buffer pool (pool_alloc / pool_free / malloc_retry: buffers.hpp) and node cache ------------
 void pool_release_all();
-hipError_t pool_alloc(void** out, size_t bytes, int device);
-hipError_t malloc_retry(void** out, size_t bytes);
-void pool_free(void* p, size_t bytes, int device);
 long cache_items(const emme_ctx* c);
 size_t cache_part_bytes(const emme_ctx* c, int gk_points, const NodeCacheGeom& g, int part);
 bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls);

@@ -82,19 +82,20 @@ size_t cache_part_bytes(const emme_ctx* c, int gk_points, const NodeCacheGeom& g
 }
 hipError_t build_cache_part(emme_ctx* c, const AssembleLaunch& L, const NodeCacheGeom& g, int part, int cls, void* recs) {
     const double omi = cls == 0 ? 1.0 : -1.0;
+    NodeCacheClass& cc = c->cache[cls];
     if (c->tiled) {
-        if (!c->d_tile_poison[cls]) {
+        if (!cc.tile_poison) {
             const size_t ntiles = ((size_t)c->npairs + 15) / 16;
-            if (malloc_retry((void**)&c->d_tile_poison[cls], ntiles) != hipSuccess) return hipErrorOutOfMemory;
-            const hipError_t e = hipMemsetAsync(c->d_tile_poison[cls], 0, ntiles, c->stream);
+            if (cc.tile_poison.grow(ntiles) != hipSuccess) return hipErrorOutOfMemory;
+            const hipError_t e = hipMemsetAsync(cc.tile_poison, 0, ntiles, c->stream);
             if (e != hipSuccess) return e;
         }
-        hipError_t e = launch_node_cache_tiled(L, g, part, omi, recs, c->d_ttab[cls], c->d_scale, c->stream, c->d_tile_poison[cls],
-                                               c->nm > 1 ? c->d_wtab[cls] : nullptr);
+        hipError_t e = launch_node_cache_tiled(L, g, part, omi, recs, cc.ttab, c->d_scale, c->stream, cc.tile_poison,
+                                               c->nm > 1 ? cc.wtab : nullptr);
         if (e == hipSuccess && std::getenv("EMME_DEBUG")) {
             const size_t ntiles = ((size_t)c->npairs + 15) / 16;
             std::vector<unsigned char> flags(ntiles);
-            (void)hipMemcpyAsync(flags.data(), c->d_tile_poison[cls], ntiles, hipMemcpyDeviceToHost, c->stream);
+            (void)hipMemcpyAsync(flags.data(), cc.tile_poison, ntiles, hipMemcpyDeviceToHost, c->stream);
             (void)hipStreamSynchronize(c->stream);
             int n_poison = 0;
             for (unsigned char f : flags) n_poison += f != 0;
@@ -102,7 +103,7 @@ hipError_t build_cache_part(emme_ctx* c, const AssembleLaunch& L, const NodeCach
         }
         return e;
     }
-    return launch_node_cache(L, g, part, omi, recs, c->d_ttab[cls], c->d_wtab[cls], c->d_scale, c->folded, c->stream);
+    return launch_node_cache(L, g, part, omi, recs, cc.ttab, cc.wtab, c->d_scale, c->folded, c->stream);
 }
 
 // Make sure the main part of the node cache of contour class `cls` (0: omi=+1, 1: omi=-1)
@@ -140,27 +141,24 @@ bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls) {
         c->cache_depth = c->cache_geom.dfull;
         c->cache_max_intervals = node_cache_intervals(c->cache_geom) + (NODE_CACHE_MAX_SUB - 1) * 511;
     }
-    if (c->d_recs[cls]) return true;
+    NodeCacheClass& cc = c->cache[cls];
+    if (cc.recs) return true;
     const size_t bytes = cache_part_bytes(c, L.gk_points, c->cache_geom, -1);
+    const size_t tbytes = node_ttab_bytes(L.gk_points, c->cache_max_intervals);
     AllocTimer at(c);
-    if (c->cache_bytes_used + (double)bytes > budget ||
-        pool_alloc(&c->d_recs[cls], bytes, c->device) != hipSuccess ||
-        malloc_retry(&c->d_ttab[cls], node_ttab_bytes(L.gk_points, c->cache_max_intervals)) != hipSuccess ||
-        ((c->em_shared || (c->tiled && c->nm > 1)) &&
-         malloc_retry(&c->d_wtab[cls], node_ttab_bytes(L.gk_points, c->cache_max_intervals)) != hipSuccess) ||
-        (!c->d_scale &&
-         malloc_retry((void**)&c->d_scale, sizeof(double) * c->cache_max_intervals) != hipSuccess)) {
+    if (c->cache_bytes_used + (double)bytes > budget || cc.recs.alloc(bytes, c->device) != hipSuccess ||
+        cc.ttab.grow(tbytes) != hipSuccess ||
+        ((c->em_shared || (c->tiled && c->nm > 1)) && cc.wtab.grow(tbytes) != hipSuccess) ||
+        c->d_scale.grow(sizeof(double) * c->cache_max_intervals) != hipSuccess) {
         (void)hipGetLastError();
-        pool_free(c->d_recs[cls], bytes, c->device);
-        c->d_recs[cls] = nullptr;
+        cc.recs.reset();
         c->cache_depth = -2;  // fall back to the on-the-fly kernels for good
         return false;
     }
     at.stop();
     c->cache_bytes_used += (double)bytes;
-    c->recs_bytes[cls] = bytes;
     ScopedSpan s(c, K_CACHE);
-    if (build_cache_part(c, L, c->cache_geom, -1, cls, c->d_recs[cls]) != hipSuccess) {
+    if (build_cache_part(c, L, c->cache_geom, -1, cls, cc.recs) != hipSuccess) {
         c->cache_depth = -2;
         return false;
     }
@@ -182,7 +180,8 @@ int find_subtree(const NodeCacheGeom& g, int depth, unsigned long long path) {
 // integrals keep going through the work list.
 void add_cache_subtree(emme_ctx* c, const AssembleLaunch& L, int depth, unsigned long long path, int cls) {
     NodeCacheGeom& g = c->cache_geom;
-    if (c->ext_failed || !c->d_recs[cls]) return;
+    NodeCacheClass& cc = c->cache[cls];
+    if (c->ext_failed || !cc.recs) return;
     if (depth <= g.dfull) return;  // (inside the full tree: a poisoned tile's hand-over, not a missing interval)
     int k = find_subtree(g, depth, path);
     const bool fresh = k < 0;
@@ -195,26 +194,23 @@ void add_cache_subtree(emme_ctx* c, const AssembleLaunch& L, int depth, unsigned
         g.rp[k] = path >> (depth - rd);
         g.dd[k] = rd + 8;
         g.nsub = k + 1;
-    } else if (c->d_recs_ext[cls][k - 1]) {
+    } else if (cc.recs_ext[k - 1]) {
         return;  // already there (the deferral was for an interval deeper than the subtree)
     }
     const double budget = c->opt.node_cache_gb * (double)(1 << 30);
     const size_t eb = cache_part_bytes(c, L.gk_points, g, k - 1);
     AllocTimer at(c);
-    if (c->cache_bytes_used + (double)eb > budget ||
-        pool_alloc(&c->d_recs_ext[cls][k - 1], eb, c->device) != hipSuccess) {
+    if (c->cache_bytes_used + (double)eb > budget || cc.recs_ext[k - 1].alloc(eb, c->device) != hipSuccess) {
         (void)hipGetLastError();
-        c->d_recs_ext[cls][k - 1] = nullptr;
         c->ext_failed = true;
         if (fresh) g.nsub = k;  // nothing built: forget the registration
         return;
     }
     at.stop();
     c->cache_bytes_used += (double)eb;
-    c->recs_ext_bytes[cls][k - 1] = eb;
     {
         ScopedSpan s(c, K_CACHE);
-        if (build_cache_part(c, L, g, k - 1, cls, c->d_recs_ext[cls][k - 1]) != hipSuccess) c->ext_failed = true;
+        if (build_cache_part(c, L, g, k - 1, cls, cc.recs_ext[k - 1]) != hipSuccess) c->ext_failed = true;
     }
     if (std::getenv("EMME_DEBUG"))
         fprintf(stderr, "[emme] node cache: subtree %d (depth %d path %llx, to depth %d) built for class %d, %.1f GiB in use\n",

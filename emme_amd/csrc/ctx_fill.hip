@@ -74,7 +74,7 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
     // and pays off after ~10 fills: a call with a handful of omegas (a single root of a
     // parameter scan) goes through the on-the-fly kernels unless the cache already exists.
     bool use_cache = !force_uncached && host_omega != nullptr && c->cache_depth != -2 &&
-                     (nbatch >= c->opt.cache_min_batch || c->d_recs[0] != nullptr || c->d_recs[1] != nullptr);
+                     (nbatch >= c->opt.cache_min_batch || c->cache[0].recs || c->cache[1].recs);
     if (use_cache) {
         bool need[2] = {false, false};
         int count[2] = {0, 0};
@@ -87,7 +87,7 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
         // side) never earns it back.  The minority goes through the omega-lane kernel in a second pass of this call;
         // once it is more than a sixteenth of the batch its cache is built as before.
         for (int k = 0; k < 2; ++k) {
-            if (need[0] && need[1] && !c->d_recs[k] && count[k] * 16 <= n_act && count[k] < count[1 - k]) {
+            if (need[0] && need[1] && !c->cache[k].recs && count[k] * 16 <= n_act && count[k] < count[1 - k]) {
                 std::vector<int> major(nbatch, 0), minor(nbatch, 0);
                 for (int b : idx) (((-std::copysign(1.0, host_omega[2 * b]) > 0.0 ? 0 : 1) == k) ? minor : major)[b] = 1;
                 int rc = do_assemble(c, nbatch, d_omega, d_active, major.data(), d_M, d_Mold, d_Mp, d_domega, cost, host_omega,
@@ -138,21 +138,12 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
         }
     }
     if (use_cache) {
+        const NodeCacheView cache = c->cache_view();
         // work list for integrals that outgrow the cache (worst case: every one of them)
         const size_t need = (size_t)c->npairs * c->nm * (size_t)nbatch;
-        if (need > c->worklist_cap) {
-            if (c->d_worklist) (void)hipFree(c->d_worklist);
-            c->d_worklist = nullptr;
-            HIP_TRY(malloc_retry((void**)&c->d_worklist, need * sizeof(unsigned long long)));
-            if (c->d_defer_info) (void)hipFree(c->d_defer_info);
-            c->d_defer_info = nullptr;
-            HIP_TRY(malloc_retry((void**)&c->d_defer_info, need * sizeof(unsigned long long)));
-            c->worklist_cap = need;
-        }
-        if (!c->d_worklist_count) HIP_TRY(malloc_retry((void**)&c->d_worklist_count, sizeof(unsigned int)));
-
-    }
-    if (use_cache) {
+        HIP_TRY(c->d_worklist.grow(need * sizeof(unsigned long long)));
+        HIP_TRY(c->d_defer_info.grow(need * sizeof(unsigned long long)));
+        HIP_TRY(c->d_worklist_count.grow(sizeof(unsigned int)));
         const int gw = L.gk_points == 15 ? 16 : 32;
         // the union-walk kernel (electrostatic GK15 on folded records, assemble_cached.hip): lanes
         // that sit a round out cost little there, so its chunks are always full and each group
@@ -211,16 +202,17 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
         }
         if (n_lane) {
             // omega order | chunk table: into a pinned slot, then ONE small kernel moves both to the device
-            int* slot = c->p_lists + (size_t)(c->p_lists_turn++ & 1u) * c->p_lists_cap;
+            // (dense fill: the position -> (chunk, column) map behind the chunk table)
+            int n2 = (int)ch.size() + (c->tiled ? n_lane : 0);
+            int* slot = nullptr;
+            HIP_TRY(c->lists.take(n_lane + n2, &slot));
             std::copy(idx.begin(), idx.end(), slot);
             std::copy(ch.begin(), ch.end(), slot + n_lane);
-            int n2 = (int)ch.size();
-            if (c->tiled) {  // dense fill: position -> (chunk, column) map behind the chunk table
+            if (c->tiled)
                 for (int k = 0; k < nchunks; ++k)
-                    for (int w = 0; w < ch[2 * k + 1]; ++w) slot[n_lane + n2 + ch[2 * k] + w] = (k << 8) | w;
-                n2 += n_lane;
-            }
+                    for (int w = 0; w < ch[2 * k + 1]; ++w) slot[n_lane + (int)ch.size() + ch[2 * k] + w] = (k << 8) | w;
             HIP_TRY(launch_stage_ints(slot, c->d_actidx, n_lane, c->d_chunks, n2, c->stream));
+            HIP_TRY(c->lists.read_on(c->stream));
         }
         HIP_TRY(hipMemsetAsync(c->d_worklist_count, 0, sizeof(unsigned int), c->stream));
         c->last_fill_mode = c->tiled ? 4 : (union_walk ? 3 : 2);
@@ -230,16 +222,11 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
             const int n_int = node_cache_intervals(c->cache_geom);
             const int nch = nchunks;
             const size_t need = btab_bytes(n_int, nch, L.gk_points);
-            if (need > c->btab_cap) {
-                if (c->d_btab) (void)hipFree(c->d_btab);
-                c->d_btab = nullptr, c->btab_cap = 0;
-                HIP_TRY(malloc_retry(&c->d_btab, need + need / 4));
-                c->btab_cap = need + need / 4;
-            }
+            if (need > c->d_btab.bytes()) HIP_TRY(c->d_btab.grow(need + need / 4));
             {
                 ScopedSpan s(c, K_OTHER);
-                HIP_TRY(launch_btab(L.gk_points, c->nm, n_int, c->d_ttab, c->d_wtab, d_omega, c->d_actidx, n_lane,
-                                    c->d_chunks + 2 * nchunks, nchunks, c->d_btab, c->stream));
+                HIP_TRY(launch_btab(L.gk_points, c->nm, n_int, cache, d_omega, c->d_actidx, n_lane, c->d_chunks + 2 * nchunks,
+                                    nchunks, c->d_btab, c->stream));
             }
             {
                 ScopedSpan s(c, K_ASM);
@@ -255,9 +242,8 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
                     HIP_TRY(hipEventCreate(&e1));
                     HIP_TRY(hipEventRecord(e0, c->stream));
                 }
-                HIP_TRY(launch_assemble_dense(L, c->cache_geom, c->d_recs, c->d_recs_ext, c->d_scale, c->d_btab,
-                                              c->d_worklist, c->d_worklist_count, c->d_defer_info, c->d_actidx, n_lane,
-                                              c->d_chunks, nchunks, c->d_rounds, c->stream, c->d_tile_poison,
+                HIP_TRY(launch_assemble_dense(L, cache, c->d_btab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
+                                              c->d_actidx, n_lane, c->d_chunks, nchunks, c->d_rounds, c->stream,
                                               (c->opt.dense_wide && c->nm == 1) ? nchunks : n_wide, newton_loop ? c->d_overflow : nullptr));
                 if (stamps) {
                     HIP_TRY(hipEventRecord(e1, c->stream));
@@ -289,36 +275,29 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
             // phase table of this launch: exp(T omega) for every cached interval, node and omega
             const int n_int = node_cache_intervals(c->cache_geom);
             const size_t need = (size_t)n_lane * n_int * gw * 2 * sizeof(double);
-            if (need > c->etab_bytes) {
-                if (c->d_etab) (void)hipFree(c->d_etab);
-                c->d_etab = nullptr, c->etab_bytes = 0;
-                HIP_TRY(malloc_retry(&c->d_etab, need + need / 4));
-                c->etab_bytes = need + need / 4;
-            }
+            if (need > c->d_etab.bytes()) HIP_TRY(c->d_etab.grow(need + need / 4));
             ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_phase_table(L.gk_points, n_int, c->d_ttab, d_omega, c->d_actidx, n_lane, c->d_etab,
-                                       c->stream));
+            HIP_TRY(launch_phase_table(L.gk_points, n_int, cache, d_omega, c->d_actidx, n_lane, c->d_etab, c->stream));
         }
         if (n_lane && !c->tiled) {
             ScopedSpan s(c, K_ASM);
             const void* etab = c->folded ? c->d_etab : nullptr;
             if (c->em_shared)
-                HIP_TRY(launch_assemble_cached_em(L, c->cache_geom, c->d_recs, c->d_recs_ext, c->d_ttab, c->d_wtab,
-                                                  c->d_scale, etab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
+                HIP_TRY(launch_assemble_cached_em(L, cache, etab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
                                                   c->d_actidx, n_lane, c->d_chunks, nchunks, c->stream));
             else
-                HIP_TRY(launch_assemble_cached(L, c->cache_geom, c->d_recs, c->d_recs_ext, c->d_ttab, c->d_scale, etab,
-                                               c->d_worklist, c->d_worklist_count, c->d_defer_info, c->d_actidx,
-                                               n_lane, c->d_chunks, nchunks, c->stream));
+                HIP_TRY(launch_assemble_cached(L, cache, etab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
+                                               c->d_actidx, n_lane, c->d_chunks, nchunks, c->stream));
         }
         if (n_lane) {
             ScopedSpan s(c, K_DEFER);
             // (tiled electromagnetic / GK31 contexts: the cooperative kernel reads the electrostatic GK15 tile blocks
             // only -- the few integrals that leave the cache are evaluated from scratch)
             const bool coop_cached = !(c->tiled && (c->nm > 1 || L.gk_points != 15));
-            HIP_TRY(launch_assemble_list(L, c->d_worklist, c->d_worklist_count, coop_cached ? &c->cache_geom : nullptr, c->d_recs,
-                                         c->d_recs_ext, c->d_ttab, c->em_shared ? c->d_wtab : nullptr, c->folded, c->stream,
-                                         c->tiled && coop_cached, c->d_tile_poison));
+            NodeCacheView coop = cache;  // (moment factors of the shared EM layout only)
+            if (!c->em_shared) coop.wtab[0] = coop.wtab[1] = nullptr;
+            HIP_TRY(launch_assemble_list(L, c->d_worklist, c->d_worklist_count, coop_cached ? &coop : nullptr, c->folded,
+                                         c->stream, c->tiled && coop_cached));
         }
         if (std::getenv("EMME_DEBUG")) {
             unsigned int cnt = 0;
@@ -338,9 +317,11 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
         const int gw = L.gk_points == 15 ? 16 : 32;
         L.items_per_group = items_per_group_for(c, (n_act + gw - 1) / gw);
         {
-            int* slot = c->p_lists + (size_t)(c->p_lists_turn++ & 1u) * c->p_lists_cap;
+            int* slot = nullptr;
+            HIP_TRY(c->lists.take(n_act, &slot));
             std::copy(idx.begin(), idx.end(), slot);
             HIP_TRY(launch_stage_ints(slot, c->d_actidx, n_act, nullptr, 0, c->stream));
+            HIP_TRY(c->lists.read_on(c->stream));
         }
         c->last_fill_mode = 1;
         ScopedSpan s(c, K_ASM);

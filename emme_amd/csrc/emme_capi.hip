@@ -156,66 +156,37 @@ int drain_spans(emme_ctx* c) {
 }
 
 int ensure_batch(emme_ctx* c, int nb) {
-    if (nb <= c->cap) return EMME_OK;
-    auto F = [](auto*& p) {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-    };
-    F(c->d_omega), F(c->d_domega), F(c->d_tr), F(c->d_active), F(c->d_iters), F(c->d_info),
-        F(c->d_status), F(c->d_intervals), F(c->d_actidx), F(c->d_chunks), F(c->d_overflow);
-    c->cap = 0;
-    HIP_TRY(malloc_retry((void**)&c->d_overflow, sizeof(unsigned int) * nb));
-    HIP_TRY(hipMemset(c->d_overflow, 0, sizeof(unsigned int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_omega, sizeof(double) * 2 * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_domega, sizeof(double) * 2 * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_tr, sizeof(double) * 2 * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_active, sizeof(int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_iters, sizeof(int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_info, sizeof(int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_status, sizeof(int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_intervals, sizeof(unsigned long long) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_actidx, sizeof(int) * nb));
-    HIP_TRY(malloc_retry((void**)&c->d_chunks, sizeof(int) * 3 * nb));  // (first, size) per chunk | position map
-    {
-        if (c->p_act) (void)hipHostFree(c->p_act);
-        if (c->p_iv) (void)hipHostFree(c->p_iv);
-        if (c->p_w) (void)hipHostFree(c->p_w);
-        if (c->p_lists) (void)hipHostFree(c->p_lists);
-        if (c->p_overflow) (void)hipHostFree(c->p_overflow);
-        c->p_act = nullptr, c->p_iv = nullptr, c->p_w = nullptr, c->p_lists = nullptr, c->p_cap = 0, c->p_lists_cap = 0;
-        c->p_overflow = nullptr;
-        HIP_TRY(hipHostMalloc((void**)&c->p_overflow, sizeof(unsigned int) * nb));
-        std::memset(c->p_overflow, 0, sizeof(unsigned int) * nb);
-        HIP_TRY(hipHostMalloc((void**)&c->p_act, sizeof(int) * nb));
-        HIP_TRY(hipHostMalloc((void**)&c->p_iv, sizeof(unsigned long long) * nb));
-        HIP_TRY(hipHostMalloc((void**)&c->p_w, sizeof(double) * 2 * nb));
-        HIP_TRY(hipHostMalloc((void**)&c->p_lists, sizeof(int) * 2 * 4 * nb));  // 2 slots x (order | chunks | map)
-        if (!c->p_deferred) HIP_TRY(hipHostMalloc((void**)&c->p_deferred, sizeof(unsigned int)));
-        c->p_cap = nb, c->p_lists_cap = 4 * nb;
-    }
+    const size_t n = (size_t)nb;
+    HIP_TRY(c->d_omega.grow(sizeof(double) * 2 * n));
+    HIP_TRY(c->d_domega.grow(sizeof(double) * 2 * n));
+    HIP_TRY(c->d_tr.grow(sizeof(double) * 2 * n));
+    HIP_TRY(c->d_active.grow(sizeof(int) * n));
+    HIP_TRY(c->d_iters.grow(sizeof(int) * n));
+    HIP_TRY(c->d_info.grow(sizeof(int) * n));
+    HIP_TRY(c->d_status.grow(sizeof(int) * n));
+    HIP_TRY(c->d_intervals.grow(sizeof(unsigned long long) * n));
+    HIP_TRY(c->d_overflow.grow(sizeof(unsigned int) * n));  // (zeroed by the root search, its only user)
+    HIP_TRY(c->d_actidx.grow(sizeof(int) * n));
+    HIP_TRY(c->d_chunks.grow(sizeof(int) * 3 * n));  // (first, size) per chunk | position map
+    HIP_TRY(c->p_act.grow(sizeof(int) * n));
+    HIP_TRY(c->p_iv.grow(sizeof(unsigned long long) * n));
+    HIP_TRY(c->p_w.grow(sizeof(double) * 2 * n));
+    HIP_TRY(c->p_overflow.grow(sizeof(unsigned int) * n));
+    HIP_TRY(c->p_deferred.grow(sizeof(unsigned int)));
+    HIP_TRY(c->lists.reserve(4 * n));  // omega order | chunks | position map of a fill; the live matrices of an LU
     if (!c->d_rounds) {
-        HIP_TRY(malloc_retry((void**)&c->d_rounds, (16 + 8192) * sizeof(unsigned long long)));  // (+ per-tile ticks of the diagnostic build)
+        HIP_TRY(c->d_rounds.grow((16 + 8192) * sizeof(unsigned long long)));  // (+ per-tile ticks of the diagnostic build)
         HIP_TRY(hipMemset(c->d_rounds, 0, (16 + 8192) * sizeof(unsigned long long)));
     }
-    c->cap = nb;
     return EMME_OK;
 }
 
 // which matrix sets a call needs: bit0 M, bit1 Mold, bit2 Mp, bit3 work
 int ensure_mats(emme_ctx* c, int nb, int sets) {
-    if (nb > c->mat_cap) {
-        auto F = [](double*& p) {
-            if (p) (void)hipFree(p);
-            p = nullptr;
-        };
-        F(c->d_M), F(c->d_Mold), F(c->d_Mp), F(c->d_work);
-        c->mat_cap = nb;
-    }
-    const size_t bytes = mat_doubles(c) * sizeof(double) * (size_t)c->mat_cap;
-    if ((sets & 1) && !c->d_M) HIP_TRY(malloc_retry((void**)&c->d_M, bytes));
-    if ((sets & 2) && !c->d_Mold) HIP_TRY(malloc_retry((void**)&c->d_Mold, bytes));
-    if ((sets & 4) && !c->d_Mp) HIP_TRY(malloc_retry((void**)&c->d_Mp, bytes));
-    if ((sets & 8) && !c->d_work) HIP_TRY(malloc_retry((void**)&c->d_work, bytes));
+    const size_t bytes = mat_doubles(c) * sizeof(double) * (size_t)nb;
+    DeviceBuffer<double>* mats[4] = {&c->d_M, &c->d_Mold, &c->d_Mp, &c->d_work};
+    for (int k = 0; k < 4; ++k)
+        if (sets & (1 << k)) HIP_TRY(mats[k]->grow(bytes));
     return EMME_OK;
 }
 
@@ -230,30 +201,15 @@ hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, con
     // needs helper workgroups (>= 2 per matrix, all resident); otherwise the unblocked kernel
     const bool fits = trace_solve_blocked_lds(n) <= 150 * 1024;
     if (!force_unblocked && (fits || n <= 1024)) {
-        const size_t need = trace_solve_blocked_scratch(n, nbatch);
-        if (need > c->lu_scratch_bytes) {
-            if (c->d_lu_scratch) (void)hipFree(c->d_lu_scratch);
-            c->d_lu_scratch = nullptr, c->lu_scratch_bytes = 0;
-            hipError_t e = hipMalloc(&c->d_lu_scratch, need);
-            if (e != hipSuccess) return e;
-            c->lu_scratch_bytes = need;
-        }
+        hipError_t e = c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, nbatch));
+        if (e != hipSuccess) return e;
         // dense list of the live matrices (h_active: host copy of `active`, null = all live)
         int n_live = nbatch;
         int* lu_slot = nullptr;
         if (h_active) {
-            if (nbatch > c->lu_items_cap) {
-                if (c->d_lu_items) (void)hipFree(c->d_lu_items);
-                if (c->h_lu_items) (void)hipHostFree(c->h_lu_items);
-                c->d_lu_items = nullptr, c->h_lu_items = nullptr, c->lu_items_cap = 0;
-                hipError_t e = hipMalloc((void**)&c->d_lu_items, sizeof(int) * nbatch);
-                // pinned, two slots used in turn: the device reads a slot (k_stage_ints) while the host
-                // may already be writing the next launch's list
-                if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_lu_items, sizeof(int) * 2 * nbatch);
-                if (e != hipSuccess) return e;
-                c->lu_items_cap = nbatch;
-            }
-            lu_slot = c->h_lu_items + (size_t)(c->lu_items_turn++ & 1u) * c->lu_items_cap;
+            e = c->d_lu_items.grow(sizeof(int) * nbatch);
+            if (e == hipSuccess) e = c->lists.take(nbatch, &lu_slot);
+            if (e != hipSuccess) return e;
             n_live = 0;
             for (int b = 0; b < nbatch; ++b)
                 if (h_active[b]) lu_slot[n_live++] = b;
@@ -275,12 +231,13 @@ hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, con
         c->last_lu_nwg = nwg;
         const int* d_items = nullptr;
         if (nwg > 1 && h_active) {
-            hipError_t e = launch_stage_ints(lu_slot, c->d_lu_items, n_live, nullptr, 0, c->stream);
+            e = launch_stage_ints(lu_slot, c->d_lu_items, n_live, nullptr, 0, c->stream);
+            if (e == hipSuccess) e = c->lists.read_on(c->stream);
             if (e != hipSuccess) return e;
             d_items = c->d_lu_items;
         }
-        const hipError_t e = launch_trace_solve_blocked(n, nbatch, A, B, active, tr, info, nwg, d_items, n_live,
-                                                        c->d_lu_scratch, c->stream, c->opt.lu_group_min_n, c->opt.lu_spin_limit);
+        e = launch_trace_solve_blocked(n, nbatch, A, B, active, tr, info, nwg, d_items, n_live, c->d_lu_scratch, c->stream,
+                                       c->opt.lu_group_min_n, c->opt.lu_spin_limit);
         if (e != hipErrorNotSupported) return e;
         (void)hipGetLastError();  // chunked build not possible here (one workgroup per matrix, or no room)
         c->last_lu_nwg = 1;
@@ -421,13 +378,12 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
         for (int i = 0; i + off < N; ++i) pairs.push_back(make_ushort2((unsigned short)i, (unsigned short)(i + off)));
     c->npairs = (int)pairs.size();
 
-    int rc = EMME_OK;
     auto fail = [&](int code) {
         emme_ctx_destroy(c);
         return code;
     };
-    if (malloc_retry((void**)&c->d_tab, tab.size() * sizeof(double)) != hipSuccess ||
-        malloc_retry((void**)&c->d_pairs, pairs.size() * sizeof(ushort2)) != hipSuccess) {
+    if (c->d_tab.grow(tab.size() * sizeof(double)) != hipSuccess ||
+        c->d_pairs.grow(pairs.size() * sizeof(ushort2)) != hipSuccess) {
         set_error("hipMalloc failed for tables");
         return fail(EMME_ENOMEM);
     }
@@ -436,7 +392,6 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
         set_error("hipMemcpy failed for tables");
         return fail(EMME_EDEVICE);
     }
-    (void)rc;
     *out = c;
     return EMME_OK;
 }
@@ -446,35 +401,6 @@ void emme_ctx_destroy(emme_ctx_t* c) {
     (void)hipSetDevice(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     else (void)hipDeviceSynchronize();
-    auto F = [](auto* p) {
-        if (p) (void)hipFree((void*)p);
-    };
-    F(c->d_tab), F(c->d_pairs), F(c->d_omega), F(c->d_domega), F(c->d_tr), F(c->d_active),
-        F(c->d_iters), F(c->d_info), F(c->d_status), F(c->d_intervals), F(c->d_actidx), F(c->d_chunks), F(c->d_M),
-        F(c->d_Mold),
-        F(c->d_Mp), F(c->d_work), F(c->d_iterates), F(c->d_rounds);
-    for (int k = 0; k < 2; ++k) {
-        // the big buffers go to the process-wide pool for the next context
-        pool_free(c->d_recs[k], c->recs_bytes[k], c->device);
-        F(c->d_ttab[k]), F(c->d_wtab[k]), F(c->d_tile_poison[k]);
-        for (int e = 0; e < NODE_CACHE_MAX_SUB - 1; ++e) pool_free(c->d_recs_ext[k][e], c->recs_ext_bytes[k][e], c->device);
-    }
-    F(c->d_scale);
-    F(c->d_etab);
-    F(c->d_btab);
-    F(c->d_lu_scratch);
-    F(c->d_lu_items);
-    if (c->h_lu_items) (void)hipHostFree(c->h_lu_items);
-    if (c->p_act) (void)hipHostFree(c->p_act);
-    if (c->p_iv) (void)hipHostFree(c->p_iv);
-    if (c->p_w) (void)hipHostFree(c->p_w);
-    if (c->p_lists) (void)hipHostFree(c->p_lists);
-    if (c->p_deferred) (void)hipHostFree(c->p_deferred);
-    if (c->p_overflow) (void)hipHostFree(c->p_overflow);
-    F(c->d_overflow);
-    F(c->d_worklist), F(c->d_worklist_count), F(c->d_defer_info);
-    for (auto& s : c->spans) (void)hipEventDestroy(s.a), (void)hipEventDestroy(s.b);
-    for (auto e : c->free_events) (void)hipEventDestroy(e);
     delete c;
 }
 
@@ -487,7 +413,7 @@ int emme_ctx_set_options(emme_ctx_t* c, const emme_options_t* opt) {
     const bool layout_differs = opt->fill != c->opt.fill || (opt->phase_table != 0) != (c->opt.phase_table != 0) ||
                                 (opt->em_shared != 0) != (c->opt.em_shared != 0);
     if (layout_differs) {
-        if (c->d_recs[0] || c->d_recs[1]) {
+        if (c->cache[0].recs || c->cache[1].recs) {
             set_error("emme_ctx_set_options: fill / phase_table / em_shared fix the layout of the node cache, which exists already");
             return EMME_EINVAL;
         }
@@ -496,7 +422,7 @@ int emme_ctx_set_options(emme_ctx_t* c, const emme_options_t* opt) {
         c->folded = opt->phase_table != 0;
         c->tiled = wants_tiled(c->p, es, c->folded, opt->fill);
     }
-    if (opt->node_cache_gb > 0.0 && c->cache_depth == -2 && !c->d_recs[0] && !c->d_recs[1])
+    if (opt->node_cache_gb > 0.0 && c->cache_depth == -2 && !c->cache[0].recs && !c->cache[1].recs)
         c->cache_depth = -1;  // a budget after "no cache": decide again
     if (opt->lu_split != c->opt.lu_split) c->lu_one_wg = false;
     c->opt = *opt;
@@ -649,17 +575,11 @@ int emme_trace_solve_batch(emme_ctx_t* c, int n, int nbatch, double* A, double* 
     }
     const size_t bytes = (size_t)n * n * 2 * sizeof(double) * nbatch;
     double *dA = A, *dB = B;
-    struct Staging {  // device copies of host operands, released on every way out
-        double *a = nullptr, *b = nullptr;
-        ~Staging() {
-            if (a) (void)hipFree(a);
-            if (b) (void)hipFree(b);
-        }
-    } st;
+    DeviceBuffer<double> st_a, st_b;  // device copies of host operands
     if (!devA) {
-        HIP_TRY(malloc_retry((void**)&st.a, bytes));
-        HIP_TRY(malloc_retry((void**)&st.b, bytes));
-        dA = st.a, dB = st.b;
+        HIP_TRY(st_a.grow(bytes));
+        HIP_TRY(st_b.grow(bytes));
+        dA = st_a, dB = st_b;
         HIP_TRY(hipMemcpyAsync(dA, A, bytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(dB, B, bytes, hipMemcpyHostToDevice, c->stream));
     }
@@ -689,26 +609,16 @@ int emme_qr_secant_batch(emme_ctx_t* c, int n, int nbatch, const double* A, cons
         return EMME_EINVAL;
     }
     const size_t bytes = (size_t)n * n * 2 * sizeof(double) * nbatch;
-    double *dA = nullptr, *dB = nullptr, *dW = nullptr;
-    auto release = [&]() {
-        if (dW) (void)hipFree(dW);
-        if (!devA && dA) (void)hipFree(dA);
-        if (!devA && dB) (void)hipFree(dB);
-    };
-    if (malloc_retry((void**)&dW, bytes) != hipSuccess) {
+    const double *dA = A, *dB = B;
+    DeviceBuffer<double> dW, st_a, st_b;  // transposed work copy; device copies of host operands
+    if (dW.grow(bytes) != hipSuccess || (!devA && (st_a.grow(bytes) != hipSuccess || st_b.grow(bytes) != hipSuccess))) {
         set_error("hipMalloc failed");
         return EMME_ENOMEM;
     }
-    if (devA) {
-        dA = const_cast<double*>(A), dB = const_cast<double*>(B);
-    } else {
-        if (malloc_retry((void**)&dA, bytes) != hipSuccess || malloc_retry((void**)&dB, bytes) != hipSuccess) {
-            release();
-            set_error("hipMalloc failed");
-            return EMME_ENOMEM;
-        }
-        (void)hipMemcpyAsync(dA, A, bytes, hipMemcpyHostToDevice, c->stream);
-        (void)hipMemcpyAsync(dB, B, bytes, hipMemcpyHostToDevice, c->stream);
+    if (!devA) {
+        dA = st_a, dB = st_b;
+        (void)hipMemcpyAsync(st_a, A, bytes, hipMemcpyHostToDevice, c->stream);
+        (void)hipMemcpyAsync(st_b, B, bytes, hipMemcpyHostToDevice, c->stream);
     }
     hipError_t e;
     {
@@ -719,7 +629,6 @@ int emme_qr_secant_batch(emme_ctx_t* c, int n, int nbatch, const double* A, cons
     if (e == hipSuccess) e = hipMemcpyAsync(q, c->d_tr, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    release();
     if (e != hipSuccess) {
         set_error(hipGetErrorString(e));
         return EMME_EDEVICE;
@@ -805,12 +714,7 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
     const int stride = step_limit + 1;
     if (iterates) {
         const size_t need = (size_t)n * stride * 2;
-        if (need > c->iterates_cap) {
-            if (c->d_iterates) (void)hipFree(c->d_iterates);
-            c->d_iterates = nullptr;
-            HIP_TRY(malloc_retry((void**)&c->d_iterates, need * sizeof(double)));
-            c->iterates_cap = need;
-        }
+        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
         std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
         HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -914,7 +818,7 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
                                          c->opt.skip_lost ? c->d_status : nullptr));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
-        std::copy(c->p_w, c->p_w + 2 * (size_t)n, h_w.begin());
+        std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
         if (pending) {
             take_pending();
             bool any = false;
@@ -975,17 +879,9 @@ int emme_bessel_batch(const double* z, int n, double* out) {
         set_error("no HIP device available (the MI355X path has no CPU fallback)");
         return EMME_EDEVICE;
     }
-    double *dz = nullptr, *dout = nullptr;
-    struct Free {
-        double*& a;
-        double*& b;
-        ~Free() {
-            if (a) (void)hipFree(a);
-            if (b) (void)hipFree(b);
-        }
-    } guard{dz, dout};
-    HIP_TRY(hipMalloc((void**)&dz, sizeof(double) * 2 * n));
-    HIP_TRY(hipMalloc((void**)&dout, sizeof(double) * 8 * n));
+    DeviceBuffer<double> dz, dout;
+    HIP_TRY(dz.grow(sizeof(double) * 2 * n));
+    HIP_TRY(dout.grow(sizeof(double) * 8 * n));
     HIP_TRY(hipMemcpy(dz, z, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
     HIP_TRY(launch_bessel_probe(dz, n, dout, nullptr));
     HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
@@ -1007,30 +903,22 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
     int rc = ensure_batch(c, nbatch);
     if (rc) return rc;
     const size_t mbytes = (size_t)n * n * 2 * sizeof(double);
-    struct Tmp {  // device scratch of this call, released on every way out
-        double *a = nullptr, *b = nullptr, *v = nullptr;
-        int *info = nullptr, *maps = nullptr;
-        ~Tmp() {
-            if (a) (void)hipFree(a);
-            if (b) (void)hipFree(b);
-            if (v) (void)hipFree(v);
-            if (info) (void)hipFree(info);
-            if (maps) (void)hipFree(maps);
-        }
-    } t;
+    // device scratch of this call
+    DeviceBuffer<double> t_a, t_b, t_v;
+    DeviceBuffer<int> t_info, t_maps;
     // work copy the factorisation overwrites: the context's LU work set after a root search, else a buffer of its own
     double* work = nullptr;
-    if (!M && c->d_work && c->mat_cap >= nbatch) {
+    if (!M && c->d_work.bytes() >= mbytes * nbatch) {
         work = c->d_work;
         HIP_TRY(hipMemcpyAsync(work, c->d_M, mbytes * nbatch, hipMemcpyDeviceToDevice, c->stream));
     } else {
-        HIP_TRY(malloc_retry((void**)&t.a, mbytes * nbatch));
-        work = t.a;
+        HIP_TRY(t_a.grow(mbytes * nbatch));
+        work = t_a;
         const double* src = M ? M : c->d_M;
         HIP_TRY(hipMemcpyAsync(work, src, mbytes * nbatch, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     }
-    HIP_TRY(malloc_retry((void**)&t.v, sizeof(double) * 2 * (size_t)n * nbatch));
-    HIP_TRY(malloc_retry((void**)&t.info, sizeof(int) * nbatch));
+    HIP_TRY(t_v.grow(sizeof(double) * 2 * (size_t)n * nbatch));
+    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
     const bool one_wg = trace_solve_blocked_lds(n) <= 150 * 1024;  // the whole L21 panel in one workgroup's LDS
     // two sweeps at a converged root; the rest is for matrices that are not singular (chains that never converged):
     // a launch lasts as long as its slowest matrix, 0.18 ms per sweep at n = 256.  Measured on the 128 matrices of the
@@ -1042,14 +930,8 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
         // multi-workgroup kernel of the Newton step factors (two workgroups per matrix, which must be resident
         // together: slices of at most half the compute units; its right-hand side is a dummy).
         const int slice_max = one_wg ? nbatch : std::max(1, c->n_cu / 2);
-        const size_t need = trace_solve_blocked_scratch(n, std::min(nbatch, slice_max));
-        if (need > c->lu_scratch_bytes) {
-            if (c->d_lu_scratch) (void)hipFree(c->d_lu_scratch);
-            c->d_lu_scratch = nullptr, c->lu_scratch_bytes = 0;
-            HIP_TRY(malloc_retry(&c->d_lu_scratch, need));
-            c->lu_scratch_bytes = need;
-        }
-        if (!one_wg) HIP_TRY(malloc_retry((void**)&t.b, mbytes * std::min(nbatch, slice_max)));
+        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, std::min(nbatch, slice_max))));
+        if (!one_wg) HIP_TRY(t_b.grow(mbytes * std::min(nbatch, slice_max)));
         for (int b0 = 0; b0 < nbatch; b0 += slice_max) {
             const int nb = std::min(slice_max, nbatch - b0);
             double* a0 = work + (size_t)b0 * n * n * 2;
@@ -1057,8 +939,8 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
             if (one_wg) {
                 HIP_TRY(launch_lu_inplace(n, nb, a0, nullptr, nb, c->d_info, c->d_lu_scratch, c->stream));
             } else {
-                HIP_TRY(hipMemsetAsync(t.b, 0, mbytes * nb, c->stream));
-                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, t.b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
+                HIP_TRY(hipMemsetAsync(t_b, 0, mbytes * nb, c->stream));
+                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, t_b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
                                                                 c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
@@ -1067,16 +949,16 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
                 }
             }
             HIP_TRY(launch_null_iterate(n, a0, trace_solve_rowmaps(c->d_lu_scratch, n, nb), trace_solve_nb(), nullptr, nb,
-                                        c->d_info, t.v + (size_t)b0 * n * 2, t.info + b0, max_sweeps, c->stream));
+                                        c->d_info, t_v + (size_t)b0 * n * 2, t_info + b0, max_sweeps, c->stream));
         }
     } else {
-        HIP_TRY(malloc_retry((void**)&t.maps, sizeof(int) * (size_t)n * nbatch));
+        HIP_TRY(t_maps.grow(sizeof(int) * (size_t)n * nbatch));
         ScopedSpan sp(c, K_NULL);
-        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, t.maps, c->d_info, c->stream));
-        HIP_TRY(launch_null_iterate(n, work, t.maps, n, nullptr, nbatch, c->d_info, t.v, t.info, max_sweeps, c->stream));
+        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, t_maps, c->d_info, c->stream));
+        HIP_TRY(launch_null_iterate(n, work, t_maps, n, nullptr, nbatch, c->d_info, t_v, t_info, max_sweeps, c->stream));
     }
-    HIP_TRY(hipMemcpyAsync(vecs, t.v, sizeof(double) * 2 * (size_t)n * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, t.info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(vecs, t_v, sizeof(double) * 2 * (size_t)n * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return EMME_OK;
 }

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/emme_hip.h"
+#include "buffers.hpp"
 
 namespace emme {
 void set_error(const std::string& msg);
@@ -88,8 +89,7 @@ int rccl_fail(const char* what, ncclResult_t rc) {
 struct emme_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1, device = 0;
-    double *d_send = nullptr, *d_recv = nullptr;
-    size_t cap = 0;  // items per rank the device buffers hold
+    emme::DeviceBuffer<double> d_send, d_recv;
 };
 
 static_assert(EMME_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "ncclUniqueId is passed through as bytes");
@@ -190,8 +190,6 @@ int emme_comm_create(const unsigned char* id, int rank, int world, int device, e
 void emme_comm_destroy(emme_comm_t* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    if (c->d_send) (void)hipFree(c->d_send);
-    if (c->d_recv) (void)hipFree(c->d_recv);
     Rccl* r = rccl();
     if (r->why.empty() && c->comm) (void)r->CommDestroy(c->comm);
     delete c;
@@ -212,16 +210,10 @@ int emme_gather_roots(emme_comm_t* c, void* hip_stream, const double* roots, con
     if (!r) return EMME_EDEVICE;
     if (hipSetDevice(c->device) != hipSuccess) return EMME_EDEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
-    if (m > c->cap) {
-        if (c->d_send) (void)hipFree(c->d_send);
-        if (c->d_recv) (void)hipFree(c->d_recv);
-        c->d_send = c->d_recv = nullptr, c->cap = 0;
-        if (hipMalloc((void**)&c->d_send, m * 4 * sizeof(double)) != hipSuccess ||
-            hipMalloc((void**)&c->d_recv, m * 4 * sizeof(double) * c->world) != hipSuccess) {
-            emme::set_error("hipMalloc failed for the gather buffers");
-            return EMME_ENOMEM;
-        }
-        c->cap = m;
+    if (c->d_send.grow(m * 4 * sizeof(double)) != hipSuccess ||
+        c->d_recv.grow(m * 4 * sizeof(double) * c->world) != hipSuccess) {
+        emme::set_error("hipMalloc failed for the gather buffers");
+        return EMME_ENOMEM;
     }
     std::vector<double> all(m * 4 * c->world);
     if (hipMemcpyAsync(c->d_send, pack.data(), pack.size() * sizeof(double), hipMemcpyHostToDevice, st) != hipSuccess)

@@ -42,11 +42,20 @@ struct AssembleLaunch {
     int defer_one_group = 0;   // deferred integrals by one lane group each
     int dense_min_cols = 3;    // dense fill: columns that must need an interval for the MFMA path
 };
-// lanes-are-nodes kernel; with a node cache (g != null) it reads cached records where they exist
-hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream, const NodeCacheGeom* g = nullptr,
-                           const void* const recs[2] = nullptr,
-                           const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1] = nullptr,
-                           const void* const ttab[2] = nullptr, const void* const wtab[2] = nullptr);
+// What the launchers that read the node cache see of it: its geometry and, per contour class (omi = +1, -1), the
+// main records, the run-time subtrees (null if absent), the T table, the moment-factor table and the tile-poison
+// flags (null where the context has none), plus the half-widths of the cached intervals.
+struct NodeCacheView {
+    const NodeCacheGeom* geom;
+    const void* recs[2];
+    const void* recs_ext[2][NODE_CACHE_MAX_SUB - 1];
+    const void* ttab[2];
+    const void* wtab[2];
+    const unsigned char* tile_poison[2];
+    const double* scale;
+};
+// lanes-are-nodes kernel, without the node cache
+hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream);
 // omega-lane form (assemble_wl.hip): the n_act batch items listed in act_idx (device) share
 // the omega-independent node data; L.active is ignored.
 hipError_t launch_assemble_wl(const AssembleLaunch& L, const int* act_idx, int n_act,
@@ -62,18 +71,11 @@ hipError_t launch_node_cache(const AssembleLaunch& L, const NodeCacheGeom& g, in
                              void* recs, void* ttab, void* wtab, double* scale, bool folded,
                              hipStream_t stream);
 // electromagnetic fill on the shared layout: a lane walks the three moments of a pair together
-hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheGeom& g,
-                                     const void* const recs[2],
-                                     const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                     const void* const ttab[2], const void* const wtab[2],
-                                     const double* scale, const void* etab, unsigned long long* worklist,
-                                     unsigned int* worklist_count, unsigned long long* defer_info,
-                                     const int* act_idx, int n_act, const void* chunks, int nchunks,
-                                     hipStream_t stream);
-hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheGeom& g,
-                                  const void* const recs[2],
-                                  const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                  const void* const ttab[2], const double* scale,
+hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheView& cache, const void* etab,
+                                     unsigned long long* worklist, unsigned int* worklist_count,
+                                     unsigned long long* defer_info, const int* act_idx, int n_act,
+                                     const void* chunks, int nchunks, hipStream_t stream);
+hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheView& cache,
                                   const void* etab /*phase table of this launch, or null*/,
                                   unsigned long long* worklist, unsigned int* worklist_count,
                                   unsigned long long* defer_info, const int* act_idx, int n_act,
@@ -81,16 +83,14 @@ hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheGeom& 
                                   hipStream_t stream);
 // exp(T omega) for every cached interval/node and the n_act omegas of a launch: etab is
 // [n_intervals][GW][n_act] complex (the records must be in the folded form)
-hipError_t launch_phase_table(int gk_points, int n_intervals, const void* const ttab[2],
+hipError_t launch_phase_table(int gk_points, int n_intervals, const NodeCacheView& cache,
                               const double* omega, const int* act_idx, int n_act, void* etab,
                               hipStream_t stream);
-// integrals deferred by the cached kernels, recomputed by k_assemble_coop (a workgroup each)
+// integrals deferred by the cached kernels, recomputed by k_assemble_coop (a workgroup each); cache null: from
+// scratch, without the node cache
 hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long long* worklist,
-                                const unsigned int* count, const NodeCacheGeom* g,
-                                const void* const recs[2],
-                                const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1],
-                                const void* const ttab[2], const void* const wtab[2], bool folded,
-                                hipStream_t stream, bool tiled = false, const unsigned char* const tile_poison[2] = nullptr);
+                                const unsigned int* count, const NodeCacheView* cache, bool folded,
+                                hipStream_t stream, bool tiled = false);
 
 // ---- dense (matrix-core) fill: assemble_dense.hip (electrostatic GK15; electromagnetic GK31) ------
 // tiled record layout: see node_cache.hpp (gk_points 15: 8 KB per (tile, interval); 31: 16 KB)
@@ -103,18 +103,15 @@ hipError_t launch_node_cache_tiled(const AssembleLaunch& L, const NodeCacheGeom&
 // weighted phase tables of one launch: btab_bytes(cached intervals, chunks of the launch)
 size_t btab_bytes(int nslots, int nchunks, int gk_points = 15);
 // wmap[position in the omega list] = chunk << 8 | position of that omega in its chunk (its first column / nm)
-hipError_t launch_btab(int gk_points, int nm, int nslots, const void* const ttab[2], const void* const wtab[2],
-                       const double* omega, const int* act_idx, int n_act, const int* wmap, int nchunks, void* btab,
-                       hipStream_t stream);
+hipError_t launch_btab(int gk_points, int nm, int nslots, const NodeCacheView& cache, const double* omega,
+                       const int* act_idx, int n_act, const int* wmap, int nchunks, void* btab, hipStream_t stream);
 // act_idx: the launch's omegas, cost-sorted; chunks: int2 (first position, size <= 16 / nm) per chunk.
 // stats (nullable): counters (dense rounds, vector rounds, vector columns, tile tasks, ...)
-hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheGeom& g, const void* const recs[2],
-                                 const void* const recs_ext[2][NODE_CACHE_MAX_SUB - 1], const double* scale,
-                                 const void* btab, unsigned long long* worklist, unsigned int* worklist_count,
+hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& cache, const void* btab,
+                                 unsigned long long* worklist, unsigned int* worklist_count,
                                  unsigned long long* defer_info, const int* act_idx, int n_act,
                                  const void* chunks, int nchunks, unsigned long long* stats, hipStream_t stream,
-                                 const unsigned char* const tile_poison[2] = nullptr, int n_wide = 0,
-                                 unsigned int* overflow = nullptr);
+                                 int n_wide = 0, unsigned int* overflow = nullptr);
 
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,

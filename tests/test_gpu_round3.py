@@ -408,6 +408,29 @@ def test_minority_contour_class_goes_uncached(emme, oracle):
         assert np.abs(M[k] - Mo).max() <= TOL_M * np.abs(Mo).max(), (k, ws[k])
 
 
+def test_minority_class_root_search_repeats_bit_for_bit(emme):
+    """A root search at N = 128 (the LU takes several workgroups per matrix and stages its list of live matrices) whose
+    batch holds one chain on the Re omega > 0 side: while that class stays a minority without a cache, every Newton
+    step stages three index lists between two synchronisations -- the majority's fill, the minority's, the LU's.
+    Fixed work (tol = 0, 4 steps: no chain retires, so the split holds throughout; every chain is still moving -- the
+    oracle's last relative step is >= 3e-7 -- so no secant divides by a zero step).  Twice on one context, once on a
+    fresh one: roots, iteration counts and info codes are identical bit for bit."""
+    d = example_tokamak(npoints=128)
+    g = np.append(np.linspace(-1.1, -0.4, 31) + 1j * np.linspace(0.1, 0.4, 31), 0.5 + 0.1j)
+    runs = []
+    with _ctx(emme, d, node_cache_gb=8.0) as ctx:
+        for _ in range(2):
+            runs.append(ctx.solve_roots(g, tol=0.0, step_limit=3))
+            assert ctx.fill_kernel().startswith("k_assemble_dense")
+    with _ctx(emme, d, node_cache_gb=8.0) as ctx:
+        runs.append(ctx.solve_roots(g, tol=0.0, step_limit=3))
+    roots, iters, info = runs[0]
+    assert (iters == 4).all() and (info == 0).all() and roots[-1].real > 0.0, (iters, info, roots[-1])
+    for r, it, inf in runs[1:]:
+        assert np.array_equal(r.view(np.float64), roots.view(np.float64)), np.abs(r - roots).max()
+        assert np.array_equal(it, iters) and np.array_equal(inf, info)
+
+
 # ---- the dense fill serves both quadrature orders, electrostatic and electromagnetic ------------------------------
 @pytest.mark.parametrize("pts,em", [(15, False), (31, False), (15, True), (31, True)])
 def test_dense_fill_every_shape_matches_oracle(emme, oracle, pts, em):
