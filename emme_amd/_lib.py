@@ -76,6 +76,15 @@ class Profile(C.Structure):
 FILL_AUTO, FILL_UNION, FILL_LANES = 0, 1, 2
 
 
+class Contour(C.Structure):
+    """emme_contour_t: the ellipse and the quadrature / probe settings of a region search."""
+
+    _fields_ = [
+        ("size", C.c_int), ("center", C.c_double * 2), ("semi_axes", C.c_double * 2),
+        ("points", C.c_int), ("max_points", C.c_int), ("probes", C.c_int), ("rank_tol", C.c_double),
+    ]
+
+
 class Options(C.Structure):
     """emme_options_t: per-context options (cache budget, fill routing, LU split ...)."""
 
@@ -173,6 +182,12 @@ def load():
     lib.emme_gather_share.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.emme_gather_pack.argtypes = [C.c_int, C.c_int, P, P, P, C.c_int, C.c_int, P]
     lib.emme_gather_unpack.argtypes = [C.c_int, C.c_int, P, P, P, P]
+    lib.emme_version.argtypes = []
+    lib.emme_contour_default.argtypes = [C.POINTER(Contour)]
+    lib.emme_contour_default.restype = None
+    lib.emme_find_roots_in_contour.argtypes = [P, C.POINTER(Contour), C.c_double, C.c_int, C.c_int, P, P, P, P, P, P]
+    lib.emme_contour_moments_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P, P, P]
+    lib.emme_contour_eigs.argtypes = [C.c_int, C.c_int, P, P, C.c_double, C.c_int, P, P, P]
     _LIB = lib
     return lib
 
@@ -250,6 +265,39 @@ def null_vector(M) -> np.ndarray:
     v = np.zeros(M.shape[0], dtype=np.complex128)
     _check(load().emme_null_vector(M.ctypes.data, M.shape[0], v.ctypes.data))
     return v
+
+
+def contour_default(**kw) -> Contour:
+    """emme_contour_default, then the given fields (center / semi_axes as complex or pairs)."""
+    c = Contour()
+    load().emme_contour_default(C.byref(c))
+    for k, v in kw.items():
+        if not hasattr(c, k):
+            raise TypeError(f"unknown contour field {k!r}")
+        if k in ("center", "semi_axes"):
+            v = (v.real, v.imag) if isinstance(v, complex) else tuple(v)
+            getattr(c, k)[0], getattr(c, k)[1] = float(v[0]), float(v[1])
+        else:
+            setattr(c, k, v)
+    return c
+
+
+def contour_eigs(A0, A1, rank_tol=None, max_eigs=64):
+    """The Beyn step on moments A0, A1 (n x L): (eigenvalues mu of the reduced matrix, numerical rank k, the L
+    singular values of A0).  rank_tol None: the emme_contour_t default."""
+    A0 = np.ascontiguousarray(A0, dtype=np.complex128)
+    A1 = np.ascontiguousarray(A1, dtype=np.complex128)
+    if A0.ndim != 2 or A0.shape != A1.shape:
+        raise ValueError("A0 and A1 must be n x L matrices of one shape")
+    n, L = A0.shape
+    if rank_tol is None:
+        rank_tol = contour_default().rank_tol
+    mu = np.zeros(max(max_eigs, 1), dtype=np.complex128)
+    sig = np.zeros(L)
+    k = C.c_int(0)
+    _check(load().emme_contour_eigs(n, L, A0.ctypes.data, A1.ctypes.data, rank_tol, max_eigs, mu.ctypes.data,
+                                    C.byref(k), sig.ctypes.data))
+    return mu[:min(k.value, max_eigs)].copy(), k.value, sig
 
 
 def scan_values(head, step, tail):
@@ -551,6 +599,54 @@ class Context:
         info = np.zeros(nb, dtype=np.int32)
         _check(self.lib.emme_null_vectors_batch(self.h, n, nb, ptr, v.ctypes.data, info.ctypes.data))
         return v, info
+
+    def find_roots_in_contour(self, center, semi_axes, tol=None, step_limit=None, max_roots=64, **contour):
+        """Every root inside the ellipse omega(t) = center + a cos t + i b sin t, semi_axes = (a, b) (Beyn's contour
+        method + argument-principle count, polished by solve_roots).  contour: points, max_points, probes, rank_tol.
+        Returns a dict: roots (sorted by Im descending), iters, info, winding (-1: unresolved), points_used and
+        complete (winding >= 0 and as many roots as it counts)."""
+        c = contour_default(center=complex(center), semi_axes=tuple(semi_axes), **contour)
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros(max_roots, dtype=np.complex128)
+        iters = np.zeros(max_roots, dtype=np.int32)
+        info = np.zeros(max_roots, dtype=np.int32)
+        nr, w, pu = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self.lib.emme_find_roots_in_contour(self.h, C.byref(c), tol, step_limit, max_roots, roots.ctypes.data,
+                                                   iters.ctypes.data, info.ctypes.data, C.byref(nr), C.byref(w),
+                                                   C.byref(pu)))
+        k = min(nr.value, max_roots)
+        return {"roots": roots[:k].copy(), "iters": iters[:k].copy(), "info": info[:k].copy(), "n_roots": nr.value,
+                "winding": w.value, "points_used": pu.value, "complete": w.value >= 0 and nr.value == w.value}
+
+    def contour_moments(self, M, z, w, L, V=None, device_ptr: int | None = None, v_device_ptr: int | None = None):
+        """X_j = M_j^-1 V, A0 = sum w_j X_j, A1 = sum w_j z_j X_j on the device.  M: [nq, n, n] (or device_ptr with
+        M = (nq, n)), z, w: nq complex, V: n x L or None (internal probes; v_device_ptr: V in device memory).
+        Returns (A0, A1, logdet, info) with logdet[j] = log|det M_j| + i arg det M_j."""
+        if device_ptr is None:
+            M = np.ascontiguousarray(_c128(M))
+            nq, n = M.shape[0], M.shape[1]
+            ptr = M.ctypes.data
+        else:
+            nq, n = M
+            ptr = C.c_void_p(device_ptr)
+        z = _c128(np.atleast_1d(z))
+        w = _c128(np.atleast_1d(w))
+        if z.shape[0] != nq or w.shape[0] != nq:
+            raise ValueError("z and w need one entry per matrix")
+        Vp = None if v_device_ptr is None else C.c_void_p(v_device_ptr)
+        if V is not None and v_device_ptr is None:
+            V = np.ascontiguousarray(_c128(V))
+            if V.shape != (n, L):
+                raise ValueError("V must be n x L")
+            Vp = V.ctypes.data
+        A0 = np.zeros((n, L), dtype=np.complex128)
+        A1 = np.zeros((n, L), dtype=np.complex128)
+        ld = np.zeros(nq, dtype=np.complex128)
+        info = np.zeros(nq, dtype=np.int32)
+        _check(self.lib.emme_contour_moments_batch(self.h, n, nq, ptr, z.ctypes.data, w.ctypes.data, L, Vp,
+                                                   A0.ctypes.data, A1.ctypes.data, ld.ctypes.data, info.ctypes.data))
+        return A0, A1, ld, info
 
     def final_matrix(self, b=0):
         M = np.zeros((self.dim, self.dim), dtype=np.complex128)

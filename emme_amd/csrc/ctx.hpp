@@ -10,6 +10,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <mutex>
 #include <string>
@@ -156,6 +157,15 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
 
 // ---- emme_capi.hip ----------------------------------------------------------------------------------------
 hipEvent_t get_event(emme_ctx* c);
+int ctx_ensure_batch(emme_ctx* c, int nb);  // batch scratch for nb items
+bool ptr_on_device(const void* p);
+// scratch of lu_factor_batch that the caller keeps until what it queued behind the factorisation has run
+struct LuScratch {
+    DeviceBuffer<double> b;  // dummy right-hand sides of the chunked multi-workgroup factorisation
+    DeviceBuffer<int> maps;  // row order of the unblocked factorisation
+};
+int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
+                    const std::function<hipError_t(int b0, int nb, const int* maps, int map_nb, const int* lu_info)>& after);
 
 // host wall time of the cache allocations (hipMalloc of tens of GB: the cold cost of a context)
 struct AllocTimer {

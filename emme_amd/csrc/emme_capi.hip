@@ -282,7 +282,7 @@ int check_method(const emme_ctx* c, int method) {
 extern "C" {
 
 const char* emme_last_error(void) { return g_error.c_str(); }
-int emme_version(void) { return 3; }
+int emme_version(void) { return 4; }
 
 void emme_options_default(emme_options_t* opt) {
     if (opt) options_default(*opt);
@@ -712,6 +712,7 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
     rc = ensure_mats(c, n, 1 | 2 | 4 | 8);
     if (rc) return rc;
     const int stride = step_limit + 1;
+    // (d_iterates is sized by the last call that asked for iterates: a call that does not ask must not write it)
     if (iterates) {
         const size_t need = (size_t)n * stride * 2;
         HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
@@ -814,7 +815,7 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
         {
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters,
-                                         c->d_info, tol, c->d_iterates, j, stride, c->stream, c->p_w,
+                                         c->d_info, tol, iterates ? c->d_iterates.get() : nullptr, j, stride, c->stream, c->p_w,
                                          c->opt.skip_lost ? c->d_status : nullptr));
         }
         HIP_TRY(hipStreamSynchronize(c->stream));
@@ -888,6 +889,60 @@ int emme_bessel_batch(const double* z, int n, double* out) {
     return EMME_OK;
 }
 
+}  // extern "C"
+
+namespace emme {
+
+// Partial-pivot LU of nbatch n x n matrices in place (P M = L U, rows never moved; n <= 2048), by the branch the
+// order allows: k_lu_inplace where the whole L21 panel fits one workgroup's LDS; above that, up to n = 1024, the chunked
+// multi-workgroup kernel of the Newton step (two workgroups per matrix, which must be resident together: slices of at
+// most half the compute units; its right-hand side is a dummy); beyond, k_lu_unblocked_inplace.  After each slice's
+// factorisation `after(b0, nb, maps, map_nb, lu_info)` queues what reads it: matrices b0 .. b0 + nb - 1, their row-order
+// snapshots (logical row x of slice item b is physical row maps[(b ceil(n / map_nb) + x / map_nb) n + x]) and their
+// info (0 or the column at which the factorisation stopped), both valid until the next slice is factored.  Used by
+// emme_null_vectors_batch and the contour solver (contour.hip); the launches are stream-ordered on c->stream.
+int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
+                    const std::function<hipError_t(int, int, const int*, int, const int*)>& after) {
+    const size_t mbytes = (size_t)n * n * 2 * sizeof(double);
+    const bool one_wg = trace_solve_blocked_lds(n) <= 150 * 1024;  // the whole L21 panel in one workgroup's LDS
+    if (one_wg || n <= 1024) {
+        const int slice_max = one_wg ? nbatch : std::max(1, c->n_cu / 2);
+        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, std::min(nbatch, slice_max))));
+        if (!one_wg) HIP_TRY(s.b.grow(mbytes * std::min(nbatch, slice_max)));
+        for (int b0 = 0; b0 < nbatch; b0 += slice_max) {
+            const int nb = std::min(slice_max, nbatch - b0);
+            double* a0 = work + (size_t)b0 * n * n * 2;
+            ScopedSpan sp(c, K_NULL);
+            if (one_wg) {
+                HIP_TRY(launch_lu_inplace(n, nb, a0, nullptr, nb, c->d_info, c->d_lu_scratch, c->stream));
+            } else {
+                HIP_TRY(hipMemsetAsync(s.b, 0, mbytes * nb, c->stream));
+                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, s.b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
+                                                                c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    set_error(std::string(who) + ": the chunked factorisation could not be launched (its two workgroups per matrix must be resident together)");
+                    return EMME_EDEVICE;
+                }
+            }
+            HIP_TRY(after(b0, nb, trace_solve_rowmaps(c->d_lu_scratch, n, nb), trace_solve_nb(), c->d_info));
+        }
+    } else {
+        HIP_TRY(s.maps.grow(sizeof(int) * (size_t)n * nbatch));
+        ScopedSpan sp(c, K_NULL);
+        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, s.maps, c->d_info, c->stream));
+        HIP_TRY(after(0, nbatch, s.maps, n, c->d_info));
+    }
+    return EMME_OK;
+}
+
+int ctx_ensure_batch(emme_ctx* c, int nb) { return ensure_batch(c, nb); }
+bool ptr_on_device(const void* p) { return is_device_ptr(p); }
+
+}  // namespace emme
+
+extern "C" {
+
 // nullSpace (reference include/solver.h:58-112), batched on the device: see nullspace.hip
 int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, double* vecs, int* info) {
     if (!c || !vecs || !info || n < 1 || nbatch < 1) return EMME_EINVAL;
@@ -904,8 +959,8 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
     if (rc) return rc;
     const size_t mbytes = (size_t)n * n * 2 * sizeof(double);
     // device scratch of this call
-    DeviceBuffer<double> t_a, t_b, t_v;
-    DeviceBuffer<int> t_info, t_maps;
+    DeviceBuffer<double> t_a, t_v;
+    DeviceBuffer<int> t_info;
     // work copy the factorisation overwrites: the context's LU work set after a root search, else a buffer of its own
     double* work = nullptr;
     if (!M && c->d_work.bytes() >= mbytes * nbatch) {
@@ -919,44 +974,19 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
     }
     HIP_TRY(t_v.grow(sizeof(double) * 2 * (size_t)n * nbatch));
     HIP_TRY(t_info.grow(sizeof(int) * nbatch));
-    const bool one_wg = trace_solve_blocked_lds(n) <= 150 * 1024;  // the whole L21 panel in one workgroup's LDS
     // two sweeps at a converged root; the rest is for matrices that are not singular (chains that never converged):
     // a launch lasts as long as its slowest matrix, 0.18 ms per sweep at n = 256.  Measured on the 128 matrices of the
     // headline search (worst 1 - overlap against the SVD where the SVD itself determines the vector): 60 sweeps
     // 11.6 ms / 2.7e-14, 30 sweeps 6.7 ms / 8.9e-14, 20 sweeps 4.9 ms / 2.2e-9
     const int max_sweeps = 30;
-    if (one_wg || n <= 1024) {
-        // blocked factorisations: row orders in the LU scratch.  Above the one-workgroup panel the chunked
-        // multi-workgroup kernel of the Newton step factors (two workgroups per matrix, which must be resident
-        // together: slices of at most half the compute units; its right-hand side is a dummy).
-        const int slice_max = one_wg ? nbatch : std::max(1, c->n_cu / 2);
-        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, std::min(nbatch, slice_max))));
-        if (!one_wg) HIP_TRY(t_b.grow(mbytes * std::min(nbatch, slice_max)));
-        for (int b0 = 0; b0 < nbatch; b0 += slice_max) {
-            const int nb = std::min(slice_max, nbatch - b0);
-            double* a0 = work + (size_t)b0 * n * n * 2;
-            ScopedSpan sp(c, K_NULL);
-            if (one_wg) {
-                HIP_TRY(launch_lu_inplace(n, nb, a0, nullptr, nb, c->d_info, c->d_lu_scratch, c->stream));
-            } else {
-                HIP_TRY(hipMemsetAsync(t_b, 0, mbytes * nb, c->stream));
-                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, t_b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
-                                                                c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
-                if (e != hipSuccess) {
-                    (void)hipGetLastError();
-                    set_error("emme_null_vectors_batch: the chunked factorisation could not be launched (its two workgroups per matrix must be resident together)");
-                    return EMME_EDEVICE;
-                }
-            }
-            HIP_TRY(launch_null_iterate(n, a0, trace_solve_rowmaps(c->d_lu_scratch, n, nb), trace_solve_nb(), nullptr, nb,
-                                        c->d_info, t_v + (size_t)b0 * n * 2, t_info + b0, max_sweeps, c->stream));
-        }
-    } else {
-        HIP_TRY(t_maps.grow(sizeof(int) * (size_t)n * nbatch));
-        ScopedSpan sp(c, K_NULL);
-        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, t_maps, c->d_info, c->stream));
-        HIP_TRY(launch_null_iterate(n, work, t_maps, n, nullptr, nbatch, c->d_info, t_v, t_info, max_sweeps, c->stream));
-    }
+    LuScratch scratch;
+    rc = lu_factor_batch(c, n, nbatch, work, scratch, "emme_null_vectors_batch",
+                              [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+                                  return launch_null_iterate(n, work + (size_t)b0 * n * n * 2, maps, map_nb, nullptr,
+                                                             nb, lu_info, t_v + (size_t)b0 * n * 2, t_info + b0,
+                                                             max_sweeps, c->stream);
+                              });
+    if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(vecs, t_v, sizeof(double) * 2 * (size_t)n * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));

@@ -108,7 +108,9 @@ typedef struct emme_options {
 
 const char* emme_last_error(void);
 int emme_params_sizeof(void);
-int emme_version(void); /* 3: emme_options_t, emme_ctx_create_ex / _set_options / _get_options, emme_null_vectors_batch,
+int emme_version(void); /* 4: emme_contour_t, emme_contour_default, emme_find_roots_in_contour,
+                           emme_contour_moments_batch, emme_contour_eigs;
+                           3: emme_options_t, emme_ctx_create_ex / _set_options / _get_options, emme_null_vectors_batch,
                            emme_profile_t grew nullspace_*; 2: cache_* fields, emme_comm_*, emme_gather_roots */
 void emme_options_default(emme_options_t* opt);
 
@@ -223,6 +225,56 @@ int emme_null_vector(const double* M, int n, double* vec /* 2n doubles */);
  * vecs: nbatch*n complex (host), unit 2-norm, arbitrary phase.  info (host, nbatch): 0, k > 0 = column k of the
  * factorisation is exactly zero (no vector: NaN), EMME_ENUMERIC = non-finite result.  n <= 2048. */
 int emme_null_vectors_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, double* vecs, int* info);
+
+/* ---- region search: every root inside a contour (version 4) ---------------------------------------
+ * The reference only polishes guesses (src/main.cpp:19-80).  These entry points answer "which modes lie in this part of
+ * the omega plane": Beyn's contour-integral method (W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, algorithm 1)
+ * turns M(omega_j)^-1 V at N quadrature nodes of an ellipse into candidates for every eigenvalue inside it, the argument
+ * principle on det M(omega_j) at the same nodes counts them, and the context's Newton step (emme_solve_roots) polishes
+ * the candidates to the reference's own roots.  M(omega) is analytic inside one half-plane only (the contour sense
+ * omi = -sign Re omega), so an ellipse must not reach Re omega = 0. */
+typedef struct emme_contour {
+    int size;              /* sizeof(emme_contour_t), set by emme_contour_default */
+    double center[2];      /* c */
+    double semi_axes[2];   /* a along Re omega, b along Im omega; the ellipse must not reach Re omega = 0 */
+    int points;            /* starting node count N (power of two) */
+    int max_points;        /* cap of the nested doubling */
+    int probes;            /* starting L; doubled up to 64 while A0 has full numerical rank */
+    double rank_tol;       /* relative singular-value cut */
+} emme_contour_t;
+/* Defaults (DESIGN.md §11 gives the measurements behind them); center and semi_axes are zero and must be set. */
+void emme_contour_default(emme_contour_t* c);
+
+/* All roots of det M(omega) inside the ellipse omega(t) = c + a cos t + i b sin t, polished by the context's Newton step
+ * (iteration_method), sorted by Im omega descending.  roots: 2*max_roots, iters/info: max_roots (at most max_roots are
+ * written, *n_roots counts all).  *winding = argument-principle count (-1 unresolved at max_points);
+ * *points_used = N at the end.  Complete iff *winding >= 0 && *n_roots == *winding.
+ * The nodes t_j = 2 pi j / N are filled in one batch and factored once (partial-pivot LU, the factors are kept for the
+ * whole call: N dim^2 16 bytes); N doubles by the midpoints while the count is unresolved, L doubles while A0 has full
+ * numerical rank, both on the factors already held.  EMME_EINVAL: an ellipse reaching Re omega = 0, non-positive
+ * semi-axes, points not a power of two >= 4, max_points < points, probes outside 1..64, rank_tol outside (0, 1);
+ * EMME_ECONFIG: dim > 2048; a node whose fill fails (depth cap, non-finite) ends the call with its error, the message
+ * names the node.  Chains that did not converge (info != 0, or the last of step_limit + 1 steps still above tol) are
+ * dropped. */
+int emme_find_roots_in_contour(emme_ctx_t* ctx, const emme_contour_t* c, double tol, int step_limit,
+                               int max_roots, double* roots, int* iters, int* info,
+                               int* n_roots, int* winding, int* points_used);
+
+/* Building block on caller matrices (host or device, nq*n*n complex, not modified):
+ * X_j = M_j^-1 V, A0 = sum w_j X_j, A1 = sum w_j z_j X_j (n*L complex each, host),
+ * logdet[j] = (log|det M_j|, arg det M_j), info[j] as emme_null_vectors_batch.  V NULL = internal probes
+ * (V[i][l] from a counter-based hash of (i, l) with a fixed seed, DESIGN.md §11: the first L columns do not depend on L).
+ * z, w: nq complex each (host).  A matrix with info != 0 has no X_j and is left out of the sums.  n <= 2048, L <= 64. */
+int emme_contour_moments_batch(emme_ctx_t* ctx, int n, int nq, const double* M, const double* z,
+                               const double* w, int L, const double* V, double* A0, double* A1,
+                               double* logdet, int* info);
+
+/* Host only: the Beyn step on given moments (row-major n x L complex).  B = U_k^H A1 W_k S_k^-1 from the thin SVD
+ * A0 = U S W^H (one-sided Jacobi), k = #{s_i > rank_tol s_1}; mu = eigenvalues of B (Hessenberg + shifted QR).
+ * mu: 2*max_eigs (min(k, max_eigs) written), *k = numerical rank used (k == L: the probes may be too few),
+ * sigma (nullable): the L singular values of A0, descending.  Returns EMME_OK, EMME_EINVAL on bad sizes. */
+int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double rank_tol,
+                      int max_eigs, double* mu, int* k, double* sigma);
 
 /* The reference's driver (src/main.cpp:182-338) on an input.json TEXT: one solve, or a
  * parameter scan over every key written {head, step, tail}, with omega continuation.
