@@ -166,6 +166,8 @@ def load():
     lib.emme_qr_secant_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P]
     lib.emme_newton_step_batch.argtypes = [P, P, P, C.c_int, P, P, C.c_int, P]
     lib.emme_solve_roots.argtypes = [P, P, C.c_int, C.c_double, C.c_int, P, P, P, P]
+    lib.emme_assemble_derivative_batch.argtypes = [P, P, C.c_int, P, P, P]
+    lib.emme_solve_roots_newton.argtypes = [P, P, C.c_int, C.c_double, C.c_int, P, P, P, P]
     lib.emme_ctx_get_matrix.argtypes = [P, C.c_int, P]
     lib.emme_null_vector.argtypes = [P, C.c_int, P]
     lib.emme_run_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
@@ -521,6 +523,18 @@ class Context:
                                             C.c_void_p(out_device_ptr), iv.ctypes.data))
         return iv
 
+    def assemble_derivative(self, omegas, want_intervals=False):
+        """M(omega) and the exact M'(omega) of the same quadrature trees, through the uncached kernels:
+        returns (M, Mp[, intervals])."""
+        w = _c128(np.atleast_1d(omegas))
+        nb = w.shape[0]
+        iv = np.zeros(nb, dtype=np.int64)
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        _check(self.lib.emme_assemble_derivative_batch(self.h, w.ctypes.data, nb, M.ctypes.data, Mp.ctypes.data,
+                                                       iv.ctypes.data))
+        return (M, Mp, iv) if want_intervals else (M, Mp)
+
     def assemble_rc(self, omegas) -> int:
         """emme_assemble_batch's return code alone (0, or EMME_ENUMERIC when a matrix holds a non-finite integral)."""
         w = _c128(np.atleast_1d(omegas))
@@ -581,6 +595,21 @@ class Context:
         _check(self.lib.emme_solve_roots(self.h, g.ctypes.data, n, tol, step_limit,
                                          roots.ctypes.data, iters.ctypes.data, info.ctypes.data,
                                          its.ctypes.data if want_iterates else None))
+        return (roots, iters, info, its) if want_iterates else (roots, iters, info)
+
+    def solve_roots_newton(self, guesses, tol=None, step_limit=None, want_iterates=False):
+        """solve_roots with the exact M' (emme_solve_roots_newton): starts at the guesses themselves."""
+        g = _c128(np.atleast_1d(guesses))
+        n = g.shape[0]
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros(n, dtype=np.complex128)
+        iters = np.zeros(n, dtype=np.int32)
+        info = np.zeros(n, dtype=np.int32)
+        its = np.zeros((n, step_limit + 1), dtype=np.complex128) if want_iterates else None
+        _check(self.lib.emme_solve_roots_newton(self.h, g.ctypes.data, n, tol, step_limit, roots.ctypes.data,
+                                                iters.ctypes.data, info.ctypes.data,
+                                                its.ctypes.data if want_iterates else None))
         return (roots, iters, info, its) if want_iterates else (roots, iters, info)
 
     def null_vectors(self, M=None, nbatch=None):

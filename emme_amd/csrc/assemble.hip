@@ -146,6 +146,8 @@ __device__ __forceinline__ cd node_value(const AsmArgs& A, const ClassTables& ct
     return node_eval(d, oc.omega, tc);
 }
 
+// (k_assemble_deriv below is the non-LIST, uncached form of this kernel with M' alongside: a change to the
+// accept / split rule or to the scatter here belongs there too)
 template <int PTS, bool LIST>
 #ifndef EMME_ASM_MIN_WAVES
 #define EMME_ASM_MIN_WAVES 3
@@ -343,6 +345,175 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
     }
 
     if (!LIST && lane_in_group == 0) {
+        if (A.intervals && my_intervals) atomicAdd(&A.intervals[b], my_intervals);
+        if (bad) A.status[b] = 1;
+    }
+}
+
+// M and the exact dM/domega of the same discretised integrals, from scratch: k_assemble<PTS, false>
+// without the node cache, each lane also evaluating F' at its node (integrand_d) and the group summing K' beside K
+// and G.  Only K and G decide accept / split, so the trees, the interval counts and M are those of the plain kernel
+// bit for bit; accepted intervals add scale K' to a second running sum.  (A separate kernel rather than a template
+// flag on k_assemble, whose generated code a shared template changed.)  Md: [nbatch][dim][dim]; no fused secant.
+template <int PTS>
+__global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_deriv(AsmArgs A, double2* Md) {
+    constexpr int GW = PTS == 15 ? 16 : 32;
+    constexpr int GROUPS_PER_BLOCK = 256 / GW;
+    constexpr int MAXD = EMME_MAX_DEPTH;
+    extern __shared__ double lds_tab[];  // eta | g | b  (3N doubles) | per-group (mid, r) stack
+
+    const DevParams& P = A.P;
+    const int b = blockIdx.y;
+    if (A.active && A.active[b] == 0) return;
+    const int N = P.N, dim = P.dim;
+
+    for (int k = threadIdx.x; k < 3 * N; k += blockDim.x) lds_tab[k] = A.tab[k];
+    __syncthreads();
+    const double* eta = lds_tab;
+    const double* gtab = lds_tab + N;
+    const double* btab = lds_tab + 2 * N;
+    double2* stk = reinterpret_cast<double2*>(lds_tab + 3 * N + (3 * N & 1)) + (threadIdx.x / GW) * MAXD;
+
+    double2* Mb = A.M + (size_t)b * dim * dim;
+    double2* Mdb = Md + (size_t)b * dim * dim;
+    OmegaConst oc;
+    oc.omega = mk(A.omega[b].x, A.omega[b].y);
+    oc.omi = -copysign(1.0, oc.omega.x);
+    // an entry of M and the same entry of M'
+    auto store = [&](int r, int c, cd v, cd vd) {
+        const size_t idx = (size_t)r * dim + c;
+        Mb[idx] = make_double2(v.x, v.y);
+        Mdb[idx] = make_double2(vd.x, vd.y);
+    };
+    const cd zero = mk(0.0, 0.0);
+
+    // diagonal (include/solver.h:442-443, 465-470): constant in omega, so 0 in M'
+    if (blockIdx.x == 0) {
+        for (int i = threadIdx.x; i < N; i += blockDim.x) {
+            store(i, i, mk(P.diag_a, 0.0), zero);
+            if (P.nm == 3) {
+                store(i, i + N, zero, zero);
+                store(i + N, i, zero, zero);
+                store(i + N, i + N, mk(P.diag_d * btab[i], 0.0), zero);
+            }
+        }
+    }
+
+    const int lane_in_group = threadIdx.x % GW;
+    const int group = blockIdx.x * GROUPS_PER_BLOCK + threadIdx.x / GW;
+    const int ngroups = gridDim.x * GROUPS_PER_BLOCK;
+    const GkLane gk = gk_lane<PTS>(lane_in_group);
+
+    const double qa = 0.0, qb = M_PI / 2.0;
+    const double inv_scale = 2. / (qb - qa);
+    const int nitems = A.npairs * P.nm;
+
+    int item = group;
+    bool live = item < nitems;
+    int i = 0, j = 0, m = 0;
+    PairConst pc{};
+    double dg = 0.0;
+    int depth = 0;
+    unsigned long long path = 0;
+    double l = qa, r = qb;
+    double abs_tol = 0.0;
+    cd sum = zero, sum_d = zero;
+    unsigned long long my_intervals = 0;
+    int item_intervals = 0;
+    int bad = 0;
+
+    auto load_item = [&]() {
+        const int p = item / P.nm;
+        m = item - p * P.nm;
+        const ushort2 ij = A.pairs[p];
+        i = ij.x, j = ij.y;
+        dg = gtab[i] - gtab[j];
+        pc = make_pair_const(P, eta[i], eta[j], btab[i], btab[j], dg);
+        depth = 0, path = 0, abs_tol = 0.0;
+        l = qa, r = qb;
+        item_intervals = 0;
+        sum = zero, sum_d = zero;
+    };
+    if (live) load_item();
+
+    while (live) {
+        const double mid = (r + l) / 2;
+        const double scale = (r - l) / 2;
+        const double x = __dadd_rn(__dmul_rn(scale, gk.x), mid);
+
+        cd fd;
+        const cd f = integrand_d(x, P, pc, oc, m, fd);
+        const double Kx = group_sum<GW>(gk.wk * f.x), Ky = group_sum<GW>(gk.wk * f.y);
+        const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
+        const double Kdx = group_sum<GW>(gk.wk * fd.x), Kdy = group_sum<GW>(gk.wk * fd.y);
+        ++my_intervals;
+        ++item_intervals;
+
+        // include/functions.h:203-208, 231-247 -- the plain kernel's rule, on K and G alone
+        const double dKx = Kx - Gx, dKy = Ky - Gy;
+        const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
+        double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+        const cd integral = mk(Kx * scale, Ky * scale);
+        err *= scale;
+        const double rel_abs = P.rel_tol * (absK * scale);
+        if (abs_tol == 0.0) abs_tol = rel_abs;
+        bool split = depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal &&
+                     err > rel_abs + P.prec_goal;
+        if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {
+            split = false;
+            bad = 1;
+        }
+        if (split) {
+            stk[depth] = make_double2(mid, r);
+            r = mid;
+            ++depth;
+            path <<= 1;
+        } else {
+            sum = sum + integral;
+            sum_d = sum_d + mk(Kdx * scale, Kdy * scale);
+            ++path;
+            while (depth > 0 && !(path & 1)) {
+                path >>= 1;
+                --depth;
+            }
+            if (depth == 0) {
+                cd kap = mk(P.pref * sum.y, -(P.pref * sum.x));
+                if (kappa_bad(kap)) bad = 1;
+                kap = kap + kappa_e(m, P, pc.de, dg, oc.omega);
+                // kappa' = -i pref sum' + kappa_e', scattered like kappa
+                cd kd = mk(P.pref * sum_d.y, -(P.pref * sum_d.x));
+                if (kappa_bad(kd)) bad = 1;
+                kd = kd + kappa_e_d(m, P, pc.de, dg, oc.omega);
+                if (lane_in_group == 0) {
+                    if (m == 0) {
+                        const double w = -(pair_weight(i, j, N) * P.dx);
+                        const cd v = w * kap, vd = w * kd;
+                        store(i, j, v, vd);
+                        store(j, i, v, vd);
+                    } else if (m == 1) {
+                        const cd v = P.dx * kap, vd = P.dx * kd;
+                        store(i, j + N, v, vd);
+                        store(j, i + N, -v, -vd);
+                        store(i + N, j, -v, -vd);
+                        store(j + N, i, v, vd);
+                    } else {
+                        const cd v = P.dx * kap, vd = P.dx * kd;
+                        store(i + N, j + N, v, vd);
+                        store(j + N, i + N, v, vd);
+                    }
+                }
+                item += ngroups;
+                live = item < nitems;
+                if (live) load_item();
+            } else {
+                const double2 pr = stk[depth - 1];
+                l = pr.x;
+                r = pr.y;
+            }
+        }
+    }
+
+    if (lane_in_group == 0) {
         if (A.intervals && my_intervals) atomicAdd(&A.intervals[b], my_intervals);
         if (bad) A.status[b] = 1;
     }
@@ -596,7 +767,13 @@ hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream) {
     dim3 grid((unsigned)gx, (unsigned)L.nbatch), block(256);
     const size_t lds = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double) +
                        (size_t)groups_per_block * EMME_MAX_DEPTH * sizeof(double2);
-    if (L.gk_points == 15)
+    if (L.Md) {
+        if (L.Mold) return hipErrorInvalidValue;  // (the derivative fill has no fused secant)
+        if (L.gk_points == 15)
+            hipLaunchKernelGGL((k_assemble_deriv<15>), grid, block, lds, stream, A, (double2*)L.Md);
+        else
+            hipLaunchKernelGGL((k_assemble_deriv<31>), grid, block, lds, stream, A, (double2*)L.Md);
+    } else if (L.gk_points == 15)
         hipLaunchKernelGGL((k_assemble<15, false>), grid, block, lds, stream, A);
     else
         hipLaunchKernelGGL((k_assemble<31, false>), grid, block, lds, stream, A);

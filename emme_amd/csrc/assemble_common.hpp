@@ -133,6 +133,19 @@ __device__ __forceinline__ cd kappa_e(int m, const DevParams& P, double de, doub
     return mk(0.0, 0.0);
 }
 
+// d kappa_e / d omega (the derivative fills): m = 1: -i c; m = 2: f (de (2 omega - ws_e) - b1e vt / qR); m = 0: 0
+__device__ __forceinline__ cd kappa_e_d(int m, const DevParams& P, double de, double dg, cd omega) {
+    if (m == 1) {
+        const double c = P.qR / (2.0 * P.vt * P.tau) * (de / fabs(de));
+        return mk(0.0, -c);
+    }
+    if (m == 2) {
+        const double f = (P.qR * P.qR) / (2.0 * P.vt * P.vt * P.tau) * de / fabs(de);
+        const double b1e = P.cbe * dg;
+        return f * mk(de * (2.0 * omega.x - P.omega_s_e) - b1e * P.vt / P.qR, de * (2.0 * omega.y));
+    }
+    return mk(0.0, 0.0);
+}
 
 // SingularityHandler weight for i < j (src/singularity_handler.cpp:4-20): end-corrected
 // band near the diagonal, 1 elsewhere, minus one half on the last column.

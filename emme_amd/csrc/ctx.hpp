@@ -154,6 +154,9 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
                 const int* host_active, double* d_M, const double* d_Mold, double* d_Mp,
                 const double* d_domega, const unsigned long long* cost = nullptr,
                 const double* host_omega = nullptr, bool newton_loop = false, bool force_uncached = false);
+// M and the exact dM/domega through the uncached derivative kernels (ctx_fill.hip; the node cache is not touched)
+int do_assemble_deriv(emme_ctx* c, int nbatch, const double* d_omega, const int* d_active, const int* host_active,
+                      double* d_M, double* d_Md);
 
 // ---- emme_capi.hip ----------------------------------------------------------------------------------------
 hipEvent_t get_event(emme_ctx* c);

@@ -336,4 +336,52 @@ int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_act
     return EMME_OK;
 }
 
+
+// M and the exact dM/domega of the items host_active marks (null = all): the uncached kernels only --
+// batches of wl_min or more through k_assemble_wl_deriv, smaller ones through k_assemble_deriv -- on every context,
+// without reading or growing the node cache.  d_active: device copy of host_active (null = all).  The uncached branch
+// of do_assemble above with L.Md set; last_fill_mode is left to the plain fills (it names their kernel).
+int do_assemble_deriv(emme_ctx* c, int nbatch, const double* d_omega, const int* d_active, const int* host_active,
+                      double* d_M, double* d_Md) {
+    AssembleLaunch L;
+    L.P = c->P;
+    L.gk_points = c->p.integration_start_points;
+    L.nbatch = nbatch;
+    L.npairs = c->npairs;
+    L.tab = c->d_tab;
+    L.pairs = c->d_pairs;
+    L.omega = d_omega;
+    L.active = d_active;
+    L.M = d_M;
+    L.Mold = nullptr;
+    L.Mp = nullptr;
+    L.domega = nullptr;
+    L.Md = d_Md;
+    L.intervals = c->d_intervals;
+    L.status = c->d_status;
+    L.rounds = c->d_rounds;
+    std::vector<int>& idx = c->h_actidx;
+    idx.clear();
+    for (int b = 0; b < nbatch; ++b)
+        if (!host_active || host_active[b] != 0) idx.push_back(b);
+    const int n_act = (int)idx.size();
+    if (n_act == 0) return EMME_OK;
+    ScopedSpan s(c, K_ASM);
+    if (n_act >= c->opt.wl_min) {
+        const int gw = L.gk_points == 15 ? 16 : 32;
+        L.items_per_group = items_per_group_for(c, (n_act + gw - 1) / gw);
+        int* slot = nullptr;
+        HIP_TRY(c->lists.take(n_act, &slot));
+        std::copy(idx.begin(), idx.end(), slot);
+        HIP_TRY(launch_stage_ints(slot, c->d_actidx, n_act, nullptr, 0, c->stream));
+        HIP_TRY(c->lists.read_on(c->stream));
+        HIP_TRY(launch_assemble_wl(L, c->d_actidx, n_act, c->stream));
+    } else {
+        L.items_per_group = items_per_group_for(c, nbatch);
+        HIP_TRY(launch_assemble(L, c->stream));
+    }
+    c->acc.matrices += n_act;
+    return EMME_OK;
+}
+
 }  // namespace emme

@@ -872,6 +872,139 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
     return EMME_OK;
 }
 
+int emme_assemble_derivative_batch(emme_ctx_t* c, const double* omega, int nbatch, double* M, double* Mp,
+                                   long long* intervals) {
+    if (!c || !omega || !M || !Mp || nbatch < 1) return EMME_EINVAL;
+    HIP_TRY(hipSetDevice(c->device));
+    const bool dev_out = is_device_ptr(M);
+    if (dev_out != is_device_ptr(Mp)) {
+        set_error("M and Mp must both be host or both be device pointers");
+        return EMME_EINVAL;
+    }
+    int rc = ensure_batch(c, nbatch);
+    if (rc) return rc;
+    double *dM = M, *dMp = Mp;
+    if (!dev_out) {
+        rc = ensure_mats(c, nbatch, 1 | 4);
+        if (rc) return rc;
+        dM = c->d_M, dMp = c->d_Mp;
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * nbatch, hipMemcpyDefault, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * nbatch, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * nbatch, c->stream));
+    rc = do_assemble_deriv(c, nbatch, c->d_omega, nullptr, nullptr, dM, dMp);
+    if (rc) return rc;
+    if (!dev_out) {
+        HIP_TRY(hipMemcpyAsync(M, dM, mat_doubles(c) * sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(Mp, dMp, mat_doubles(c) * sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    }
+    std::vector<unsigned long long> iv(nbatch);
+    std::vector<int> stv(nbatch);
+    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    bool bad = false;
+    for (int b = 0; b < nbatch; ++b) {
+        c->acc.gk_intervals += (long long)iv[b];
+        if (intervals) intervals[b] = (long long)iv[b];
+        bad |= stv[b] != 0;
+    }
+    if (bad) {
+        set_error("quadrature depth cap hit or non-finite integral in at least one item");
+        return EMME_ENUMERIC;
+    }
+    return EMME_OK;
+}
+
+int emme_solve_roots_newton(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit, double* roots,
+                            int* iters, int* info, double* iterates) {
+    if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
+    const int method = c->p.iteration_method;
+    int rc = check_method(c, method);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(c->device));
+    rc = ensure_batch(c, n);
+    if (rc) return rc;
+    rc = ensure_mats(c, n, 1 | 4 | 8);
+    if (rc) return rc;
+    const int stride = step_limit + 1;
+    if (iterates) {
+        const size_t need = (size_t)n * stride * 2;
+        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
+        std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
+        HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    // omega_0 = g: one fill of M and the exact M' there, no secant bootstrap
+    std::vector<int> act(n, 1), zeros(n, 0);
+    HIP_TRY(hipMemcpyAsync(c->d_active, act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_iters, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_info, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * n, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * n, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_omega, guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    rc = do_assemble_deriv(c, n, c->d_omega, c->d_active, act.data(), c->d_M, c->d_Mp);
+    if (rc) return rc;
+    for (int j = 0; j <= step_limit; ++j) {
+        {
+            // the step of the context's iteration_method on (M, M'): trace form on a work copy of M (the LU destroys
+            // both operands; M' is filled again before it is needed), QR form on the transpose
+            ScopedSpan s(c, K_LIN);
+            const bool trace = method == EMME_METHOD_TRACE_SECANT;
+            if (trace) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
+            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                act.data(), trace));
+        }
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
+                                         iterates ? c->d_iterates.get() : nullptr, j, stride, c->stream, nullptr,
+                                         c->opt.skip_lost ? c->d_status : nullptr));
+        }
+        // the live chains (2 = converged at this step: M and M' are filled at the new omega once more)
+        HIP_TRY(hipMemcpyAsync(c->p_act, c->d_active, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool any = false;
+        for (int b = 0; b < n; ++b) {
+            act[b] = c->p_act[b];
+            any |= act[b] != 0;
+        }
+        if (!any) break;
+        rc = do_assemble_deriv(c, n, c->d_omega, c->d_active, act.data(), c->d_M, c->d_Mp);
+        if (rc) return rc;
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_retire(n, c->d_active, c->stream));
+        }
+    }
+    std::vector<unsigned long long> iv(n);
+    std::vector<int> stv(n);
+    HIP_TRY(hipMemcpyAsync(roots, c->d_omega, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iters, c->d_iters, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (iterates)
+        HIP_TRY(hipMemcpyAsync(iterates, c->d_iterates, sizeof(double) * 2 * (size_t)n * stride, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_n = n;
+    for (int b = 0; b < n; ++b) {
+        c->acc.gk_intervals += (long long)iv[b];
+        if (stv[b] != 0 && info[b] == 0) info[b] = EMME_ENUMERIC;
+        if (info[b] == 0 && !(std::isfinite(roots[2 * b]) && std::isfinite(roots[2 * b + 1]))) info[b] = EMME_ENUMERIC;
+    }
+    // (a multi-workgroup LU whose hand-over timed out: again with one workgroup per matrix, as emme_solve_roots does)
+    if (!c->lu_one_wg) {
+        bool timed_out = false;
+        for (int b = 0; b < n; ++b) timed_out |= info[b] == EMME_EDEVICE;
+        if (timed_out) {
+            c->lu_one_wg = true;
+            return emme_solve_roots_newton(c, guesses, n, tol, step_limit, roots, iters, info, iterates);
+        }
+    }
+    return EMME_OK;
+}
+
 int emme_bessel_batch(const double* z, int n, double* out) {
     if (!z || !out || n < 1) return EMME_EINVAL;
     int ndev = 0;

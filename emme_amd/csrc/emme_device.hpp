@@ -469,6 +469,82 @@ __device__ __forceinline__ cd integrand(double x, const DevParams& P, const Pair
     return inv_c2 * F;
 }
 
+// integrand() and its exact derivative d/d omega (the derivative fill k_assemble_deriv): F by the same operations,
+// and, since omega enters through exp(i t~ omega) and a0 = omega - ...,
+//     F' = i t~ F + (jacob / t~) exp(log_coef) nv^m (y0 / lambda) / (mu cos^2 x);  0 where F is clamped to 0.
+// (A copy rather than a flag on integrand(): a shared template changed the plain fill's register allocation.)
+__device__ __forceinline__ cd integrand_d(double x, const DevParams& P, const PairConst& pc,
+                                          const OmegaConst& oc, int m, cd& Fd) {
+    double sx, cx;
+    sincos(x, &sx, &cx);
+    const double rsc = frcp(sx * cx);
+    const double inv_cx = sx * rsc;
+    double t = sx * inv_cx;
+    const double inv_c2 = inv_cx * inv_cx;
+    double inv_t = cx * (cx * rsc);
+    double u = t * P.inv_arc;
+
+    // ---- stage A: exponent of the integrand and the underflow clamp -----------------
+    cd arg, w;
+    double zabs, inv_zabs;
+    bool zneg;
+    {
+        const NodeTerms n = node_terms(t, inv_t, u, pc, oc.omi);
+        const cd z = pc.s * n.rl;
+        // log_coef, src/Parameters.cpp:154-165
+        cd L = (-0.5) * n.nv2 + times_i(n.taut * oc.omega);
+        L = L + (-0.5 * pc.beta1) * times_i(n.nv);
+        L = L - (0.5 * pc.bsum) * n.rl;
+        zneg = z.x < 0.0;
+        arg = zneg ? (L - z) : (L + z);  // log_coef - (Re z<0 ? z : -z)
+        if (!(arg.x >= -40.)) {
+            // safe_exp clamp (:167-173); NaN falls through and is propagated below
+            if (arg.x < -40.) {
+                Fd = mk(0.0, 0.0);
+                return mk(0.0, 0.0);
+            }
+        }
+        w = pc.inv_s * n.lam;
+        zabs = pc.s * n.rlabs;
+        inv_zabs = pc.inv_s * (norm2(n.lam) * n.rlabs);
+    }
+
+    // ---- stage B: Miller recurrence (the long, data-dependent part) -------------------
+    cd y0, y1, mutot;
+    bessel_miller(w, zabs, inv_zabs, zneg, y0, y1, mutot);
+
+    // ---- stage C: coefficients and assembly of F ---------------------------------------
+    const NodeTerms n = node_terms(t, inv_t, u, pc, oc.omi);
+    double sa, ca;
+#if EMME_FAST_TRANSCENDENTALS
+    fsincos(arg.y, sa, ca);
+    const double ea = fexp(arg.x);
+#else
+    sincos(arg.y, &sa, &ca);
+    const double ea = exp(arg.x);
+#endif
+    const cd sexp = mk(ea * ca, ea * sa);
+
+    const cd rl3 = n.rl * n.rl * n.rl;  // lambda^-3 (reference: pow(lambda, -3.) via log/polar)
+    const double wsi_eta = P.omega_s_i * P.eta_i;
+    const cd a0 = oc.omega - P.omega_s_i * mk(fma(P.eta_i, fma(0.5, n.nv2.x, -1.5), 1.0),
+                                               P.eta_i * 0.5 * n.nv2.y);
+    const cd i0c = a0 * n.rl + (wsi_eta * mk(0.5 * pc.bsum - n.lam.x, -n.lam.y)) * rl3;
+    const cd i1c = (-wsi_eta * pc.s) * rl3;
+
+    cd F = mk(inv_t, -(n.ou * n.r2 * inv_t)) * sexp;  // (jacob / t~) * safe_exp
+    if (m == 1)
+        F = F * n.nv;
+    else if (m == 2)
+        F = F * n.nv2;
+    const cd G = F;  // (the factor of d a0 / d omega = 1)
+    F = F * (i0c * y0 + i1c * y1);
+    F = F * rcp(mutot);
+    F = inv_c2 * F;
+    Fd = inv_c2 * ((G * (n.rl * y0)) * rcp(mutot)) + times_i(n.taut) * F;
+    return F;
+}
+
 // ---- omega-independent half of the integrand ------------------------------------------
 // For fixed pair, moment and contour sense (omi) the integrand at abscissa x is
 //     F(omega) = exp(A0 + T omega) (omega Q1 + Q0)      [0 when Re(A0 + T omega) < -40]
@@ -565,6 +641,27 @@ __device__ __forceinline__ cd node_eval(const NodeData& d, cd omega, const Trans
     const cd S = mk(fma(omega.x, d.Q1.x, fma(-omega.y, d.Q1.y, d.Q0.x)),
                     fma(omega.x, d.Q1.y, fma(omega.y, d.Q1.x, d.Q0.y)));
     return mk(ea * ca, ea * sa) * S;
+}
+
+// F and F' = exp(A0 + T omega) (T (omega Q1 + Q0) + Q1) at one node (the derivative fills): F by the operations
+// of node_eval above, F' beside it; a clamped node is 0 in both
+__device__ __forceinline__ cd node_eval_d(const NodeData& d, cd omega, const TransConsts& k, cd& Fd) {
+    const double ax = fma(d.T.x, omega.x, fma(-d.T.y, omega.y, d.A0.x));
+    if (!(ax >= -40.)) {
+        if (ax < -40.) {
+            Fd = mk(0.0, 0.0);
+            return mk(0.0, 0.0);
+        }
+    }
+    const double ay = fma(d.T.x, omega.y, fma(d.T.y, omega.x, d.A0.y));
+    double sa, ca;
+    fsincos(ay, sa, ca, k);
+    const double ea = fexp(ax, k);
+    const cd S = mk(fma(omega.x, d.Q1.x, fma(-omega.y, d.Q1.y, d.Q0.x)),
+                    fma(omega.x, d.Q1.y, fma(omega.y, d.Q1.x, d.Q0.y)));
+    const cd E = mk(ea * ca, ea * sa);
+    Fd = E * (d.T * S + d.Q1);
+    return E * S;
 }
 
 // Gauss-Kronrod node tables laid out per lane of a group (centre, +x_1..+x_h, -x_1..-x_h,

@@ -41,6 +41,7 @@ struct AssembleLaunch {
     int coop_wide_min = 4096;  // deferred list: length from which the one-wave cooperative kernel takes over (-1 never)
     int defer_one_group = 0;   // deferred integrals by one lane group each
     int dense_min_cols = 3;    // dense fill: columns that must need an interval for the MFMA path
+    double* Md = nullptr;      // device or null: exact dM/domega beside M (uncached kernels only; Mold must be null)
 };
 // What the launchers that read the node cache see of it: its geometry and, per contour class (omi = +1, -1), the
 // main records, the run-time subtrees (null if absent), the T table, the moment-factor table and the tile-poison
@@ -54,10 +55,10 @@ struct NodeCacheView {
     const unsigned char* tile_poison[2];
     const double* scale;
 };
-// lanes-are-nodes kernel, without the node cache
+// lanes-are-nodes kernel, without the node cache (L.Md set: k_assemble_deriv, M and dM/domega)
 hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream);
 // omega-lane form (assemble_wl.hip): the n_act batch items listed in act_idx (device) share
-// the omega-independent node data; L.active is ignored.
+// the omega-independent node data; L.active is ignored.  L.Md set: k_assemble_wl_deriv.
 hipError_t launch_assemble_wl(const AssembleLaunch& L, const int* act_idx, int n_act,
                               hipStream_t stream);
 

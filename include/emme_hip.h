@@ -211,7 +211,25 @@ int emme_qr_secant_batch(emme_ctx_t* ctx, int n, int nbatch, const double* A, co
  * iterates (optional): n*(step_limit+1)*2 doubles, omega after every step, NaN padded. */
 int emme_solve_roots(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
                      double* roots, int* iters, int* info, double* iterates);
-/* Copy M(omega_final) of item b of the last emme_solve_roots call (dim*dim complex). */
+/* ---- exact derivative and true Newton (additions within version 4: find them by symbol lookup) ------------------
+ * M(omega) and M'(omega) = dM/domega exactly, for the intervals the adaptive rule chose for M: the
+ * derivative rides along the quadrature, the accept/split decisions and M are those of the plain fill of the same
+ * kernel bit for bit.  Pointers as emme_assemble_batch (omega host or device; M and Mp both host or both device).
+ * Batches of wl_min or more go through the omega-lane kernel, smaller ones through the lanes-are-nodes kernel, on
+ * every context: the node cache is neither read nor grown (emme_ctx_cache_state is unchanged), and
+ * emme_ctx_fill_mode keeps naming the last plain fill.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
+ * integral), and also when an entry of M' is non-finite or beyond the range M is held to: a fill whose M alone the
+ * plain fill accepts can then fail. */
+int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nbatch, double* M, double* Mp,
+                                   long long* intervals);
+/* Newton's method on det M = 0 with the exact M': arguments, outputs, info codes, NaN-padded iterates and stopping
+ * rule as emme_solve_roots, but starting at omega_0 = g (no 0.99 g / 0.01 g bootstrap), and every step fills M and M'
+ * at the current omega of the live chains.  The step is the context's iteration_method on (M, M'): trace form
+ * domega = -1/tr(M^-1 M'), QR form domega = -1/q.  emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) see the
+ * last fill's M per chain afterwards.  Derivative fills count in the emme_profile_t fill counters. */
+int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
+                            double* roots, int* iters, int* info, double* iterates);
+/* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton call (dim*dim complex). */
 int emme_ctx_get_matrix(emme_ctx_t* ctx, int b, double* M_host);
 
 /* nullSpace (reference include/solver.h:58-112): the right singular vector of the smallest
