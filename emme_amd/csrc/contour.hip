@@ -457,26 +457,23 @@ int emme_find_roots_in_contour(emme_ctx_t* c, const emme_contour_t* ct, double t
         NodeSet& set = S.sets.back();
         set.first = (int)node_m.size(), set.count = cnt;
         HIP_TRY(set.A.grow(sizeof(double) * 2 * (size_t)n * n * cnt));
-        HIP_TRY(hipMemcpyAsync(c->d_omega, om.data(), sizeof(double) * 2 * cnt, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * cnt, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * cnt, c->stream));
-        r = do_assemble(c, cnt, c->d_omega, nullptr, nullptr, set.A, nullptr, nullptr, nullptr, nullptr, om.data());
+        r = upload_omega(c, om.data(), cnt);
         if (r) return r;
-        std::vector<int> stv(cnt);
-        std::vector<unsigned long long> iv(cnt);
-        HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * cnt, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * cnt, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int k = 0; k < cnt; ++k) {
-            c->acc.gk_intervals += (long long)iv[k];
-            if (stv[k] != 0) {
-                char buf[200];
-                snprintf(buf, sizeof buf, "emme_find_roots_in_contour: the fill of the node omega = %.17g%+.17gi failed "
-                         "(quadrature depth cap or non-finite integral)", om[2 * k], om[2 * k + 1]);
-                set_error(buf);
-                return EMME_ENUMERIC;
-            }
+        r = reset_fill_counters(c, cnt);
+        if (r) return r;
+        FillRequest nodes(cnt, c->d_omega, set.A);
+        nodes.host_omega = om.data();
+        r = fill(c, nodes);
+        if (r) return r;
+        int k = 0;
+        r = collect_fill_status(c, cnt, nullptr, &k);
+        if (r == EMME_ENUMERIC) {
+            char buf[200];
+            snprintf(buf, sizeof buf, "emme_find_roots_in_contour: the fill of the node omega = %.17g%+.17gi failed "
+                     "(quadrature depth cap or non-finite integral)", om[2 * k], om[2 * k + 1]);
+            set_error(buf);
         }
+        if (r) return r;
         for (int m : ms) node_m.push_back(m);
         r = factor_set(S, set, "emme_find_roots_in_contour");
         if (r) return r;

@@ -1,6 +1,6 @@
 // ctx.hpp -- the context behind the C ABI (include/emme_hip.h) and the host-side helpers its translation
 // units share: emme_capi.hip (the ABI entry points and the Newton loop), ctx_cache.hip (buffer pool and the
-// HBM node cache's host side), ctx_fill.hip (the fill dispatcher).
+// HBM node cache's host side), ctx_fill.hip (the fill dispatcher; its host arithmetic is fill_plan.cpp).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -34,7 +34,17 @@ void set_error(const std::string& msg);
         }                                                                              \
     } while (0)
 
+// the same for the EMME_* codes of the host layer's own functions
+#define EMME_TRY(expr)             \
+    do {                           \
+        const int rc_ = (expr);    \
+        if (rc_) return rc_;       \
+    } while (0)
+
 enum Kind { K_ASM = 0, K_LIN = 1, K_OTHER = 2, K_DEFER = 3, K_CACHE = 4, K_NULL = 5 };
+
+// kernel family of a plain fill, as emme_ctx_fill_mode reports it (include/emme_hip.h)
+enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4 };
 
 // HBM node cache of one contour class (omi = +1, -1)
 struct NodeCacheClass {
@@ -72,7 +82,7 @@ struct emme_ctx {
     DeviceBuffer<int> d_chunks;   // (first, size) of every omega chunk of the cached kernel
     std::vector<int> h_chunks;
     std::vector<int> h_actidx; // its host image
-    int last_fill_mode = -1;   // kernel family of the last fill: 0 nodes, 1 omega-lane, 2 cached
+    int last_fill_mode = -1;   // FillMode of the last plain fill (-1: none yet)
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
     // HBM cache of omega-independent node records, per contour class (omi = +1, -1)
     int cache_depth = -1;      // -1: not decided yet, -2: disabled / does not fit, else dfull
@@ -150,17 +160,34 @@ bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls);
 void add_cache_subtree(emme_ctx* c, const AssembleLaunch& L, int depth, unsigned long long path, int cls);
 
 // ---- ctx_fill.hip: the fill dispatcher ------------------------------------------------------------------
-int do_assemble(emme_ctx* c, int nbatch, const double* d_omega, const int* d_active,
-                const int* host_active, double* d_M, const double* d_Mold, double* d_Mp,
-                const double* d_domega, const unsigned long long* cost = nullptr,
-                const double* host_omega = nullptr, bool newton_loop = false, bool force_uncached = false);
-// M and the exact dM/domega through the uncached derivative kernels (ctx_fill.hip; the node cache is not touched)
-int do_assemble_deriv(emme_ctx* c, int nbatch, const double* d_omega, const int* d_active, const int* host_active,
-                      double* d_M, double* d_Md);
+// One fill of M(omega) for a batch.  Pointers starting with d_ are device memory, host_ their host images.
+struct FillRequest {
+    int nbatch;
+    const double* d_omega;
+    const double* host_omega = nullptr;  // the omegas' host values: without them the node cache is not used
+    const int* d_active = nullptr;       // which items to assemble (null = all), and its host image
+    const int* host_active = nullptr;
+    double* d_M;
+    double* d_Md = nullptr;              // set: the exact dM/domega beside M, uncached kernels only
+    const double* d_Mold = nullptr;      // fused secant: Mp = (M - Mold) / domega
+    double* d_Mp = nullptr;
+    const double* d_domega = nullptr;
+    const unsigned long long* cost = nullptr;  // per item (interval count of its previous fill): orders the omegas
+    bool newton_loop = false;            // a fill of a root search (skip_lost, wide items, deferred count published)
+    bool force_uncached = false;         // omega-lane kernel whatever the batch size and the cache
+    FillRequest(int n, const double* omega, double* M) : nbatch(n), d_omega(omega), d_M(M) {}
+};
+int fill(emme_ctx* c, const FillRequest& r);
 
 // ---- emme_capi.hip ----------------------------------------------------------------------------------------
 hipEvent_t get_event(emme_ctx* c);
 int ctx_ensure_batch(emme_ctx* c, int nb);  // batch scratch for nb items
+// around a fill: the batch's omegas into d_omega; interval counts and status flags zeroed; afterwards the counts
+// read back (into `intervals` if given, and the profile) -- synchronises; EMME_ENUMERIC if an item's flag is set
+// (*bad_item, if given: the first such item)
+int upload_omega(emme_ctx* c, const double* omega, int n, hipMemcpyKind kind = hipMemcpyHostToDevice);
+int reset_fill_counters(emme_ctx* c, int n);
+int collect_fill_status(emme_ctx* c, int n, long long* intervals, int* bad_item = nullptr);
 bool ptr_on_device(const void* p);
 // scratch of lu_factor_batch that the caller keeps until what it queued behind the factorisation has run
 struct LuScratch {

@@ -40,6 +40,35 @@ hipEvent_t get_event(emme_ctx* c) {
     if (hipEventCreate(&e) != hipSuccess) return nullptr;
     return e;
 }
+
+int upload_omega(emme_ctx* c, const double* omega, int n, hipMemcpyKind kind) {
+    HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * n, kind, c->stream));
+    return EMME_OK;
+}
+
+int reset_fill_counters(emme_ctx* c, int n) {
+    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * n, c->stream));
+    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * n, c->stream));
+    return EMME_OK;
+}
+
+int collect_fill_status(emme_ctx* c, int n, long long* intervals, int* bad_item) {
+    std::vector<unsigned long long> iv(n);
+    std::vector<int> stv(n);
+    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    int bad = -1;
+    for (int b = 0; b < n; ++b) {
+        c->acc.gk_intervals += (long long)iv[b];
+        if (intervals) intervals[b] = (long long)iv[b];
+        if (stv[b] != 0 && bad < 0) bad = b;
+    }
+    if (bad < 0) return EMME_OK;
+    if (bad_item) *bad_item = bad;
+    set_error("quadrature depth cap hit or non-finite integral in at least one item");
+    return EMME_ENUMERIC;
+}
 }  // namespace emme
 
 namespace {
@@ -264,6 +293,40 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
     return trace_solve(c, n, nbatch, work, Mp, active, tr, info, h_active);
 }
 
+// one fill of a plain assembly call: the omegas into d_omega, counters zeroed, M (and, dMd given, the exact
+// derivative) queued.  The node cache needs the omegas' host values, so the derivative entry point, which also takes
+// device omegas, goes without.
+int fill_at(emme_ctx* c, const double* omega, int nbatch, double* dM, double* dMd, hipMemcpyKind kind) {
+    EMME_TRY(upload_omega(c, omega, nbatch, kind));
+    EMME_TRY(reset_fill_counters(c, nbatch));
+    FillRequest r(nbatch, c->d_omega, dM);
+    r.d_Md = dMd;
+    if (!dMd) r.host_omega = omega;
+    return fill(c, r);
+}
+
+// The two operands of a linear step where the kernels can read them: A and B themselves if they are device
+// pointers, else copies that live as long as this object.  EMME_EINVAL if one is on the host and one on the device;
+// otherwise *e is the status of the allocations and copies, which each caller reports in its own words.
+struct DeviceOperands {
+    double *A = nullptr, *B = nullptr;  // (written only by a caller whose own operands are not const)
+    DeviceBuffer<double> st_a, st_b;
+    int stage(emme_ctx* c, const double* hA, const double* hB, size_t bytes, hipError_t* e) {
+        const bool dev = is_device_ptr(hA);
+        if (dev != is_device_ptr(hB)) {
+            set_error("A and B must both be host or both be device pointers");
+            return EMME_EINVAL;
+        }
+        A = const_cast<double*>(hA), B = const_cast<double*>(hB), *e = hipSuccess;
+        if (dev) return EMME_OK;
+        if ((*e = st_a.grow(bytes)) == hipSuccess) *e = st_b.grow(bytes);
+        if (*e == hipSuccess) *e = hipMemcpyAsync(st_a, hA, bytes, hipMemcpyHostToDevice, c->stream);
+        if (*e == hipSuccess) *e = hipMemcpyAsync(st_b, hB, bytes, hipMemcpyHostToDevice, c->stream);
+        A = st_a, B = st_b;
+        return EMME_OK;
+    }
+};
+
 int check_method(const emme_ctx* c, int method) {
     if (method != EMME_METHOD_TRACE_SECANT && method != EMME_METHOD_QR_SECANT) {
         set_error("unknown iteration method");
@@ -274,6 +337,257 @@ int check_method(const emme_ctx* c, int method) {
         return EMME_ECONFIG;
     }
     return EMME_OK;
+}
+
+
+// ---- the two root searches: what they share --------------------------------------------------------------------
+// One call's arguments and the host images its loop keeps.
+struct RootSearch {
+    const double* guesses;
+    int n;
+    double tol;
+    int step_limit;
+    bool want_iterates;
+    int method = 0;
+    std::vector<int> act, zeros;  // host image of d_active (every chain live at the start); n zeros
+    int stride() const { return step_limit + 1; }
+    // (d_iterates is sized by the last call that asked for iterates: a call that does not ask must not write it)
+    double* d_iterates(const emme_ctx* c) const { return want_iterates ? c->d_iterates.get() : nullptr; }
+};
+
+// buffers for n chains and the matrix sets of `mat_sets` (ensure_mats); the iterate record, if asked for, all NaN;
+// every chain live, no step taken, counters and flags clean
+int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
+    const int n = s.n;
+    EMME_TRY(ensure_batch(c, n));
+    EMME_TRY(ensure_mats(c, n, mat_sets));
+    if (s.want_iterates) {
+        const size_t need = (size_t)n * s.stride() * 2;
+        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
+        std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
+        HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    s.act.assign(n, 1), s.zeros.assign(n, 0);
+    HIP_TRY(hipMemcpyAsync(c->d_active, s.act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_iters, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_info, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    return reset_fill_counters(c, n);
+}
+
+// the results to the caller, per-chain failures marked.  *repeat: the search has to be run again (below).
+int search_end(emme_ctx* c, const RootSearch& s, double* roots, int* iters, int* info, double* iterates, bool* repeat) {
+    const int n = s.n;
+    std::vector<unsigned long long> iv(n);
+    std::vector<int> stv(n);
+    HIP_TRY(hipMemcpyAsync(roots, c->d_omega, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iters, c->d_iters, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    if (iterates)
+        HIP_TRY(hipMemcpyAsync(iterates, c->d_iterates, sizeof(double) * 2 * (size_t)n * s.stride(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_n = n;
+    bool timed_out = false;
+    for (int b = 0; b < n; ++b) {
+        c->acc.gk_intervals += (long long)iv[b];
+        // a chain that met a non-finite integral or the quadrature depth cap is reported
+        // per item (the reference would carry the NaN to its "eigenvalue": "NaN" record,
+        // src/main.cpp:311-316); the other chains of the batch are unaffected
+        if (stv[b] != 0 && info[b] == 0) info[b] = EMME_ENUMERIC;
+        // whatever the cause, a non-finite omega is never handed back as a root
+        if (info[b] == 0 && !(std::isfinite(roots[2 * b]) && std::isfinite(roots[2 * b + 1]))) info[b] = EMME_ENUMERIC;
+        timed_out |= info[b] == EMME_EDEVICE;
+    }
+    // The multi-workgroup LU needs its workgroups resident together; if something else held
+    // compute units for seconds (a foreign kernel on a shared device) a hand-over wait timed out
+    // and retired those chains with EMME_EDEVICE.  Do the search again with one workgroup per
+    // matrix, and keep it that way for this context.
+    *repeat = timed_out && !c->lu_one_wg;
+    if (*repeat) {
+        c->lu_one_wg = true;
+        if (std::getenv("EMME_DEBUG")) fprintf(stderr, "[emme] LU hand-over timed out: repeating the search with one workgroup per matrix\n");
+    }
+    return EMME_OK;
+}
+
+// The secant search of emme_solve_roots (EigenSolver's constructor and newtonTraceSecantIteration, include/solver.h:
+// 396-415 and 113-160, under the loop of src/main.cpp:19-80), between search_begin and search_end.
+int secant_loop(emme_ctx* c, RootSearch& search) {
+    const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
+    const double* guesses = search.guesses;
+    const double tol = search.tol;
+    double* const d_iterates = search.d_iterates(c);
+    std::vector<int>& act = search.act;
+    // EigenSolver ctor (include/solver.h:396-415): eigen_value = 0.99 g, d = 0.01 g;
+    // M_old = M(eigen_value); eigen_value += d; M = M(eigen_value); M' = (M - M_old)/d
+    std::vector<double> w0(2 * (size_t)n), dw(2 * (size_t)n), w1(2 * (size_t)n);
+    for (int b = 0; b < 2 * n; ++b) {
+        w0[b] = 0.99 * guesses[b];
+        dw[b] = 0.01 * guesses[b];
+        w1[b] = w0[b] + dw[b];
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_omega, w0.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_domega, dw.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    c->h_wide.assign(n, 0);
+    HIP_TRY(hipMemsetAsync(c->d_overflow, 0, sizeof(unsigned int) * n, c->stream));
+    std::vector<double> h_w(2 * (size_t)n);
+    std::vector<unsigned long long> iv_prev(n, 0), iv_now(n, 0), cost(n, 0), iv_prev_dbg(n, 0);
+    auto refresh_cost = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(iv_now.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        for (int b = 0; b < n; ++b) {
+            if (iv_now[b] != iv_prev[b]) cost[b] = iv_now[b] - iv_prev[b];
+            iv_prev[b] = iv_now[b];
+        }
+        return EMME_OK;
+    };
+    FillRequest first(n, c->d_omega, c->d_Mold);
+    first.host_omega = w0.data(), first.newton_loop = true;
+    EMME_TRY(fill(c, first));
+    EMME_TRY(refresh_cost());  // synchronises; the first fill's interval counts order the second
+    HIP_TRY(hipMemcpyAsync(c->d_omega, w1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    // (the fills of a root search write M only: the secant M' = (M - M_old) / d, include/solver.h:157 and :412, is
+    // taken by k_secant_copy at the top of the step that uses it, in one coalesced pass)
+    FillRequest next(n, c->d_omega, c->d_M);
+    next.host_omega = w1.data(), next.cost = cost.data(), next.newton_loop = true;
+    EMME_TRY(fill(c, next));
+    next.host_omega = h_w.data(), next.d_active = c->d_active, next.host_active = act.data();  // (the steps' fills)
+
+    EMME_TRY(refresh_cost());
+    // One stream synchronisation per Newton step: the host needs the new omegas (contour
+    // classes, cache growth) before it can launch the fill.  The active flags and interval
+    // counts a fill leaves behind travel to pinned memory asynchronously and are read after the
+    // NEXT step's synchronisation, so the LU and the update of that step are queued behind the
+    // fill without a bubble (their list of live matrices is one step old: a superset).
+    bool pending = false;
+    int j_pending = 0;
+    auto take_pending = [&]() {  // results of the previous step's fill + retire
+        for (int b = 0; b < n; ++b) {
+            act[b] = c->p_act[b];
+            iv_now[b] = c->p_iv[b];
+            // (an eighth of its integrals did not fit the 64-entry level lists: 128 entries from now on)
+            if (c->p_overflow[b] * 8u >= (unsigned)c->npairs) c->h_wide[b] = 1;
+            c->last_deferred = *c->p_deferred, c->pub_valid = true;
+            if (iv_now[b] != iv_prev[b]) cost[b] = iv_now[b] - iv_prev[b];
+            iv_prev[b] = iv_now[b];
+        }
+        pending = false;
+        if (std::getenv("EMME_DEBUG")) {
+            unsigned long long tot = 0, mx = 0;
+            int na = 0, nprev = 0;
+            for (int b = 0; b < n; ++b) {
+                if (iv_now[b] != iv_prev_dbg[b]) {
+                    const unsigned long long d = iv_now[b] - iv_prev_dbg[b];
+                    tot += d, mx = d > mx ? d : mx, ++nprev;
+                }
+                iv_prev_dbg[b] = iv_now[b];
+                na += act[b] != 0;
+            }
+            fprintf(stderr, "[emme] LU workgroups per matrix %d\n", c->last_lu_nwg);
+            fprintf(stderr, "[emme] iter %2d: assembled %3d, lane-intervals %10llu (max/item %9llu), still active %d\n",
+                    j_pending, nprev, tot, mx, na);
+        }
+    };
+    for (int j = 0; j <= step_limit; ++j) {  // src/main.cpp:43
+        const bool fused_copy = method == EMME_METHOD_TRACE_SECANT;
+        {
+            // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
+            // LU's work copy): one pass, for the chains still iterating only
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_secant_copy_sym(c->dim, n, c->d_M, c->d_Mold, fused_copy ? c->d_work : nullptr, c->d_Mp,
+                                           c->d_domega, c->d_active, c->stream));
+        }
+        {
+            ScopedSpan s(c, K_LIN);
+            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                act.data(), fused_copy));
+        }
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters,
+                                         c->d_info, tol, d_iterates, j, stride, c->stream, c->p_w,
+                                         c->opt.skip_lost ? c->d_status : nullptr));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
+        if (pending) {
+            take_pending();
+            bool any = false;
+            for (int b = 0; b < n; ++b) any |= act[b] != 0;
+            if (!any) break;  // (this step's LU and update found nothing active: no-ops)
+        }
+        EMME_TRY(fill(c, next));
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_retire(n, c->d_active, c->stream, c->p_act, c->d_intervals, c->p_iv,
+                                  c->d_worklist_count, c->p_deferred, c->d_overflow, c->p_overflow));
+        }
+        pending = true, j_pending = j;
+    }
+    return EMME_OK;
+}
+
+// The Newton search of emme_solve_roots_newton, between search_begin and search_end.
+int newton_loop(emme_ctx* c, RootSearch& search) {
+    const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
+    const double tol = search.tol;
+    double* const d_iterates = search.d_iterates(c);
+    std::vector<int>& act = search.act;
+    // omega_0 = g: one fill of M and the exact M' there, no secant bootstrap
+    HIP_TRY(hipMemcpyAsync(c->d_omega, search.guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    FillRequest both(n, c->d_omega, c->d_M);
+    both.d_Md = c->d_Mp, both.d_active = c->d_active, both.host_active = act.data();
+    EMME_TRY(fill(c, both));
+    for (int j = 0; j <= step_limit; ++j) {
+        {
+            // the step of the context's iteration_method on (M, M'): trace form on a work copy of M (the LU destroys
+            // both operands; M' is filled again before it is needed), QR form on the transpose
+            ScopedSpan s(c, K_LIN);
+            const bool trace = method == EMME_METHOD_TRACE_SECANT;
+            if (trace) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
+            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                act.data(), trace));
+        }
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
+                                         d_iterates, j, stride, c->stream, nullptr,
+                                         c->opt.skip_lost ? c->d_status : nullptr));
+        }
+        // the live chains (2 = converged at this step: M and M' are filled at the new omega once more)
+        HIP_TRY(hipMemcpyAsync(c->p_act, c->d_active, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool any = false;
+        for (int b = 0; b < n; ++b) {
+            act[b] = c->p_act[b];
+            any |= act[b] != 0;
+        }
+        if (!any) break;
+        EMME_TRY(fill(c, both));
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_retire(n, c->d_active, c->stream));
+        }
+    }
+    return EMME_OK;
+}
+
+int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_limit, double* roots, int* iters, int* info,
+               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&)) {
+    if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
+    RootSearch s{guesses, n, tol, step_limit, iterates != nullptr};
+    s.method = c->p.iteration_method;  // src/main.cpp:45-49
+    EMME_TRY(check_method(c, s.method));
+    HIP_TRY(hipSetDevice(c->device));
+    for (;;) {
+        bool repeat = false;
+        EMME_TRY(search_begin(c, s, mat_sets));
+        EMME_TRY(loop(c, s));
+        EMME_TRY(search_end(c, s, roots, iters, info, iterates, &repeat));
+        if (!repeat) return EMME_OK;
+    }
 }
 
 }  // namespace
@@ -298,14 +612,12 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     emme_options_t o;
     options_default(o);
     if (opt) {
-        const int rc = options_check(opt);
-        if (rc) return rc;
+        EMME_TRY(options_check(opt));
         o = *opt;
     }
     options_env_overrides(o);
     {
-        const int rc = options_check(&o);
-        if (rc) return rc;
+        EMME_TRY(options_check(&o));
     }
     if (p->integration_start_points != 15 && p->integration_start_points != 31) {
         // include/functions.h:329
@@ -408,8 +720,7 @@ void emme_release_pooled_memory(void) { pool_release_all(); }
 
 int emme_ctx_set_options(emme_ctx_t* c, const emme_options_t* opt) {
     if (!c || !opt) return EMME_EINVAL;
-    const int rc = options_check(opt);
-    if (rc) return rc;
+    EMME_TRY(options_check(opt));
     const bool layout_differs = opt->fill != c->opt.fill || (opt->phase_table != 0) != (c->opt.phase_table != 0) ||
                                 (opt->em_shared != 0) != (c->opt.em_shared != 0);
     if (layout_differs) {
@@ -458,8 +769,7 @@ int emme_ctx_profile_enable(emme_ctx_t* c, int on) {
 int emme_ctx_profile_read(emme_ctx_t* c, emme_profile_t* out, int reset) {
     if (!c || !out) return EMME_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = drain_spans(c);
-    if (rc) return rc;
+    EMME_TRY(drain_spans(c));
     c->acc.integrand_evals = c->acc.gk_intervals * c->p.integration_start_points;
     if (c->d_rounds) {
         unsigned long long r[16] = {};
@@ -490,58 +800,31 @@ int emme_assemble_batch(emme_ctx_t* c, const double* omega, int nbatch, double* 
                         long long* intervals) {
     if (!c || !omega || !M || nbatch < 1) return EMME_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
+    EMME_TRY(ensure_batch(c, nbatch));
     const bool dev_out = is_device_ptr(M);
     double* dM = M;
     if (!dev_out) {
-        rc = ensure_mats(c, nbatch, 1);
-        if (rc) return rc;
+        EMME_TRY(ensure_mats(c, nbatch, 1));
         dM = c->d_M;
     }
-    HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * nbatch, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * nbatch, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * nbatch, c->stream));
-    rc = do_assemble(c, nbatch, c->d_omega, nullptr, nullptr, dM, nullptr, nullptr, nullptr, nullptr, omega);
-    if (rc) return rc;
+    EMME_TRY(fill_at(c, omega, nbatch, dM, nullptr, hipMemcpyHostToDevice));
     if (!dev_out)
         HIP_TRY(hipMemcpyAsync(M, dM, mat_doubles(c) * sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    std::vector<unsigned long long> iv(nbatch);
-    std::vector<int> stv(nbatch);
-    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    bool bad = false;
-    for (int b = 0; b < nbatch; ++b) {
-        c->acc.gk_intervals += (long long)iv[b];
-        if (intervals) intervals[b] = (long long)iv[b];
-        bad |= stv[b] != 0;
-    }
-    if (bad) {
-        set_error("quadrature depth cap hit or non-finite integral in at least one item");
-        return EMME_ENUMERIC;
-    }
-    return EMME_OK;
+    return collect_fill_status(c, nbatch, intervals);
 }
 
 int emme_ctx_cache_settle(emme_ctx_t* c, const double* omega, int nbatch, int* fills_done) {
     if (!c || !omega || nbatch < 1) return EMME_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
-    rc = ensure_mats(c, nbatch, 1);
-    if (rc) return rc;
+    EMME_TRY(ensure_batch(c, nbatch));
+    EMME_TRY(ensure_mats(c, nbatch, 1));
     int fills = 0;
     // a fill that deferred integrals makes the NEXT one cache a subtree around the interval most of
     // them were missing; at most NODE_CACHE_MAX_SUB - 1 run-time subtrees per contour class exist, so
     // the shape is final after at most that many growing fills plus one that finds nothing to add
     for (int round = 0; round < 2 * NODE_CACHE_MAX_SUB + 2; ++round) {
         const double before = c->cache_bytes_used;
-        HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * nbatch, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * nbatch, c->stream));
-        HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * nbatch, c->stream));
-        rc = do_assemble(c, nbatch, c->d_omega, nullptr, nullptr, c->d_M, nullptr, nullptr, nullptr, nullptr, omega);
-        if (rc) return rc;
+        EMME_TRY(fill_at(c, omega, nbatch, c->d_M, nullptr, hipMemcpyHostToDevice));
         HIP_TRY(hipStreamSynchronize(c->stream));
         ++fills;
         if (round > 0 && c->cache_bytes_used == before) break;  // this fill found the shape it started with
@@ -566,23 +849,13 @@ int emme_trace_solve_batch(emme_ctx_t* c, int n, int nbatch, double* A, double* 
         return EMME_EINVAL;
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
-    const bool devA = is_device_ptr(A), devB = is_device_ptr(B);
-    if (devA != devB) {
-        set_error("A and B must both be host or both be device pointers");
-        return EMME_EINVAL;
-    }
+    EMME_TRY(ensure_batch(c, nbatch));
     const size_t bytes = (size_t)n * n * 2 * sizeof(double) * nbatch;
-    double *dA = A, *dB = B;
-    DeviceBuffer<double> st_a, st_b;  // device copies of host operands
-    if (!devA) {
-        HIP_TRY(st_a.grow(bytes));
-        HIP_TRY(st_b.grow(bytes));
-        dA = st_a, dB = st_b;
-        HIP_TRY(hipMemcpyAsync(dA, A, bytes, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipMemcpyAsync(dB, B, bytes, hipMemcpyHostToDevice, c->stream));
-    }
+    DeviceOperands ops;
+    hipError_t staged = hipSuccess;
+    EMME_TRY(ops.stage(c, A, B, bytes, &staged));
+    HIP_TRY(staged);
+    double *dA = ops.A, *dB = ops.B;
     {
         ScopedSpan s(c, K_LIN);
         HIP_TRY(trace_solve(c, n, nbatch, dA, dB, nullptr, c->d_tr, c->d_info, nullptr));
@@ -601,29 +874,20 @@ int emme_qr_secant_batch(emme_ctx_t* c, int n, int nbatch, const double* A, cons
         return EMME_ECONFIG;
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
-    const bool devA = is_device_ptr(A), devB = is_device_ptr(B);
-    if (devA != devB) {
-        set_error("A and B must both be host or both be device pointers");
-        return EMME_EINVAL;
-    }
+    EMME_TRY(ensure_batch(c, nbatch));
     const size_t bytes = (size_t)n * n * 2 * sizeof(double) * nbatch;
-    const double *dA = A, *dB = B;
-    DeviceBuffer<double> dW, st_a, st_b;  // transposed work copy; device copies of host operands
-    if (dW.grow(bytes) != hipSuccess || (!devA && (st_a.grow(bytes) != hipSuccess || st_b.grow(bytes) != hipSuccess))) {
+    DeviceOperands ops;
+    DeviceBuffer<double> dW;  // transposed work copy
+    hipError_t e = hipSuccess;
+    EMME_TRY(ops.stage(c, A, B, bytes, &e));
+    if (e == hipErrorOutOfMemory || dW.grow(bytes) != hipSuccess) {
         set_error("hipMalloc failed");
         return EMME_ENOMEM;
     }
-    if (!devA) {
-        dA = st_a, dB = st_b;
-        (void)hipMemcpyAsync(st_a, A, bytes, hipMemcpyHostToDevice, c->stream);
-        (void)hipMemcpyAsync(st_b, B, bytes, hipMemcpyHostToDevice, c->stream);
-    }
-    hipError_t e;
+    const double *dA = ops.A, *dB = ops.B;
     {
         ScopedSpan s(c, K_LIN);
-        e = launch_transpose(n, nbatch, dA, dW, nullptr, c->stream);
+        if (e == hipSuccess) e = launch_transpose(n, nbatch, dA, dW, nullptr, c->stream);
         if (e == hipSuccess) e = launch_qr_secant(n, nbatch, dW, dB, nullptr, c->d_tr, c->d_info, c->stream);
     }
     if (e == hipSuccess) e = hipMemcpyAsync(q, c->d_tr, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream);
@@ -639,19 +903,16 @@ int emme_qr_secant_batch(emme_ctx_t* c, int n, int nbatch, const double* A, cons
 int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nbatch, double* M,
                            double* Mp, int method, int* info) {
     if (!c || !omega || !domega || !M || !Mp || !info || nbatch < 1) return EMME_EINVAL;
-    int rc = check_method(c, method);
-    if (rc) return rc;
+    EMME_TRY(check_method(c, method));
     HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
+    EMME_TRY(ensure_batch(c, nbatch));
     const bool dev = is_device_ptr(M);
     if (dev != is_device_ptr(Mp)) {
         set_error("M and Mp must both be host or both be device pointers");
         return EMME_EINVAL;
     }
     const size_t mbytes = mat_doubles(c) * sizeof(double) * nbatch;
-    rc = ensure_mats(c, nbatch, dev ? (2 | 8) : (1 | 2 | 4 | 8));
-    if (rc) return rc;
+    EMME_TRY(ensure_mats(c, nbatch, dev ? (2 | 8) : (1 | 2 | 4 | 8)));
     double *dM = M, *dMp = Mp;
     if (!dev) {
         dM = c->d_M, dMp = c->d_Mp;
@@ -660,9 +921,8 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
     }
     const hipMemcpyKind in_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     const hipMemcpyKind out_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
-    HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * nbatch, in_kind, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * nbatch, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * nbatch, c->stream));
+    EMME_TRY(upload_omega(c, omega, nbatch, in_kind));
+    EMME_TRY(reset_fill_counters(c, nbatch));
     {
         // eigen_matrix_old = eigen_matrix (include/solver.h:114); the factorisation then
         // consumes a scratch copy so M_old survives for the secant update
@@ -681,8 +941,10 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
     std::vector<double> h_w(2 * (size_t)nbatch);
     HIP_TRY(hipMemcpyAsync(h_w.data(), c->d_omega, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    rc = do_assemble(c, nbatch, c->d_omega, nullptr, nullptr, dM, c->d_Mold, dMp, c->d_domega, nullptr, h_w.data());
-    if (rc) return rc;
+    FillRequest secant_fill(nbatch, c->d_omega, dM);
+    secant_fill.host_omega = h_w.data();
+    secant_fill.d_Mold = c->d_Mold, secant_fill.d_Mp = dMp, secant_fill.d_domega = c->d_domega;
+    EMME_TRY(fill(c, secant_fill));
     if (!dev) {
         HIP_TRY(hipMemcpyAsync(M, dM, mbytes, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(Mp, dMp, mbytes, hipMemcpyDeviceToHost, c->stream));
@@ -702,174 +964,7 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
 
 int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit,
                      double* roots, int* iters, int* info, double* iterates) {
-    if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
-    const int method = c->p.iteration_method;  // src/main.cpp:45-49
-    int rc = check_method(c, method);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_batch(c, n);
-    if (rc) return rc;
-    rc = ensure_mats(c, n, 1 | 2 | 4 | 8);
-    if (rc) return rc;
-    const int stride = step_limit + 1;
-    // (d_iterates is sized by the last call that asked for iterates: a call that does not ask must not write it)
-    if (iterates) {
-        const size_t need = (size_t)n * stride * 2;
-        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
-        std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
-        HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-
-    // EigenSolver ctor (include/solver.h:396-415): eigen_value = 0.99 g, d = 0.01 g;
-    // M_old = M(eigen_value); eigen_value += d; M = M(eigen_value); M' = (M - M_old)/d
-    std::vector<double> w0(2 * (size_t)n), dw(2 * (size_t)n), w1(2 * (size_t)n);
-    for (int b = 0; b < 2 * n; ++b) {
-        w0[b] = 0.99 * guesses[b];
-        dw[b] = 0.01 * guesses[b];
-        w1[b] = w0[b] + dw[b];
-    }
-    std::vector<int> ones(n, 1), zeros(n, 0);
-    HIP_TRY(hipMemcpyAsync(c->d_active, ones.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_iters, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_info, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * n, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * n, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_omega, w0.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_domega, dw.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    c->h_wide.assign(n, 0);
-    HIP_TRY(hipMemsetAsync(c->d_overflow, 0, sizeof(unsigned int) * n, c->stream));
-    std::vector<int> act(n, 1);
-    std::vector<double> h_w(2 * (size_t)n);
-    std::vector<unsigned long long> iv_prev(n, 0), iv_now(n, 0), cost(n, 0), iv_prev_dbg(n, 0);
-    auto refresh_cost = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(iv_now.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        for (int b = 0; b < n; ++b) {
-            if (iv_now[b] != iv_prev[b]) cost[b] = iv_now[b] - iv_prev[b];
-            iv_prev[b] = iv_now[b];
-        }
-        return EMME_OK;
-    };
-    rc = do_assemble(c, n, c->d_omega, nullptr, nullptr, c->d_Mold, nullptr, nullptr, nullptr, nullptr, w0.data(), true);
-    if (rc) return rc;
-    rc = refresh_cost();  // synchronises; the first fill's interval counts order the second
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(c->d_omega, w1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    // (the fills of a root search write M only: the secant M' = (M - M_old) / d, include/solver.h:157 and :412, is
-    // taken by k_secant_copy at the top of the step that uses it, in one coalesced pass)
-    rc = do_assemble(c, n, c->d_omega, nullptr, nullptr, c->d_M, nullptr, nullptr, nullptr,
-                     cost.data(), w1.data(), true);
-    if (rc) return rc;
-
-    rc = refresh_cost();
-    if (rc) return rc;
-    // One stream synchronisation per Newton step: the host needs the new omegas (contour
-    // classes, cache growth) before it can launch the fill.  The active flags and interval
-    // counts a fill leaves behind travel to pinned memory asynchronously and are read after the
-    // NEXT step's synchronisation, so the LU and the update of that step are queued behind the
-    // fill without a bubble (their list of live matrices is one step old: a superset).
-    bool pending = false;
-    int j_pending = 0;
-    auto take_pending = [&]() {  // results of the previous step's fill + retire
-        for (int b = 0; b < n; ++b) {
-            act[b] = c->p_act[b];
-            iv_now[b] = c->p_iv[b];
-            // (an eighth of its integrals did not fit the 64-entry level lists: 128 entries from now on)
-            if (c->p_overflow[b] * 8u >= (unsigned)c->npairs) c->h_wide[b] = 1;
-            c->last_deferred = *c->p_deferred, c->pub_valid = true;
-            if (iv_now[b] != iv_prev[b]) cost[b] = iv_now[b] - iv_prev[b];
-            iv_prev[b] = iv_now[b];
-        }
-        pending = false;
-        if (std::getenv("EMME_DEBUG")) {
-            unsigned long long tot = 0, mx = 0;
-            int na = 0, nprev = 0;
-            for (int b = 0; b < n; ++b) {
-                if (iv_now[b] != iv_prev_dbg[b]) {
-                    const unsigned long long d = iv_now[b] - iv_prev_dbg[b];
-                    tot += d, mx = d > mx ? d : mx, ++nprev;
-                }
-                iv_prev_dbg[b] = iv_now[b];
-                na += act[b] != 0;
-            }
-            fprintf(stderr, "[emme] LU workgroups per matrix %d\n", c->last_lu_nwg);
-            fprintf(stderr, "[emme] iter %2d: assembled %3d, lane-intervals %10llu (max/item %9llu), still active %d\n",
-                    j_pending, nprev, tot, mx, na);
-        }
-    };
-    for (int j = 0; j <= step_limit; ++j) {  // src/main.cpp:43
-        const bool fused_copy = method == EMME_METHOD_TRACE_SECANT;
-        {
-            // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
-            // LU's work copy): one pass, for the chains still iterating only
-            ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_secant_copy_sym(c->dim, n, c->d_M, c->d_Mold, fused_copy ? c->d_work : nullptr, c->d_Mp,
-                                           c->d_domega, c->d_active, c->stream));
-        }
-        {
-            ScopedSpan s(c, K_LIN);
-            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
-                                act.data(), fused_copy));
-        }
-        {
-            ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters,
-                                         c->d_info, tol, iterates ? c->d_iterates.get() : nullptr, j, stride, c->stream, c->p_w,
-                                         c->opt.skip_lost ? c->d_status : nullptr));
-        }
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
-        if (pending) {
-            take_pending();
-            bool any = false;
-            for (int b = 0; b < n; ++b) any |= act[b] != 0;
-            if (!any) break;  // (this step's LU and update found nothing active: no-ops)
-        }
-        rc = do_assemble(c, n, c->d_omega, c->d_active, act.data(), c->d_M, nullptr, nullptr, nullptr,
-                         cost.data(), h_w.data(), true);
-        if (rc) return rc;
-        {
-            ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_retire(n, c->d_active, c->stream, c->p_act, c->d_intervals, c->p_iv,
-                                  c->d_worklist_count, c->p_deferred, c->d_overflow, c->p_overflow));
-        }
-        pending = true, j_pending = j;
-    }
-    std::vector<unsigned long long> iv(n);
-    std::vector<int> stv(n);
-    HIP_TRY(hipMemcpyAsync(roots, c->d_omega, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(iters, c->d_iters, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (iterates)
-        HIP_TRY(hipMemcpyAsync(iterates, c->d_iterates, sizeof(double) * 2 * (size_t)n * stride, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last_n = n;
-    for (int b = 0; b < n; ++b) {
-        c->acc.gk_intervals += (long long)iv[b];
-        // a chain that met a non-finite integral or the quadrature depth cap is reported
-        // per item (the reference would carry the NaN to its "eigenvalue": "NaN" record,
-        // src/main.cpp:311-316); the other chains of the batch are unaffected
-        if (stv[b] != 0 && info[b] == 0) info[b] = EMME_ENUMERIC;
-        // whatever the cause, a non-finite omega is never handed back as a root
-        if (info[b] == 0 && !(std::isfinite(roots[2 * b]) && std::isfinite(roots[2 * b + 1]))) info[b] = EMME_ENUMERIC;
-    }
-    // The multi-workgroup LU needs its workgroups resident together; if something else held
-    // compute units for seconds (a foreign kernel on a shared device) a hand-over wait timed out
-    // and retired those chains with EMME_EDEVICE.  Do the search again with one workgroup per
-    // matrix, and keep it that way for this context.
-    if (!c->lu_one_wg) {
-        bool timed_out = false;
-        for (int b = 0; b < n; ++b) timed_out |= info[b] == EMME_EDEVICE;
-        if (timed_out) {
-            c->lu_one_wg = true;
-            if (std::getenv("EMME_DEBUG")) fprintf(stderr, "[emme] LU hand-over timed out: repeating the search with one workgroup per matrix\n");
-            return emme_solve_roots(c, guesses, n, tol, step_limit, roots, iters, info, iterates);
-        }
-    }
-    return EMME_OK;
+    return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 2 | 4 | 8, secant_loop);
 }
 
 int emme_assemble_derivative_batch(emme_ctx_t* c, const double* omega, int nbatch, double* M, double* Mp,
@@ -881,128 +976,23 @@ int emme_assemble_derivative_batch(emme_ctx_t* c, const double* omega, int nbatc
         set_error("M and Mp must both be host or both be device pointers");
         return EMME_EINVAL;
     }
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
+    EMME_TRY(ensure_batch(c, nbatch));
     double *dM = M, *dMp = Mp;
     if (!dev_out) {
-        rc = ensure_mats(c, nbatch, 1 | 4);
-        if (rc) return rc;
+        EMME_TRY(ensure_mats(c, nbatch, 1 | 4));
         dM = c->d_M, dMp = c->d_Mp;
     }
-    HIP_TRY(hipMemcpyAsync(c->d_omega, omega, sizeof(double) * 2 * nbatch, hipMemcpyDefault, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * nbatch, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * nbatch, c->stream));
-    rc = do_assemble_deriv(c, nbatch, c->d_omega, nullptr, nullptr, dM, dMp);
-    if (rc) return rc;
+    EMME_TRY(fill_at(c, omega, nbatch, dM, dMp, hipMemcpyDefault));
     if (!dev_out) {
         HIP_TRY(hipMemcpyAsync(M, dM, mat_doubles(c) * sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(Mp, dMp, mat_doubles(c) * sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
     }
-    std::vector<unsigned long long> iv(nbatch);
-    std::vector<int> stv(nbatch);
-    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    bool bad = false;
-    for (int b = 0; b < nbatch; ++b) {
-        c->acc.gk_intervals += (long long)iv[b];
-        if (intervals) intervals[b] = (long long)iv[b];
-        bad |= stv[b] != 0;
-    }
-    if (bad) {
-        set_error("quadrature depth cap hit or non-finite integral in at least one item");
-        return EMME_ENUMERIC;
-    }
-    return EMME_OK;
+    return collect_fill_status(c, nbatch, intervals);
 }
 
 int emme_solve_roots_newton(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit, double* roots,
                             int* iters, int* info, double* iterates) {
-    if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
-    const int method = c->p.iteration_method;
-    int rc = check_method(c, method);
-    if (rc) return rc;
-    HIP_TRY(hipSetDevice(c->device));
-    rc = ensure_batch(c, n);
-    if (rc) return rc;
-    rc = ensure_mats(c, n, 1 | 4 | 8);
-    if (rc) return rc;
-    const int stride = step_limit + 1;
-    if (iterates) {
-        const size_t need = (size_t)n * stride * 2;
-        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
-        std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
-        HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-    }
-    // omega_0 = g: one fill of M and the exact M' there, no secant bootstrap
-    std::vector<int> act(n, 1), zeros(n, 0);
-    HIP_TRY(hipMemcpyAsync(c->d_active, act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_iters, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_info, zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_intervals, 0, sizeof(unsigned long long) * n, c->stream));
-    HIP_TRY(hipMemsetAsync(c->d_status, 0, sizeof(int) * n, c->stream));
-    HIP_TRY(hipMemcpyAsync(c->d_omega, guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
-    rc = do_assemble_deriv(c, n, c->d_omega, c->d_active, act.data(), c->d_M, c->d_Mp);
-    if (rc) return rc;
-    for (int j = 0; j <= step_limit; ++j) {
-        {
-            // the step of the context's iteration_method on (M, M'): trace form on a work copy of M (the LU destroys
-            // both operands; M' is filled again before it is needed), QR form on the transpose
-            ScopedSpan s(c, K_LIN);
-            const bool trace = method == EMME_METHOD_TRACE_SECANT;
-            if (trace) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
-            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
-                                act.data(), trace));
-        }
-        {
-            ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
-                                         iterates ? c->d_iterates.get() : nullptr, j, stride, c->stream, nullptr,
-                                         c->opt.skip_lost ? c->d_status : nullptr));
-        }
-        // the live chains (2 = converged at this step: M and M' are filled at the new omega once more)
-        HIP_TRY(hipMemcpyAsync(c->p_act, c->d_active, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        bool any = false;
-        for (int b = 0; b < n; ++b) {
-            act[b] = c->p_act[b];
-            any |= act[b] != 0;
-        }
-        if (!any) break;
-        rc = do_assemble_deriv(c, n, c->d_omega, c->d_active, act.data(), c->d_M, c->d_Mp);
-        if (rc) return rc;
-        {
-            ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_retire(n, c->d_active, c->stream));
-        }
-    }
-    std::vector<unsigned long long> iv(n);
-    std::vector<int> stv(n);
-    HIP_TRY(hipMemcpyAsync(roots, c->d_omega, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(iters, c->d_iters, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(iv.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(stv.data(), c->d_status, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
-    if (iterates)
-        HIP_TRY(hipMemcpyAsync(iterates, c->d_iterates, sizeof(double) * 2 * (size_t)n * stride, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    c->last_n = n;
-    for (int b = 0; b < n; ++b) {
-        c->acc.gk_intervals += (long long)iv[b];
-        if (stv[b] != 0 && info[b] == 0) info[b] = EMME_ENUMERIC;
-        if (info[b] == 0 && !(std::isfinite(roots[2 * b]) && std::isfinite(roots[2 * b + 1]))) info[b] = EMME_ENUMERIC;
-    }
-    // (a multi-workgroup LU whose hand-over timed out: again with one workgroup per matrix, as emme_solve_roots does)
-    if (!c->lu_one_wg) {
-        bool timed_out = false;
-        for (int b = 0; b < n; ++b) timed_out |= info[b] == EMME_EDEVICE;
-        if (timed_out) {
-            c->lu_one_wg = true;
-            return emme_solve_roots_newton(c, guesses, n, tol, step_limit, roots, iters, info, iterates);
-        }
-    }
-    return EMME_OK;
+    return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop);  // (no M_old)
 }
 
 int emme_bessel_batch(const double* z, int n, double* out) {
@@ -1088,8 +1078,7 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
         return EMME_ECONFIG;
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ensure_batch(c, nbatch);
-    if (rc) return rc;
+    EMME_TRY(ensure_batch(c, nbatch));
     const size_t mbytes = (size_t)n * n * 2 * sizeof(double);
     // device scratch of this call
     DeviceBuffer<double> t_a, t_v;
@@ -1113,7 +1102,7 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
     // 11.6 ms / 2.7e-14, 30 sweeps 6.7 ms / 8.9e-14, 20 sweeps 4.9 ms / 2.2e-9
     const int max_sweeps = 30;
     LuScratch scratch;
-    rc = lu_factor_batch(c, n, nbatch, work, scratch, "emme_null_vectors_batch",
+    const int rc = lu_factor_batch(c, n, nbatch, work, scratch, "emme_null_vectors_batch",
                               [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
                                   return launch_null_iterate(n, work + (size_t)b0 * n * n * 2, maps, map_nb, nullptr,
                                                              nb, lu_info, t_v + (size_t)b0 * n * 2, t_info + b0,
