@@ -99,6 +99,7 @@ class Options(C.Structure):
         ("skip_lost", C.c_int),
         ("lu_split", C.c_int), ("lu_group_min_n", C.c_int), ("lu_spin_limit", C.c_int),
         ("lu_unblocked", C.c_int),
+        ("deriv_cached", C.c_int),
     ]
 
 
@@ -524,8 +525,9 @@ class Context:
         return iv
 
     def assemble_derivative(self, omegas, want_intervals=False):
-        """M(omega) and the exact M'(omega) of the same quadrature trees, through the uncached kernels:
-        returns (M, Mp[, intervals])."""
+        """M(omega) and the exact M'(omega) of the same quadrature trees, through the uncached kernels
+        (option deriv_cached = 1: through the node cache where the context has the tiled one): returns
+        (M, Mp[, intervals])."""
         w = _c128(np.atleast_1d(omegas))
         nb = w.shape[0]
         iv = np.zeros(nb, dtype=np.int64)

@@ -168,7 +168,8 @@ struct FillRequest {
     const int* d_active = nullptr;       // which items to assemble (null = all), and its host image
     const int* host_active = nullptr;
     double* d_M;
-    double* d_Md = nullptr;              // set: the exact dM/domega beside M, uncached kernels only
+    double* d_Md = nullptr;              // set: the exact dM/domega beside M; through the node cache
+                                         // only with the option deriv_cached, where k_assemble_dense_deriv applies
     const double* d_Mold = nullptr;      // fused secant: Mp = (M - Mold) / domega
     double* d_Mp = nullptr;
     const double* d_domega = nullptr;

@@ -18,6 +18,14 @@ FillShape shape_of(const emme_ctx* c) {
     return s;
 }
 
+// A derivative request that may go through the node cache (option deriv_cached): k_assemble_dense_deriv
+// exists for electrostatic GK15 on the tiled layout, and the contour classes need the omegas' host values.  Every other
+// derivative request keeps the uncached kernels.
+bool deriv_from_cache(const emme_ctx* c, const FillRequest& r) {
+    return r.d_Md && c->opt.deriv_cached != 0 && c->tiled && c->nm == 1 && c->p.integration_start_points == 15 &&
+           r.host_omega != nullptr;
+}
+
 // what the fill kernels are told: the context's tables and counters, the request's operands and, for the plain
 // fills, the context's options (a derivative fill runs its two kernels on the struct defaults)
 AssembleLaunch make_launch(const emme_ctx* c, const FillRequest& r) {
@@ -53,9 +61,10 @@ AssembleLaunch make_launch(const emme_ctx* c, const FillRequest& r) {
 // The cache costs a few hundred ms of kernels plus the allocation of up to ~170 GB to build
 // and pays off after ~10 fills: a call with a handful of omegas (a single root of a
 // parameter scan) goes through the on-the-fly kernels unless the cache already exists.
-// (The contour classes need the omegas' host values; the derivative kernels do not read the cache.)
+// (The contour classes need the omegas' host values; a derivative request reads the cache only where
+// deriv_from_cache says so.)
 bool wants_cache(const emme_ctx* c, const FillRequest& r) {
-    return !r.d_Md && !r.force_uncached && r.host_omega != nullptr && c->cache_depth != -2 &&
+    return (!r.d_Md || deriv_from_cache(c, r)) && !r.force_uncached && r.host_omega != nullptr && c->cache_depth != -2 &&
            (r.nbatch >= c->opt.cache_min_batch || c->cache[0].recs || c->cache[1].recs);
 }
 
@@ -220,6 +229,33 @@ int launch_cached_lanes(emme_ctx* c, const AssembleLaunch& L, const NodeCacheVie
     return EMME_OK;
 }
 
+// M and M' from the tiled cache: twin-column phase tables, then one wave per (16-pair tile, chunk of <= 8 omegas), then
+// the integrals that left the cache through the list-driven from-scratch derivative kernel
+int launch_dense_deriv(emme_ctx* c, const AssembleLaunch& L, const NodeCacheView& cache, const FillRequest& r, int n_lane,
+                       int nchunks) {
+    for (int k = 0; k < nchunks; ++k)
+        if (c->h_chunks[2 * k + 1] > 8) {
+            set_error("derivative fill: a chunk of more than 8 omegas was planned");
+            return EMME_EINVAL;
+        }
+    const int n_int = node_cache_intervals(c->cache_geom);
+    const size_t need = btab_bytes(n_int, nchunks, L.gk_points);
+    if (need > c->d_btab.bytes()) HIP_TRY(c->d_btab.grow(need + need / 4));
+    {
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(launch_btab_deriv(n_int, cache, r.d_omega, c->d_actidx, n_lane, c->d_chunks + 2 * nchunks, nchunks, c->d_btab,
+                                  c->stream));
+    }
+    {
+        ScopedSpan s(c, K_ASM);
+        HIP_TRY(launch_assemble_dense_deriv(L, cache, c->d_btab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
+                                            c->d_actidx, c->d_chunks, nchunks, c->d_rounds, c->stream));
+    }
+    ScopedSpan s(c, K_DEFER);
+    HIP_TRY(launch_assemble_deriv_list(L, c->d_worklist, c->d_worklist_count, c->stream));
+    return EMME_OK;
+}
+
 // the integrals the cached kernels could not finish from the cache
 int launch_deferred(emme_ctx* c, const AssembleLaunch& L, const NodeCacheView& cache) {
     ScopedSpan s(c, K_DEFER);
@@ -243,10 +279,21 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
     HIP_TRY(c->d_worklist.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_defer_info.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_worklist_count.grow(sizeof(unsigned int)));
-    const ChunkPlan plan = plan_chunks(shape_of(c), c->h_actidx, r.cost, n_wide, c->h_chunks);
+    FillShape shape = shape_of(c);
+    shape.deriv = r.d_Md != nullptr;
+    const ChunkPlan plan = plan_chunks(shape, c->h_actidx, r.cost, n_wide, c->h_chunks);
     L.items_per_group = plan.items_per_group;
     EMME_TRY(stage_lists(c, &c->h_chunks));
     HIP_TRY(hipMemsetAsync(c->d_worklist_count, 0, sizeof(unsigned int), c->stream));
+    if (r.d_Md) {
+        // (make_launch leaves a derivative request on the struct defaults, which the uncached kernels keep; here the
+        // context's options apply as to a plain dense fill.  last_fill_mode keeps naming the last plain fill.)
+        L.skip_lost = r.newton_loop && c->opt.skip_lost != 0;
+        L.dense_min_cols = c->opt.dense_min_cols;
+        EMME_TRY(launch_dense_deriv(c, L, cache, r, n_lane, plan.nchunks));
+        if (std::getenv("EMME_DEBUG")) print_deferred(c, n_lane);
+        return EMME_OK;
+    }
     c->last_fill_mode = c->tiled ? FILL_DENSE : (plan.union_walk ? FILL_CACHED_UNION : FILL_CACHED_LANES);
     EMME_TRY(c->tiled ? launch_dense(c, L, cache, r, n_lane, plan.nchunks, n_wide)
                       : launch_cached_lanes(c, L, cache, r, n_lane, plan.nchunks));
@@ -296,7 +343,8 @@ int fill_by_class(emme_ctx* c, const FillRequest& r, int minority) {
 int fill(emme_ctx* c, const FillRequest& r) {
     // omegas whose level lists overflowed in their previous fill (root search only): first, a chunk each, through the
     // wide-list build of the dense fill
-    const bool has_wide = r.newton_loop && c->tiled && c->nm == 1 && !c->h_wide.empty();
+    // (a derivative request has no wide-list build)
+    const bool has_wide = r.newton_loop && !r.d_Md && c->tiled && c->nm == 1 && !c->h_wide.empty();
     const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->h_wide.data() : nullptr, c->h_actidx);
     const int n_act = (int)c->h_actidx.size();
     if (n_act == 0) return EMME_OK;

@@ -108,6 +108,7 @@ void options_default(emme_options_t& o) {
     o.lu_group_min_n = 256;
     o.lu_spin_limit = 16000000;  // about 4 s
     o.lu_unblocked = 0;
+    o.deriv_cached = 0;
 }
 
 // The EMME_* environment variables: developer overrides, read ONCE per context (at creation), winning over
@@ -143,6 +144,7 @@ void options_env_overrides(emme_options_t& o) {
     if (const char* e = std::getenv("EMME_LU_GROUP")) o.lu_group_min_n = std::atoi(e) <= 0 ? -1 : std::atoi(e);
     geti("EMME_LU_SPIN_LIMIT", o.lu_spin_limit);
     if (std::getenv("EMME_LU_UNBLOCKED")) o.lu_unblocked = 1;
+    geti("EMME_DERIV_CACHED", o.deriv_cached);
 }
 
 int options_check(const emme_options_t* o) {
@@ -154,7 +156,7 @@ int options_check(const emme_options_t* o) {
         o->fill > EMME_FILL_LANES || o->wl_min < 1 || (o->union_sel != 1 && o->union_sel != 2 && o->union_sel != 4) ||
         o->union_ipg_few < 1 || o->union_few_chunks < 0 || o->coop_wide_min < -1 || o->dense_min_cols < 1 ||
         o->dense_min_cols > 17 || o->dense_min_tasks < 0 || !(o->dense_cost_ratio > 0.0) || o->lu_split < 0 ||
-        o->lu_split > 16 || o->lu_spin_limit < 1) {
+        o->lu_split > 16 || o->lu_spin_limit < 1 || o->deriv_cached < 0 || o->deriv_cached > 1) {
         set_error("emme_options_t: value out of range");
         return EMME_EINVAL;
     }
@@ -294,14 +296,14 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
 }
 
 // one fill of a plain assembly call: the omegas into d_omega, counters zeroed, M (and, dMd given, the exact
-// derivative) queued.  The node cache needs the omegas' host values, so the derivative entry point, which also takes
-// device omegas, goes without.
+// derivative) queued.  The node cache needs the omegas' host values: the derivative entry point, which also takes
+// device omegas, hands them on only with the option deriv_cached, and only if they are on the host.
 int fill_at(emme_ctx* c, const double* omega, int nbatch, double* dM, double* dMd, hipMemcpyKind kind) {
     EMME_TRY(upload_omega(c, omega, nbatch, kind));
     EMME_TRY(reset_fill_counters(c, nbatch));
     FillRequest r(nbatch, c->d_omega, dM);
     r.d_Md = dMd;
-    if (!dMd) r.host_omega = omega;
+    if (!dMd || (c->opt.deriv_cached != 0 && !is_device_ptr(omega))) r.host_omega = omega;
     return fill(c, r);
 }
 
@@ -539,7 +541,32 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
     HIP_TRY(hipMemcpyAsync(c->d_omega, search.guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
     FillRequest both(n, c->d_omega, c->d_M);
     both.d_Md = c->d_Mp, both.d_active = c->d_active, both.host_active = act.data();
+    // Option deriv_cached: the fills may go through the node cache, which needs what the secant loop gives its fills --
+    // the live omegas on the host (contour classes), every omega's interval count of its previous fill (cost order)
+    // and the root-search flag (skip_lost).  They travel as there: k_newton_update writes the omegas, k_retire the
+    // counters and the deferred count into pinned memory, read after the step's one synchronisation.
+    const bool cached = c->opt.deriv_cached != 0;
+    std::vector<double> h_w;
+    std::vector<unsigned long long> iv_prev, cost;
+    bool pending = false;
+    if (cached) {
+        h_w.assign(search.guesses, search.guesses + 2 * (size_t)n);
+        iv_prev.assign(n, 0), cost.assign(n, 0);
+        both.host_omega = h_w.data(), both.newton_loop = true;
+        c->pub_valid = false;
+    }
+    auto publish = [&]() -> hipError_t {
+        if (!cached) return launch_retire(n, c->d_active, c->stream);
+        pending = true;
+        return launch_retire(n, c->d_active, c->stream, nullptr, c->d_intervals, c->p_iv, c->d_worklist_count, c->p_deferred);
+    };
     EMME_TRY(fill(c, both));
+    if (cached) {
+        // (the first fill's counts order the second; no chain has been retired yet: every flag is 1)
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(publish());
+        both.cost = cost.data();
+    }
     for (int j = 0; j <= step_limit; ++j) {
         {
             // the step of the context's iteration_method on (M, M'): trace form on a work copy of M (the LU destroys
@@ -553,7 +580,7 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
         {
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
-                                         d_iterates, j, stride, c->stream, nullptr,
+                                         d_iterates, j, stride, c->stream, cached ? c->p_w.get() : nullptr,
                                          c->opt.skip_lost ? c->d_status : nullptr));
         }
         // the live chains (2 = converged at this step: M and M' are filled at the new omega once more)
@@ -565,10 +592,22 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
             any |= act[b] != 0;
         }
         if (!any) break;
+        if (cached) {
+            std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
+            if (pending) {  // what the previous fill left behind
+                for (int b = 0; b < n; ++b) {
+                    const unsigned long long now = c->p_iv[b];
+                    if (now != iv_prev[b]) cost[b] = now - iv_prev[b];
+                    iv_prev[b] = now;
+                }
+                c->last_deferred = *c->p_deferred, c->pub_valid = true;
+                pending = false;
+            }
+        }
         EMME_TRY(fill(c, both));
         {
             ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_retire(n, c->d_active, c->stream));
+            HIP_TRY(publish());
         }
     }
     return EMME_OK;

@@ -71,7 +71,8 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
         // EMME_DENSE_MIN_TASKS (2000; 8000 while every lane ended with a global atomic -- with the counters
         // summed per workgroup 0 .. 3000 are equal, 44.7 ms of fill per bench search, and 8000 costs 45.8)
         // (dense fill: a chunk is 16 COLUMNS -- 16 omegas, or 5 omegas x 3 moments)
-        const int tile_cap = 16 / s.nm;
+        // (a derivative request, s.deriv: K and K' of an omega are twin columns -- 8 omegas)
+        const int tile_cap = s.deriv ? 8 : 16 / s.nm;
         int dense_cap = s.tiled ? tile_cap : gw;
         if (s.tiled) {
             const long ntiles = (s.npairs + 15) / 16;
@@ -79,7 +80,7 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
             while (dense_cap > 2 && ((long)order.size() + dense_cap - 1) / dense_cap * ntiles < min_tasks) dense_cap >>= 1;
         }
         size_t q = 0;
-        for (; q < (size_t)n_wide; ++q) ch.push_back((int)q), ch.push_back(1);
+        for (; !s.deriv && q < (size_t)n_wide; ++q) ch.push_back((int)q), ch.push_back(1);
         while (q < order.size()) {
             int cap = s.tiled ? dense_cap : gw;
             while ((!plan.union_walk || s.tiled) && cap > (s.tiled ? 2 : 1) &&

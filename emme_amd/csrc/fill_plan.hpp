@@ -15,6 +15,7 @@ struct FillShape {
     int dense_min_tasks = 2000;
     double dense_cost_ratio = 4.0;
     int union_ipg_few = 2, union_few_chunks = 3;
+    bool deriv = false;  // a derivative request on the tiled cache: twin columns, so a chunk holds 8 omegas, never wide
     int lane_group() const { return gk_points == 15 ? 16 : 32; }
 };
 
@@ -40,7 +41,7 @@ int items_per_group_for(const FillShape& s, long units);
 
 // The cached fill's omega chunks over an order that plan_order made: chunks <- (first position, size) per chunk
 // and, for the dense fill (s.tiled), behind them position -> (chunk << 8 | column).  The first n_wide positions
-// get a chunk each.
+// get a chunk each (none of them for a derivative request, s.deriv: it has no wide-list build).
 struct ChunkPlan {
     bool union_walk = false;  // the union-walk kernel's policy: full chunks, three items per group
     int nchunks = 0;

@@ -41,7 +41,7 @@ struct AssembleLaunch {
     int coop_wide_min = 4096;  // deferred list: length from which the one-wave cooperative kernel takes over (-1 never)
     int defer_one_group = 0;   // deferred integrals by one lane group each
     int dense_min_cols = 3;    // dense fill: columns that must need an interval for the MFMA path
-    double* Md = nullptr;      // device or null: exact dM/domega beside M (uncached kernels only; Mold must be null)
+    double* Md = nullptr;      // device or null: exact dM/domega beside M (Mold must be null)
 };
 // What the launchers that read the node cache see of it: its geometry and, per contour class (omi = +1, -1), the
 // main records, the run-time subtrees (null if absent), the T table, the moment-factor table and the tile-poison
@@ -113,6 +113,19 @@ hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& c
                                  unsigned long long* defer_info, const int* act_idx, int n_act,
                                  const void* chunks, int nchunks, unsigned long long* stats, hipStream_t stream,
                                  int n_wide = 0, unsigned int* overflow = nullptr);
+
+// ---- M and the exact dM/domega from the tiled cache: assemble_dense_deriv.hip (electrostatic GK15, L.Md set) ------
+// chunks hold <= 8 omegas: column c of a chunk's phase block is E' of omega c, column c + 8 its D' = T E'
+// (btab_bytes(cached intervals, chunks) as for the plain fill)
+hipError_t launch_btab_deriv(int nslots, const NodeCacheView& cache, const double* omega, const int* act_idx, int n_act,
+                             const int* wmap, int nchunks, void* btab, hipStream_t stream);
+hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheView& cache, const void* btab,
+                                       unsigned long long* worklist, unsigned int* worklist_count,
+                                       unsigned long long* defer_info, const int* act_idx, const void* chunks,
+                                       int nchunks, unsigned long long* stats, hipStream_t stream);
+// the integrals that kernel handed over (work list of batch << 32 | pair): M and M' from scratch, a lane group each
+hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
+                                      const unsigned int* count, hipStream_t stream);
 
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,

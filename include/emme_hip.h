@@ -104,6 +104,10 @@ typedef struct emme_options {
     int lu_group_min_n;       /* smallest order that takes the grouped trailing updates (256); -1 never   */
     int lu_spin_limit;        /* polls before a hand-over wait of the multi-workgroup LU gives up         */
     int lu_unblocked;         /* 1: the unblocked LU                                                      */
+    /* ---- exact derivative (addition within version 4: present if size covers it) ---- */
+    int deriv_cached;         /* 1: derivative fills of electrostatic GK15 contexts with the tiled node cache read and
+                                 grow that cache (k_assemble_dense_deriv); 0 (default): always uncached.
+                                 Not a layout option: it may change on a live context                        */
 } emme_options_t;
 
 const char* emme_last_error(void);
@@ -216,8 +220,11 @@ int emme_solve_roots(emme_ctx_t* ctx, const double* guesses, int n, double tol, 
  * derivative rides along the quadrature, the accept/split decisions and M are those of the plain fill of the same
  * kernel bit for bit.  Pointers as emme_assemble_batch (omega host or device; M and Mp both host or both device).
  * Batches of wl_min or more go through the omega-lane kernel, smaller ones through the lanes-are-nodes kernel, on
- * every context: the node cache is neither read nor grown (emme_ctx_cache_state is unchanged), and
- * emme_ctx_fill_mode keeps naming the last plain fill.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
+ * every context: the node cache is neither read nor grown (emme_ctx_cache_state is unchanged) unless deriv_cached is
+ * set, and emme_ctx_fill_mode keeps naming the last plain fill.  With the option deriv_cached, a call with host omegas
+ * on an electrostatic GK15 context with the tiled cache follows the cache policy of emme_assemble_batch instead: M and
+ * M' come from the cached records (k_assemble_dense_deriv), the same interval trees, M and M' within the project's
+ * 1e-10 bar of the uncached fill, and the cache may be built or grown.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
  * integral), and also when an entry of M' is non-finite or beyond the range M is held to: a fill whose M alone the
  * plain fill accepts can then fail. */
 int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nbatch, double* M, double* Mp,
@@ -226,7 +233,8 @@ int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nba
  * rule as emme_solve_roots, but starting at omega_0 = g (no 0.99 g / 0.01 g bootstrap), and every step fills M and M'
  * at the current omega of the live chains.  The step is the context's iteration_method on (M, M'): trace form
  * domega = -1/tr(M^-1 M'), QR form domega = -1/q.  emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) see the
- * last fill's M per chain afterwards.  Derivative fills count in the emme_profile_t fill counters. */
+ * last fill's M per chain afterwards.  Derivative fills count in the emme_profile_t fill counters.  With the option
+ * deriv_cached the fills of the search go through the node cache where emme_assemble_derivative_batch's would. */
 int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
                             double* roots, int* iters, int* info, double* iterates);
 /* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton call (dim*dim complex). */

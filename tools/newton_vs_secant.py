@@ -9,6 +9,9 @@ Three ways of running the bench's 128-guess lattice:
             built, so every fill is a from-scratch lanes-are-nodes fill -- the reference's parameter-scan workload
 For each: fills (matrices assembled) per converged chain, ms per call (per guess for `scan`), converged chains and the
 distinct roots reached.  Also the cost of one fill: plain against derivative, per kernel.
+--deriv-cached adds the option deriv_cached = 1 (derivative fills through the node cache, k_assemble_dense_deriv): the
+cached rows are then printed for both settings (`cached` = 0, `cached+dc` = 1, one context each, same process and
+device), and the fill-cost table gets the cached derivative fill of the 128 omegas.
 --out FILE writes the numbers as JSON."""
 import argparse
 import json
@@ -62,6 +65,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--deriv-cached", action="store_true")
     a = ap.parse_args()
     d = bench.workload_dict(256)
     lattice = bench.lattice(1, 0, 128)
@@ -69,7 +73,10 @@ def main():
     res = {"workload": "BASELINE configs[2], npoints 256, 128-guess lattice", "modes": {}, "fill_ms": {}}
     reached = {}
 
-    for mode, opt in (("cached", {}), ("uncached", {"node_cache_gb": 0.0})):
+    runs = [("cached", {}), ("uncached", {"node_cache_gb": 0.0})]
+    if a.deriv_cached:
+        runs.insert(1, ("cached+dc", {"deriv_cached": 1}))
+    for mode, opt in runs:
         with emme_amd.Context(emme_amd.params_from_dict(d), device=0, **opt) as ctx:
             ctx.profile(True)
             for method in ("secant", "newton"):
@@ -90,9 +97,14 @@ def main():
                     p = fill_cost(ctx, om, a.repeat, False)
                     q = fill_cost(ctx, om, a.repeat, True)
                     res["fill_ms"][name] = {"plain": p, "derivative": q, "ratio": q / p}
-            else:
+            elif mode == "cached":
                 p = fill_cost(ctx, lattice, a.repeat, False)
                 res["fill_ms"]["cached plain, 128 omegas"] = {"plain": p}
+            else:
+                p = fill_cost(ctx, lattice, a.repeat, False)
+                q = fill_cost(ctx, lattice, a.repeat, True)
+                res["fill_ms"]["cached derivative (k_assemble_dense_deriv), 128 omegas"] = {
+                    "plain": p, "derivative": q, "ratio": q / p}
 
     with emme_amd.Context(emme_amd.params_from_dict(d), device=0) as ctx:
         ctx.profile(True)
@@ -111,7 +123,7 @@ def main():
                 "ms_per_call": tot_ms / len(scan), "calls": len(scan), "distinct_roots": len(rs)}
         assert ctx.cache_state()[0] == -1, "the scan built a node cache"
 
-    for mode in ("cached", "uncached", "scan"):
+    for mode in [m for m, _ in runs] + ["scan"]:
         s, n = reached[(mode, "secant")], reached[(mode, "newton")]
         only_s = [x for x in s if all(abs(x - y) > 1e-5 * abs(x) for y in n)]
         only_n = [x for x in n if all(abs(x - y) > 1e-5 * abs(x) for y in s)]
@@ -122,7 +134,7 @@ def main():
     for k, v in res["modes"].items():
         print(f"{k:18s} " + "  ".join(f"{kk} {vv:.4g}" if isinstance(vv, float) else f"{kk} {vv}" for kk, vv in v.items()))
     for k, v in res["fill_ms"].items():
-        print(f"fill {k:28s} " + "  ".join(f"{kk} {vv:.4g}" for kk, vv in v.items()))
+        print(f"fill {k:60s} " + "  ".join(f"{kk} {vv:.4g}" for kk, vv in v.items()))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(res, f, indent=1)
