@@ -142,6 +142,8 @@ def load():
     lib.emme_weight.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.emme_weight.restype = C.c_double
     lib.emme_bessel_batch.argtypes = [P, C.c_int, P]
+    lib.emme_elementary_batch.argtypes = [C.c_int, P, C.c_int, P]
+    lib.emme_integrand_batch.argtypes = [PP, C.c_int, C.c_int, P, P, P, P, P, P]
     lib.emme_ctx_create.argtypes = [PP, C.c_int, C.POINTER(P)]
     lib.emme_options_default.argtypes = [C.POINTER(Options)]
     lib.emme_options_default.restype = None
@@ -259,6 +261,39 @@ def bessel(z) -> np.ndarray:
     z = np.ascontiguousarray(np.atleast_1d(z), dtype=np.complex128)
     out = np.zeros((len(z), 4), dtype=np.complex128)
     _check(load().emme_bessel_batch(z.ctypes.data, len(z), out.ctypes.data))
+    return out
+
+
+# emme_elementary_batch: name -> (fn, doubles in, doubles out) per item
+ELEMENTARY = {"rcp": (0, 1, 1), "rsqrt": (1, 1, 1), "exp": (2, 1, 1), "exp_s": (3, 1, 1), "exp_v": (4, 1, 1),
+              "sincos": (5, 1, 2), "sincos_s": (6, 1, 2), "sincos_v": (7, 1, 2), "crcp": (8, 2, 2)}
+FORM_F, FORM_F_DF, FORM_SPLIT, FORM_W = 0, 1, 2, 3
+
+
+def elementary(fn: str, x) -> np.ndarray:
+    """One device math primitive of the fill per argument (emme_elementary_batch): [n] for rcp / rsqrt / exp*,
+    [n, 2] = (sin, cos) for sincos*, complex [n] in and out for crcp."""
+    code, n_in, n_out = ELEMENTARY[fn]
+    x = np.ascontiguousarray(np.atleast_1d(x), dtype=np.complex128 if n_in == 2 else np.float64)
+    out = np.zeros((len(x), n_out))
+    _check(load().emme_elementary_batch(code, x.ctypes.data, len(x), out.ctypes.data))
+    if fn == "crcp":
+        return out.view(np.complex128)[:, 0]
+    return out[:, 0] if n_out == 1 else out
+
+
+def integrand(p: Params, form: int, i, j, m, x, omega) -> np.ndarray:
+    """The device's pointwise integrand per item (emme_integrand_batch), complex [n, k]: form 0: F; 1: F, F';
+    2: A0, T, Q1, Q0, F; 3: W."""
+    i, j, m = (np.ascontiguousarray(a, dtype=np.int32) for a in (i, j, m))
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    w = np.ascontiguousarray(omega, dtype=np.complex128)
+    n = len(x)
+    if not (len(i) == len(j) == len(m) == len(w) == n):
+        raise ValueError("i, j, m, x and omega need one entry per item")
+    out = np.zeros((n, {0: 1, 1: 2, 2: 5, 3: 1}.get(form, 1)), dtype=np.complex128)
+    _check(load().emme_integrand_batch(C.byref(p), form, n, i.ctypes.data, j.ctypes.data, m.ctypes.data, x.ctypes.data,
+                                       w.ctypes.data, out.ctypes.data))
     return out
 
 

@@ -849,28 +849,4 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
     return hipGetLastError();
 }
 
-
-// ---- the Bessel helper alone (tests / tooling) ---------------------------------------------------
-// util::bessel_i_alter_helper (include/functions.h:381-408) as the fill kernels evaluate it:
-// out = {y0, y1, mu + y0, Re z < 0 ? z : -z} per argument.
-namespace {
-__global__ void k_bessel_probe(const double2* z, int n, double2* out) {
-    const int k = blockIdx.x * blockDim.x + threadIdx.x;
-    if (k >= n) return;
-    const cd zz = mk(z[k].x, z[k].y);
-    const double zabs = sqrt(norm2(zz));
-    cd y0, y1, mutot;
-    bessel_miller(rcp(zz), zabs, 1.0 / zabs, zz.x < 0.0, y0, y1, mutot);
-    out[4 * k + 0] = make_double2(y0.x, y0.y);
-    out[4 * k + 1] = make_double2(y1.x, y1.y);
-    out[4 * k + 2] = make_double2(mutot.x, mutot.y);
-    out[4 * k + 3] = zz.x < 0.0 ? make_double2(zz.x, zz.y) : make_double2(-zz.x, -zz.y);
-}
-}  // namespace
-hipError_t launch_bessel_probe(const double* z, int n, double* out, hipStream_t stream) {
-    hipLaunchKernelGGL(k_bessel_probe, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, stream, (const double2*)z, n,
-                       (double2*)out);
-    return hipGetLastError();
-}
-
 }  // namespace emme

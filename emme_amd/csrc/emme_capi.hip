@@ -632,6 +632,30 @@ int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_l
 }  // namespace
 
 
+// The kernels' scalars and tables (eta | g | b) of a parameter set: what every context launches with, and what the
+// probe entry points (emme_integrand_batch) evaluate single nodes with.
+static void dev_params_from(const emme_params_t* p, DevParams& P, std::vector<double>& tab) {
+    const int N = p->npoints;
+    const bool es = std::fpclassify(p->beta_e) == FP_ZERO;  // include/solver.h:406-407
+    tab.assign(3 * (size_t)N, 0.0);
+    double dx = 0;
+    emme_tables(p, tab.data(), tab.data() + N, tab.data() + 2 * N, &dx);
+    P.N = N, P.dim = es ? N : 2 * N, P.nm = es ? 1 : 3, P.max_sub = p->integration_iteration_limit;
+    P.dx = dx;
+    P.inv_arc = 1.0 / p->arc_coeff;
+    P.qR = p->q * p->R;
+    P.vt = p->vt;
+    P.cb = (p->q * p->R) / p->vt * (p->omega_d_bar);                                  // :88
+    P.cbe = (p->q * p->R) / p->vt * (p->omega_d_bar * p->omega_s_e / p->omega_s_i);  // :93
+    P.omega_s_i = p->omega_s_i, P.omega_s_e = p->omega_s_e;
+    P.eta_i = p->eta_i, P.eta_e = p->eta_e, P.tau = p->tau;
+    P.rel_tol = p->integration_precision;
+    P.prec_goal = p->integration_accuracy;
+    P.pref = (p->q * p->R) / (p->vt * std::sqrt(2.0 * M_PI));
+    P.diag_a = 1.0 + 1.0 / p->tau;
+    P.diag_d = es ? 0.0 : (2.0 * p->tau) / p->beta_e;
+}
+
 extern "C" {
 
 const char* emme_last_error(void) { return g_error.c_str(); }
@@ -704,23 +728,8 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     c->tiled = wants_tiled(*p, es, c->folded, o.fill);
 
     DevParams& P = c->P;
-    std::vector<double> tab(3 * (size_t)N);
-    double dx = 0;
-    emme_tables(p, tab.data(), tab.data() + N, tab.data() + 2 * N, &dx);
-    P.N = N, P.dim = c->dim, P.nm = c->nm, P.max_sub = p->integration_iteration_limit;
-    P.dx = dx;
-    P.inv_arc = 1.0 / p->arc_coeff;
-    P.qR = p->q * p->R;
-    P.vt = p->vt;
-    P.cb = (p->q * p->R) / p->vt * (p->omega_d_bar);                                  // :88
-    P.cbe = (p->q * p->R) / p->vt * (p->omega_d_bar * p->omega_s_e / p->omega_s_i);  // :93
-    P.omega_s_i = p->omega_s_i, P.omega_s_e = p->omega_s_e;
-    P.eta_i = p->eta_i, P.eta_e = p->eta_e, P.tau = p->tau;
-    P.rel_tol = p->integration_precision;
-    P.prec_goal = p->integration_accuracy;
-    P.pref = (p->q * p->R) / (p->vt * std::sqrt(2.0 * M_PI));
-    P.diag_a = 1.0 + 1.0 / p->tau;
-    P.diag_d = es ? 0.0 : (2.0 * p->tau) / p->beta_e;
+    std::vector<double> tab;
+    dev_params_from(p, P, tab);
 
     // pair list ordered by diagonal offset (see assemble.hip header)
     std::vector<ushort2> pairs;
@@ -1034,20 +1043,90 @@ int emme_solve_roots_newton(emme_ctx_t* c, const double* guesses, int n, double 
     return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop);  // (no M_old)
 }
 
-int emme_bessel_batch(const double* z, int n, double* out) {
-    if (!z || !out || n < 1) return EMME_EINVAL;
+static int probe_device_check() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
         (void)hipGetLastError();
         set_error("no HIP device available (the MI355X path has no CPU fallback)");
         return EMME_EDEVICE;
     }
+    return EMME_OK;
+}
+
+int emme_bessel_batch(const double* z, int n, double* out) {
+    if (!z || !out || n < 1) return EMME_EINVAL;
+    EMME_TRY(probe_device_check());
     DeviceBuffer<double> dz, dout;
     HIP_TRY(dz.grow(sizeof(double) * 2 * n));
     HIP_TRY(dout.grow(sizeof(double) * 8 * n));
     HIP_TRY(hipMemcpy(dz, z, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
     HIP_TRY(launch_bessel_probe(dz, n, dout, nullptr));
     HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
+    return EMME_OK;
+}
+
+int emme_elementary_batch(int fn, const double* x, int n, double* out) {
+    if (!x || !out || n < 1 || fn < 0 || fn > EMME_FN_CRCP) return EMME_EINVAL;
+    EMME_TRY(probe_device_check());
+    const size_t n_in = fn == EMME_FN_CRCP ? 2 : 1;
+    const size_t n_out = fn >= EMME_FN_SINCOS ? 2 : 1;
+    DeviceBuffer<double> dx, dout;
+    HIP_TRY(dx.grow(sizeof(double) * n_in * n));
+    HIP_TRY(dout.grow(sizeof(double) * n_out * n));
+    HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n_in * n, hipMemcpyHostToDevice));
+    HIP_TRY(launch_elementary_probe(fn, dx, n, dout, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n_out * n, hipMemcpyDeviceToHost));
+    return EMME_OK;
+}
+
+int emme_integrand_batch(const emme_params_t* p, int form, int n, const int* i, const int* j, const int* m,
+                         const double* x, const double* omega, double* out) {
+    if (!p || !i || !j || !m || !x || !omega || !out || n < 1 || form < 0 || form > EMME_FORM_W) return EMME_EINVAL;
+    if (p->npoints < 2 || p->npoints > 65535) {
+        set_error("npoints must be in [2, 65535]");
+        return EMME_EINVAL;
+    }
+    // the scalars DevParams divides by: a zero or non-finite one would put inf / NaN into every item
+    for (const double v : {p->arc_coeff, p->vt, p->tau, p->q, p->R, p->omega_s_i}) {
+        if (!std::isfinite(v) || v == 0.0) {
+            set_error("emme_integrand_batch: arc_coeff, vt, tau, q, R and omega_s_i must be finite and non-zero");
+            return EMME_EINVAL;
+        }
+    }
+    const int nm = std::fpclassify(p->beta_e) == FP_ZERO ? 1 : 3;
+    for (int k = 0; k < n; ++k) {
+        const bool pair_ok = i[k] >= 0 && i[k] < j[k] && j[k] < p->npoints;
+        const bool x_ok = x[k] > 0.0 && x[k] < M_PI / 2;  // (false for NaN)
+        if (!pair_ok || m[k] < 0 || m[k] >= nm || !x_ok) {
+            set_error("emme_integrand_batch: item " + std::to_string(k) +
+                      " needs 0 <= i < j < npoints, a moment of the context (0, or 0..2 with beta_e != 0) and x in (0, pi/2)");
+            return EMME_EINVAL;
+        }
+    }
+    EMME_TRY(probe_device_check());
+    IntegrandProbe A;
+    std::vector<double> tab;
+    dev_params_from(p, A.P, tab);
+    A.form = form, A.n = n;
+    const size_t per = (size_t)integrand_probe_doubles(form);
+    DeviceBuffer<double> dtab, dx, dw, dout;
+    DeviceBuffer<int> dijm;
+    HIP_TRY(dtab.grow(sizeof(double) * tab.size()));
+    HIP_TRY(dx.grow(sizeof(double) * n));
+    HIP_TRY(dw.grow(sizeof(double) * 2 * n));
+    HIP_TRY(dout.grow(sizeof(double) * per * n));
+    HIP_TRY(dijm.grow(sizeof(int) * 3 * (size_t)n));
+    HIP_TRY(hipMemcpy(dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dw, omega, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    int* d_ijm = dijm;
+    HIP_TRY(hipMemcpy(d_ijm, i, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ijm + n, j, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ijm + 2 * (size_t)n, m, sizeof(int) * n, hipMemcpyHostToDevice));
+    A.tab = dtab, A.i = d_ijm, A.j = d_ijm + n, A.m = d_ijm + 2 * (size_t)n;
+    A.x = dx, A.omega = dw, A.out = dout;
+    HIP_TRY(launch_integrand_probe(A, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * per * n, hipMemcpyDeviceToHost));
     return EMME_OK;
 }
 

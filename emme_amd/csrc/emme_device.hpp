@@ -110,6 +110,13 @@ __device__ __forceinline__ double sreg(double c) {
     return c;
 }
 
+// The low 32 bits of an integer-valued double |n| < 2^51, in two's complement: adding 1.5 * 2^52 leaves them in the
+// low word of the sum (exact).  For the quadrant n mod 4 of the reductions below -- a conversion to int saturates
+// from |n| = 2^31 on (|x| = 3.4e9) and then names the wrong quadrant.
+__device__ __forceinline__ int quadrant_bits(double n) {
+    return __double2loint(n + 6755399441055744.0);
+}
+
 // sin and cos of a moderate argument (|x| < ~1e9): three-term Cody-Waite reduction by pi/2
 // carried by FMAs (the first FMA x - n*C1 is exact by cancellation), then the classical
 // degree-13 / degree-14 minimax kernels on [-pi/4, pi/4].  ~1 ulp, no slow path: the
@@ -136,7 +143,7 @@ __device__ __forceinline__ void fsincos(double x, double& s, double& c) {
     const double hz = 0.5 * z;
     const double wv = 1.0 - hz;
     const double cs = wv + (((1.0 - wv) - hz) + z * (z * pc));
-    const int q = (int)n & 3;
+    const int q = quadrant_bits(n) & 3;
     const double s0 = (q & 1) ? cs : sn;
     const double c0 = (q & 1) ? sn : cs;
     s = (q & 2) ? -s0 : s0;
@@ -231,7 +238,7 @@ __device__ __forceinline__ void fsincos(double x, double& s, double& c, const Tr
     const double cs = fma(z * z, pc, fma(-0.5, z, 1.0));  // |error| <= 1 ulp of 1
     // quadrant q = n mod 4: (cos, sin)(x) = rotation of (cs, sn) by q quarter turns; the signs go
     // straight into the sign bits
-    const unsigned q = (unsigned)(int)n;
+    const unsigned q = (unsigned)quadrant_bits(n);
     const bool odd = (q & 1u) != 0u;
     const double s0 = odd ? cs : sn;
     const double c0 = odd ? sn : cs;

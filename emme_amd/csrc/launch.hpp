@@ -205,7 +205,26 @@ hipError_t launch_stage_ints(const int* src_pinned, int* dst1, int n1, int* dst2
 hipError_t launch_secant(int nbatch, size_t nn, const double* M, const double* Mold,
                          const double* domega, const int* active, double* Mp, hipStream_t stream);
 
+// ---- probes (probe.hip): one building block of emme_device.hpp per thread, for tests and tooling ------------------
 // bessel_miller on n complex arguments (device pointers): out[4n] = y0, y1, mu + y0, -/+ z
 hipError_t launch_bessel_probe(const double* z, int n, double* out, hipStream_t stream);
+// one math primitive (fn = EMME_FN_* of include/emme_hip.h) on n arguments (device pointers): one double in and out
+// per item for frcp / frsqrt / fexp, one in and (sin, cos) out for fsincos, (re, im) in and out for the complex rcp
+hipError_t launch_elementary_probe(int fn, const double* x, int n, double* out, hipStream_t stream);
+// the pointwise integrand of n items (pair, moment, abscissa, omega; device pointers) in formulation `form`
+// (EMME_FORM_*); out holds integrand_probe_doubles(form) doubles per item
+struct IntegrandProbe {
+    DevParams P;
+    int form, n;
+    const double* tab;  // eta[N] | g[N] | b[N]
+    const int *i, *j, *m;
+    const double* x;
+    const double* omega;  // 2n
+    double* out;
+};
+__host__ __device__ constexpr int integrand_probe_doubles(int form) {
+    return form == 1 ? 4 : form == 2 ? 10 : 2;
+}
+hipError_t launch_integrand_probe(const IntegrandProbe& A, hipStream_t stream);
 
 }  // namespace emme

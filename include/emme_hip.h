@@ -240,6 +240,34 @@ int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, doubl
 /* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton call (dim*dim complex). */
 int emme_ctx_get_matrix(emme_ctx_t* ctx, int b, double* M_host);
 
+/* ---- point probes (additions within version 4: find them by symbol lookup; tests and tooling only) ---------------
+ * Like emme_bessel_batch: no context, host pointers, EMME_EDEVICE without a GPU, EMME_EINVAL on bad arguments
+ * (checked before the device is looked for).  Every item is evaluated by one thread, by the very device function
+ * the fill kernels call.
+ *
+ * One math primitive of the fill per argument.  fn:                     in per item   out per item */
+#define EMME_FN_RCP 0         /* frcp: hardware seed + two Newton steps     x             1/x            */
+#define EMME_FN_RSQRT 1       /* frsqrt                                     x             1/sqrt(x)      */
+#define EMME_FN_EXP 2         /* fexp, literal coefficients                 x             exp(x)         */
+#define EMME_FN_EXP_S 3       /* fexp, coefficients in scalar registers     x             exp(x)         */
+#define EMME_FN_EXP_V 4       /* fexp, coefficients in vector registers     x             exp(x)         */
+#define EMME_FN_SINCOS 5      /* fsincos, three-term reduction              x             sin x, cos x   */
+#define EMME_FN_SINCOS_S 6    /* fsincos, two-term, scalar registers        x             sin x, cos x   */
+#define EMME_FN_SINCOS_V 7    /* fsincos, two-term, vector registers        x             sin x, cos x   */
+#define EMME_FN_CRCP 8        /* complex rcp                                re, im        re, im of 1/z  */
+int emme_elementary_batch(int fn, const double* x, int n, double* out);
+/* The pointwise integrand F_m(tan x) / cos^2 x of the mapped integral (reference src/Parameters.cpp:120-176), per item
+ * k < n: grid pair i[k] < j[k], moment m[k] (0, or 0..2 when beta_e != 0), abscissa x[k] in (0, pi/2) and
+ * omega[2k], omega[2k+1]; the contour sense is that of the item's omega.  The pair constants are built by the code the
+ * fill kernels use.  EMME_EINVAL also for a parameter set whose arc_coeff, vt, tau, q, R or omega_s_i is zero or not
+ * finite (the kernels divide by them).  form:                                                               doubles out per item */
+#define EMME_FORM_F 0         /* integrand(): F                                                    2  */
+#define EMME_FORM_F_DF 1      /* integrand_d(): F, dF/domega                                       4  */
+#define EMME_FORM_SPLIT 2     /* node_data(): A0, T, Q1, Q0, then node_eval of them at omega: F   10  */
+#define EMME_FORM_W 3         /* node_w(): W, the moment factor (F_m = F_0 (c_nv W)^m)             2  */
+int emme_integrand_batch(const emme_params_t* p, int form, int n, const int* i, const int* j, const int* m,
+                         const double* x, const double* omega, double* out);
+
 /* nullSpace (reference include/solver.h:58-112): the right singular vector of the smallest
  * singular value of the n x n complex matrix M (row-major), by inverse iteration on M^H M.
  * Same vector as the reference's SVD result up to the arbitrary complex phase. Host pointers. */

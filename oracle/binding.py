@@ -148,6 +148,8 @@ class Oracle:
         lib.oracle_kappa.argtypes = [PP, C.c_uint, _D, _D, _D, _D, _I, _P]
         lib.oracle_kappa.restype = _L
         lib.oracle_kappa_e.argtypes = [PP, C.c_uint, _D, _D, _D, _D, _P]
+        lib.oracle_kappa_integrand.argtypes = [PP, C.c_uint, _D, _D, _D, _D, _D, _P, _P]
+        lib.oracle_kappa_integrand.restype = None
         lib.oracle_integrate_test.argtypes = [_D, _D, _D, _D, _D, C.c_ulong, C.c_ulong, _P]
         lib.oracle_integrate_test.restype = _L
         lib.oracle_assemble.argtypes = [PP, _D, _D, _P, _I, _I, _P, _P]
@@ -183,6 +185,14 @@ class Oracle:
         n = self.lib.oracle_kappa(C.byref(p), m, eta, eta_p, omega.real, omega.imag, recompute,
                                   o.ctypes.data)
         return complex(o[0], o[1]), n
+
+    def kappa_integrand(self, p, m, eta, eta_p, omega: complex, x, want_clamp_arg=False):
+        """the integrand of kappa at abscissa x of the mapped integral, F_m(tan x) / cos^2 x (and, on request, the
+        real part of safe_exp's argument: the value is exactly 0 where that is below -40)"""
+        o = np.zeros(3)
+        self.lib.oracle_kappa_integrand(C.byref(p), m, eta, eta_p, omega.real, omega.imag, x, o.ctypes.data,
+                                        o.ctypes.data + 16)
+        return (complex(o[0], o[1]), o[2]) if want_clamp_arg else complex(o[0], o[1])
 
     def kappa_e(self, p, m, eta, eta_p, omega: complex):
         o = np.zeros(2)

@@ -353,6 +353,7 @@ typedef struct {
     int recompute;
     /* per-pair hoist (identical values, see oracle_kappa) */
     double beta1, bi, bip;
+    double* clamp_arg; /* optional: receives Re of safe_exp's argument (oracle_kappa_integrand) */
 } kctx_t;
 
 static double beta_1(const emme_params_t* p, double eta, double eta_p) {
@@ -411,6 +412,7 @@ static cplx kappa_integrand(double t, void* vctx) {
     const cplx log_coef = log_norm_vel + log_i_beta + log_hf_tau + log_exp_term;
 
     const cplx ev = log_coef - bs.zexp;
+    if (k->clamp_arg) *k->clamp_arg = creal(ev);
     const cplx sexp = creal(ev) < -40. ? (cplx)0.0 : cexp(ev);
 
     cplx r = c_div(c_pow_real(nv, (double)k->m), taut);
@@ -422,7 +424,7 @@ static cplx kappa_integrand(double t, void* vctx) {
 
 long oracle_kappa(const emme_params_t* p, unsigned m, double eta, double eta_p, double wre,
                   double wim, int recompute, double* out2) {
-    kctx_t k = {p, m, eta, eta_p, c_mk(wre, wim), recompute, 0, 0, 0};
+    kctx_t k = {p, m, eta, eta_p, c_mk(wre, wim), recompute, 0, 0, 0, 0};
     if (!recompute) {
         k.beta1 = beta_1(p, eta, eta_p);
         k.bi = oracle_bi(p, eta);
@@ -442,6 +444,17 @@ long oracle_kappa(const emme_params_t* p, unsigned m, double eta, double eta_p, 
     cplx kappa = c_mul(pref, res);
     out2[0] = creal(kappa), out2[1] = cimag(kappa);
     return n;
+}
+
+/* the integrand of oracle_kappa at one abscissa of the mapped integral: F_m(tan x) / cos^2 x */
+void oracle_kappa_integrand(const emme_params_t* p, unsigned m, double eta, double eta_p, double wre,
+                            double wim, double x, double* out2, double* clamp_arg) {
+    kctx_t k = {p, m, eta, eta_p, c_mk(wre, wim), 0, 0, 0, 0, clamp_arg};
+    k.beta1 = beta_1(p, eta, eta_p);
+    k.bi = oracle_bi(p, eta);
+    k.bip = oracle_bi(p, eta_p);
+    const cplx f = mapped(kappa_integrand, &k, x);
+    out2[0] = creal(f), out2[1] = cimag(f);
 }
 
 static cplx kappa_e(const emme_params_t* p, unsigned m, double eta, double eta_p, cplx omega,

@@ -42,6 +42,12 @@ void oracle_bessel(double zre, double zim, double* out8);
 long oracle_kappa(const emme_params_t* p, unsigned m, double eta, double eta_p, double wre,
                   double wim, int recompute, double* out2);
 
+/* The integrand of oracle_kappa alone, at one abscissa x in (0, pi/2) of the mapped integral
+ * (include/functions.h:313-316): out2 = F_m(tan x) / cos^2 x.  clamp_arg (optional) receives the real
+ * part of safe_exp's argument (src/Parameters.cpp:167-173): below -40 the value is exactly 0. */
+void oracle_kappa_integrand(const emme_params_t* p, unsigned m, double eta, double eta_p, double wre,
+                            double wim, double x, double* out2, double* clamp_arg);
+
 /* src/Parameters.cpp:186-209 */
 int oracle_kappa_e(const emme_params_t* p, unsigned m, double eta, double eta_p, double wre,
                    double wim, double* out2);
