@@ -191,13 +191,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
     if (!LIST) bind_batch();
 
     auto store = [&](int r, int c, cd v) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        if (Moldb) {
-            const double2 o = Moldb[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            Mpb[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)r * dim + c, v);
     };
 
     // diagonal (include/solver.h:442-443, 465-470): block 0 of each batch item
@@ -272,18 +266,8 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
         ++my_intervals;
         ++item_intervals;
 
-        // include/functions.h:203-208, 231-233
-        const double dKx = Kx - Gx, dKy = Ky - Gy;
-        const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
-        double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
         const cd integral = mk(Kx * scale, Ky * scale);
-        err *= scale;
-        const double rel_abs = P.rel_tol * (absK * scale);  // |rel * integral|
-        if (abs_tol == 0.0) abs_tol = rel_abs;              // :237-239
-        // :240-242.  ldexp(scale, max_sub) > 0.99 (b - a) with scale = (b-a) 2^-(depth+1)
-        // (up to rounding far below the 1 % margin) is exactly depth < max_sub.
-        bool split = depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal &&
-                     err > rel_abs + P.prec_goal;
+        bool split = gk_split(mk(Kx, Ky), mk(Gx, Gy), scale, inv_scale, depth, P, abs_tol);
         if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {  // flag and accept
             split = false;
             bad = 1;
@@ -381,9 +365,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_deriv(AsmA
     oc.omi = -copysign(1.0, oc.omega.x);
     // an entry of M and the same entry of M'
     auto store = [&](int r, int c, cd v, cd vd) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        Mdb[idx] = make_double2(vd.x, vd.y);
+        store_entry_twin(Mb, Mdb, (size_t)r * dim + c, v, vd);
     };
     const cd zero = mk(0.0, 0.0);
 
@@ -449,16 +431,9 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_deriv(AsmA
         ++my_intervals;
         ++item_intervals;
 
-        // include/functions.h:203-208, 231-247 -- the plain kernel's rule, on K and G alone
-        const double dKx = Kx - Gx, dKy = Ky - Gy;
-        const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
-        double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+        // the plain kernel's rule, on K and G alone
         const cd integral = mk(Kx * scale, Ky * scale);
-        err *= scale;
-        const double rel_abs = P.rel_tol * (absK * scale);
-        if (abs_tol == 0.0) abs_tol = rel_abs;
-        bool split = depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal &&
-                     err > rel_abs + P.prec_goal;
+        bool split = gk_split(mk(Kx, Ky), mk(Gx, Gy), scale, inv_scale, depth, P, abs_tol);
         if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {
             split = false;
             bad = 1;
@@ -602,7 +577,7 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
         const PairConst pc = make_pair_const(P, eta[i], eta[j], btab[i], btab[j], dg);
         const ClassTables ct = class_tables(A, oc.omi > 0.0 ? 0 : 1);
 
-        // one interval: GK estimate, error, accept/split (include/functions.h:203-208, 231-247)
+        // one interval: GK estimate, then the accept / split verdict
         double abs_tol = 0.0;
         auto evaluate = [&](double l, double r, int depth, unsigned long long path, cd& integral,
                             double& mid) -> bool {
@@ -612,15 +587,8 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
             const cd f = node_value<GW>(A, ct, depth, path, (long)it, lane_in_group, x, pc, oc, m, TC);
             const double Kx = group_sum<GW>(gk.wk * f.x), Ky = group_sum<GW>(gk.wk * f.y);
             const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
-            const double dKx = Kx - Gx, dKy = Ky - Gy;
-            const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
-            double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
             integral = mk(Kx * scale, Ky * scale);
-            err *= scale;
-            const double rel_abs = P.rel_tol * (absK * scale);
-            if (abs_tol == 0.0) abs_tol = rel_abs;
-            return depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal &&
-                   err > rel_abs + P.prec_goal;
+            return gk_split(mk(Kx, Ky), mk(Gx, Gy), scale, inv_scale, depth, P, abs_tol);
         };
 
         // root: every group evaluates it (identical bits) so that all hold abs_tol
@@ -694,13 +662,7 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
             double2* Mpb = A.Mp ? A.Mp + (size_t)b * dim * dim : nullptr;
             const cd rdw = Moldb ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
             auto store = [&](int rr, int cc, cd v) {
-                const size_t idx = (size_t)rr * dim + cc;
-                Mb[idx] = make_double2(v.x, v.y);
-                if (Moldb) {
-                    const double2 o = Moldb[idx];
-                    const cd d = (v - mk(o.x, o.y)) * rdw;
-                    Mpb[idx] = make_double2(d.x, d.y);
-                }
+                store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)rr * dim + cc, v);
             };
             if (m == 0) {  // include/solver.h:448-453
                 const double w = pair_weight(i, j, N);

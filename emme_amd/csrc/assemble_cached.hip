@@ -247,13 +247,7 @@ __global__ __launch_bounds__(256, EMME_CACHED_MIN_WAVES) void k_assemble_cached(
     const double2* Moldb = A.Mold ? A.Mold + (size_t)b * dim * dim : nullptr;
     double2* Mpb = A.Mp ? A.Mp + (size_t)b * dim * dim : nullptr;
     auto store = [&](int r, int c, cd v) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        if (Moldb) {
-            const double2 o = Moldb[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            Mpb[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)r * dim + c, v);
     };
     if (blockIdx.x == 0 && has_w && sub == 0) {  // diagonal (include/solver.h:442-443, 465-470)
         for (int i = group_in_block; i < N; i += GROUPS_PER_BLOCK) {
@@ -371,7 +365,7 @@ __global__ __launch_bounds__(256, EMME_CACHED_MIN_WAVES) void k_assemble_cached(
                 if (s + 2 < PTS) proc(r2, t2, s + 2);
             }
             ++item_intervals;
-            // include/functions.h:203-208, 231-247
+            // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
             const double dKx = K.x - G.x, dKy = K.y - G.y;
             const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
             double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
@@ -489,13 +483,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_cached_em(AsmCachedArgs A) 
 #ifdef EMME_EM_NO_STORE  // timing experiment only (results are garbage): what the scattered 16-byte stores cost
         if (v.x != 1.2345e300) return;
 #endif
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        if (Moldb) {
-            const double2 o = Moldb[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            Mpb[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)r * dim + c, v);
     };
     if (blockIdx.x == 0 && has_w && sub == 0) {  // diagonal (include/solver.h:465-470)
         for (int i = group_in_block; i < N; i += GROUPS_PER_BLOCK) {
@@ -623,20 +611,13 @@ __global__ __launch_bounds__(256, 2) void k_assemble_cached_em(AsmCachedArgs A) 
                 if (s + 4 < PTS) r1 = rp[node_of(s + 4)], t1 = tp[node_of(s + 4) * tstride], w1 = wp[node_of(s + 4)];
                 if (s + 2 < PTS) proc(r2, t2, w2, s + 2);
             }
-            // per moment: include/functions.h:203-208, 231-247
+            // per moment
 #pragma unroll
             for (int m = 0; m < 3; ++m) {
                 if (key[m] != cur) continue;
                 ++count[m];
-                const double dKx = K[m].x - G[m].x, dKy = K[m].y - G[m].y;
-                const double absK = sqrt(fma(K[m].x, K[m].x, K[m].y * K[m].y));
-                double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
                 const cd integral = mk(K[m].x * scale, K[m].y * scale);
-                err *= scale;
-                const double rel_abs = P.rel_tol * (absK * scale);
-                if (abs_tol[m] == 0.0) abs_tol[m] = rel_abs;
-                bool split = depth < P.max_sub && err > abs_tol[m] * inv_scale + P.prec_goal &&
-                             err > rel_abs + P.prec_goal;
+                bool split = gk_split(K[m], G[m], scale, inv_scale, depth, P, abs_tol[m]);
                 if (split && (depth >= EMME_MAX_DEPTH || count[m] >= EMME_MAX_INTERVALS)) {
                     split = false;
                     bad = 1;
@@ -754,13 +735,7 @@ __global__ __launch_bounds__(256, 4) void k_assemble_union(AsmCachedArgs A) {
     const double2* Moldb = A.Mold ? A.Mold + (size_t)b * dim * dim : nullptr;
     double2* Mpb = A.Mp ? A.Mp + (size_t)b * dim * dim : nullptr;
     auto store = [&](int r, int c, cd v) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        if (Moldb) {
-            const double2 o = Moldb[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            Mpb[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)r * dim + c, v);
     };
     if (blockIdx.x == 0 && has_w)  // diagonal (include/solver.h:442-443)
         for (int i = group_in_block; i < N; i += GROUPS_PER_BLOCK) store(i, i, mk(P.diag_a, 0.0));
@@ -871,7 +846,7 @@ __global__ __launch_bounds__(256, 4) void k_assemble_union(AsmCachedArgs A) {
                     }
                 }
                 ++count;
-                // include/functions.h:203-208, 231-247
+                // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
                 const double scale = A.scale[cslot];  // (r - l)/2 of the interval: small table, L2-resident
                 const double dKx = K.x - G.x, dKy = K.y - G.y;
                 const double absK = sqrt(fma(K.x, K.x, K.y * K.y));

@@ -1,6 +1,8 @@
-// assemble_common.hpp -- pieces shared by the two fill kernels (assemble.hip: lanes = nodes,
-// one omega per lane group; assemble_wl.hip: lanes = omegas sharing the omega-independent
-// node data).
+// assemble_common.hpp -- the leaf pieces that the fill kernels share (assemble.hip, assemble_wl.hip,
+// assemble_cached.hip, assemble_dense.hip, assemble_dense_deriv.hip; probe.hip for the tables): the Gauss-Kronrod
+// tables, the caps, the accept / split rule of the adaptive quadrature, kappa_e, the pair weights, the three ways an
+// entry of M is stored and the small helpers of the dense fills.  The kernel BODIES stay separate texts (DESIGN.md
+// 12): what is here are forceinline leaves that perform the same operations in the same order at every call site.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +30,35 @@ constexpr int EMME_MAX_INTERVALS = 1 << 18;
 constexpr double EMME_MAX_ENTRY = 1e150;
 __device__ __forceinline__ bool kappa_bad(cd k) { return !(fabs(k.x) < EMME_MAX_ENTRY && fabs(k.y) < EMME_MAX_ENTRY); }
 
+// ---- the accept / split rule (include/functions.h:203-208, 231-247) ------------------------------------------
+// Square root of the error estimates: the exact one, or (the dense fills) the hardware reciprocal-square-root seed
+// + two Newton steps of frsqrt (<= 1 ulp for normal arguments), 0 for 0 and NaN for NaN.
+__device__ __forceinline__ double fsqrt_pos(double x) {
+    const double y = x * frsqrt(x);
+    return x > 0.0 ? y : x;
+}
+struct SqrtExact {
+    static __device__ __forceinline__ double of(double x) { return sqrt(x); }
+};
+struct SqrtSeeded {
+    static __device__ __forceinline__ double of(double x) { return fsqrt_pos(x); }
+};
+// Does the interval of half-width `scale` at bisection depth `depth`, with Kronrod sum K and Gauss sum G (both
+// before the factor scale), have to be split?  :203-208: err = max(|K - G|, 2 eps |K|) scale; :231-233:
+// |rel * integral|; :237-239: abs_tol is set by the first interval of the integral (the root) and is what the
+// caller keeps per integral; :240-242: ldexp(scale, max_sub) > 0.99 (b - a) with scale = (b - a) 2^-(depth+1)
+// (up to rounding far below the 1 % margin) is exactly depth < max_sub.  inv_scale = 2 / (b - a).
+template <class Sqrt = SqrtExact>
+__device__ __forceinline__ bool gk_split(cd K, cd G, double scale, double inv_scale, int depth, const DevParams& P,
+                                         double& abs_tol) {
+    const double dKx = K.x - G.x, dKy = K.y - G.y;
+    const double absK = Sqrt::of(fma(K.x, K.x, K.y * K.y));
+    double err = fmax(Sqrt::of(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+    err *= scale;
+    const double rel_abs = P.rel_tol * (absK * scale);
+    if (abs_tol == 0.0) abs_tol = rel_abs;
+    return depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal && err > rel_abs + P.prec_goal;
+}
 // per-lane node tables: lane r of a group -> (signed abscissa, Kronrod weight, Gauss weight)
 __device__ const double kX15[8] = {0.,
                                    0.20778495500789847,
@@ -159,6 +190,45 @@ __device__ __forceinline__ double pair_weight(int i, int j, int N) {
                       : 1.0;
     if (j == N - 1) w -= 0.5;
     return w;
+}
+
+// ---- entries of M ----------------------------------------------------------------------------------------------
+// One entry idx = row * dim + col of a matrix at `Mb`: with the fused secant quotient Mp = (M - Mold) / domega
+// (include/solver.h:54-57; rdw = 1 / domega, Moldb null = none), or M and the same entry of M'.
+__device__ __forceinline__ void store_entry_secant(double2* Mb, const double2* Moldb, double2* Mpb, cd rdw, size_t idx,
+                                                   cd v) {
+    Mb[idx] = make_double2(v.x, v.y);
+    if (Moldb) {
+        const double2 o = Moldb[idx];
+        const cd d = (v - mk(o.x, o.y)) * rdw;
+        Mpb[idx] = make_double2(d.x, d.y);
+    }
+}
+__device__ __forceinline__ void store_entry_twin(double2* Mb, double2* Mdb, size_t idx, cd v, cd vd) {
+    Mb[idx] = make_double2(v.x, v.y);
+    Mdb[idx] = make_double2(vd.x, vd.y);
+}
+
+// A_ij = -kappa_all(0) W_ij dx (include/solver.h:448-453): the factor of kappa
+__device__ __forceinline__ double pair_entry_weight(int i, int j, int N, double dx) {
+    return -(pair_weight(i, j, N) * dx);
+}
+
+// ---- small helpers of the dense fills ----------------------------------------------------------------------------
+// (wg / wk) of node slot sn of a tile block: the Gauss rule's weight relative to the Kronrod weight; 0 for
+// Kronrod-only nodes
+template <int PTS>
+__device__ __forceinline__ double gauss_ratio(int sn) {
+    if (sn >= (PTS - 1) / 2) return 0.0;          // (7 / 15 Gauss nodes, slots 0 ..)
+    const int q = sn == 0 ? 0 : ((sn + 1) & ~1);  // slots (1,2) (3,4) (5,6) .. are nodes +-x2, +-x4, +-x6 ..
+    return PTS == 15 ? kWg15[q >> 1] / kWk15[q] : kWg31[q >> 1] / kWk31[q];
+}
+// the pointer lane k holds (k wave-uniform): two v_readlane, not a bpermute through LDS
+__device__ __forceinline__ const double* lane_ptr(const double* p, int k) {
+    const unsigned long long bits = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
+    return reinterpret_cast<const double*>(((unsigned long long)hi << 32) | lo);
 }
 
 __device__ __forceinline__ PairConst make_pair_const(const DevParams& P, double eta_i, double eta_j,

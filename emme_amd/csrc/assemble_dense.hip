@@ -209,14 +209,6 @@ __global__ __launch_bounds__(256) void k_btab(BtabArgs A) {
     }
 }
 
-// (wg / wk) of node slot sn: the Gauss rule's weight relative to the Kronrod weight; 0 for Kronrod-only nodes
-template <int PTS>
-__device__ __forceinline__ double gauss_ratio(int sn) {
-    if (sn >= (PTS - 1) / 2) return 0.0;          // (7 / 15 Gauss nodes, slots 0 ..)
-    const int q = sn == 0 ? 0 : ((sn + 1) & ~1);  // slots (1,2) (3,4) (5,6) .. are nodes +-x2, +-x4, +-x6 ..
-    return PTS == 15 ? kWg15[q >> 1] / kWk15[q] : kWg31[q >> 1] / kWk31[q];
-}
-
 struct DenseArgs {
     DevParams P;
     const double* tab;  // eta | g | b (electromagnetic fills: c_nv, kappa_e and the D diagonal)
@@ -263,13 +255,6 @@ struct DenseArgs {
 // An element whose split does not fit the next list (more than 64 intervals of one level in a tile: in
 // the bench, one strongly damped omega per search whose trees also leave the cached depth)
 // is handed, whole, to the cooperative kernel.
-__device__ __forceinline__ double fsqrt_pos(double x) {
-    // sqrt for the error estimates: hardware reciprocal-square-root seed + two Newton steps (<= 1 ulp
-    // for normal arguments), 0 for 0 and NaN for NaN
-    const double y = x * frsqrt(x);
-    return x > 0.0 ? y : x;
-}
-
 #ifndef EMME_DENSE_MIN_WAVES
 #define EMME_DENSE_MIN_WAVES 2
 #endif
@@ -342,12 +327,7 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
         if (r > c) return;
 #endif
         const size_t idx = (size_t)b * dim * dim + (size_t)r * dim + c;
-        A.M[idx] = make_double2(v.x, v.y);
-        if (A.Mold) {
-            const double2 o = A.Mold[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            A.Mp[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(A.M, A.Mold, A.Mp, rdw, idx, v);
     };
     if (tile == 0 && has_w && mom == 0) {  // diagonal (include/solver.h:442-443; electromagnetic: 465-470)
         const cd rdw0 = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
@@ -403,12 +383,6 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
     // block number of the subtree's first interval for this wave's tile in its buffer
     const unsigned long long g_blk0 =
         gk == 0 ? g_blk_main + (unsigned long long)g_base : (unsigned long long)tile * (unsigned long long)((2 << (g_dd - g_rd)) - 1);
-    auto lane_ptr = [&](const double* p, int k) -> const double* {
-        const unsigned long long bits = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
-        return reinterpret_cast<const double*>(((unsigned long long)hi << 32) | lo);
-    };
     // ---- the wave's 256 integrals: element r of this lane = (pair tile*16 + rho + 4 r, omega col) -----
     unsigned long long mcur[4][LW], mnext[4][LW];  // entries of the current / next level this element needs
     // per-element accumulators live in LDS (touched only by their owner lane, only when the element owns
@@ -560,11 +534,12 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 }
                 Kre += K2re, Kim += K2im, Gre += G2re, Gim += G2im;
             }
-            // ---- every element that owns the interval decides for itself (include/functions.h:203-208,
-            // 231-247); an entry somebody splits puts its two children on the next level's list
+            // ---- every element that owns the interval decides for itself; an entry somebody splits puts its two
+            // children on the next level's list
             const double scale = A.scale[cslot];
             bool split[4] = {false, false, false, false};
             // one decision: sums (kx, ky) / (gx, gy) of the element whose accumulators are slot [r][owner]
+            // (gk_split<SqrtSeeded>, assemble_common.hpp, spelled out: the call renames registers in the NM = 1 builds)
             auto decide = [&](int r, int owner, double kx, double ky, double gx, double gy, int& flag_bad) -> bool {
                 const int cnt = s_count[wave][r][owner] + 1;
                 s_count[wave][r][owner] = cnt;

@@ -16,8 +16,8 @@
 // would overflow) go, whole, to k_assemble_deriv_list below, which evaluates M and M' of them from scratch.
 //
 // This is separate kernel text, not a template flag on k_assemble_dense: a shared body changed the register
-// allocation of the plain kernels.  assemble_dense.hip is not touched; the few small helpers both
-// need (gauss_ratio, fsqrt_pos) are repeated here.
+// allocation of the plain kernels.  The small helpers both need (gauss_ratio, fsqrt_pos, lane_ptr) and
+// the accept / split rule live in assemble_common.hpp.
 #include <hip/hip_runtime.h>
 
 #include "assemble_common.hpp"
@@ -79,18 +79,6 @@ __global__ __launch_bounds__(256) void k_btab_deriv(BtabDerivArgs A) {
         bk[sn * 16 + col] = make_double2(bv.x, bv.y);
         bk[sn * 16 + col + DERIV_CHUNK] = make_double2(dv.x, dv.y);
     }
-}
-
-// (wg / wk) of node slot sn of the GK15 tile block (assemble_dense.hip: gauss_ratio<15>)
-__device__ __forceinline__ double gauss_ratio15(int sn) {
-    if (sn >= 7) return 0.0;
-    const int q = sn == 0 ? 0 : ((sn + 1) & ~1);
-    return kWg15[q >> 1] / kWk15[q];
-}
-
-__device__ __forceinline__ double fsqrt_pos_d(double x) {
-    const double y = x * frsqrt(x);
-    return x > 0.0 ? y : x;
 }
 
 struct DenseDerivArgs {
@@ -162,8 +150,8 @@ __global__ __launch_bounds__(256, 2) void k_assemble_dense_deriv(DenseDerivArgs 
     const double inv_scale = 2. / (M_PI / 2.0);
     double grat[GKS];
 #pragma unroll
-    for (int ks = 0; ks < GKS; ++ks) grat[ks] = gauss_ratio15((4 * ks + (lane >> 4)) >> 1);
-    const double grat_node = gauss_ratio15(col);
+    for (int ks = 0; ks < GKS; ++ks) grat[ks] = gauss_ratio<15>((4 * ks + (lane >> 4)) >> 1);
+    const double grat_node = gauss_ratio<15>(col);
     const int loff = tile_index(lane >> 4, lane & 15);
     const int eoff = (lane >> 5) * 16 + (lane & 15);
     const double2 omw = A.omega[b];  // this lane's column omega (K' lanes: their partner's)
@@ -177,12 +165,6 @@ __global__ __launch_bounds__(256, 2) void k_assemble_dense_deriv(DenseDerivArgs 
     const unsigned long long g_blk_main = (unsigned long long)tile * (unsigned long long)A.geom.ni_main();
     const unsigned long long g_blk0 =
         gk == 0 ? g_blk_main + (unsigned long long)g_base : (unsigned long long)tile * (unsigned long long)((2 << (g_dd - g_rd)) - 1);
-    auto lane_ptr = [&](const double* p, int k) -> const double* {
-        const unsigned long long bits = reinterpret_cast<unsigned long long>(p);
-        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
-        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
-        return reinterpret_cast<const double*>(((unsigned long long)hi << 32) | lo);
-    };
     // ---- the wave's 128 integrals and their twins: element r of this lane = (pair tile*16 + rho + 4 r, column col)
     unsigned long long mcur[4], mnext[4];
     // per-element state in LDS, touched by the owner lane (dense rounds) or the column's decider lane (vector rounds):
@@ -312,17 +294,8 @@ __global__ __launch_bounds__(256, 2) void k_assemble_dense_deriv(DenseDerivArgs 
             auto decide = [&](int r, int owner, double kx, double ky, double gx, double gy, int& flag_bad) -> bool {
                 const int cnt = s_count[wave][r][owner] + 1;
                 s_count[wave][r][owner] = cnt;
-                const double dKx = kx - gx, dKy = ky - gy;
-                const double absK = fsqrt_pos_d(fma(kx, kx, ky * ky));
-                double err = fmax(fsqrt_pos_d(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
-                err *= scale;
-                const double rel_abs = P.rel_tol * (absK * scale);
-                double at = s_abstol[wave][r][owner];
-                if (at == 0.0) {
-                    at = rel_abs;
-                    s_abstol[wave][r][owner] = at;
-                }
-                bool sp = depth < P.max_sub && err > at * inv_scale + P.prec_goal && err > rel_abs + P.prec_goal;
+                bool sp = gk_split<SqrtSeeded>(mk(kx, ky), mk(gx, gy), scale, inv_scale, depth, P,
+                                               s_abstol[wave][r][owner]);
                 if (sp && (depth >= EMME_MAX_DEPTH || cnt >= EMME_MAX_INTERVALS)) {
                     sp = false;
                     flag_bad = 1;
@@ -462,7 +435,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_dense_deriv(DenseDerivArgs 
             const cd sm = mk(s_sumx[wave][r][lane], s_sumy[wave][r][lane]);
             const cd kap = mk(P.pref * sm.y, -(P.pref * sm.x));
             if (kappa_bad(kap)) bad = 1;
-            const cd v = (-(pair_weight(i, j, N) * P.dx)) * kap;
+            const cd v = pair_entry_weight(i, j, N, P.dx) * kap;
             out[(size_t)i * dim + j] = make_double2(v.x, v.y);
             out[(size_t)j * dim + i] = make_double2(v.x, v.y);
         }
@@ -493,7 +466,7 @@ __global__ __launch_bounds__(256, 2) void k_assemble_dense_deriv(DenseDerivArgs 
 // ---- the integrals that left the cache ----------------------------------------------------------------------------
 // The LIST form of k_assemble_deriv (assemble.hip), as k_assemble<PTS, true> is the LIST form of k_assemble: a lane
 // group per work-list entry (batch << 32 | pair), from scratch (integrand_d per lane), M and M' of the integral.
-// The accept / split rule and the scatter are k_assemble_deriv's: a change there belongs here too.
+// The scatter is k_assemble_deriv's m = 0 branch: a change there belongs here too.
 struct DerivListArgs {
     DevParams P;
     const double* tab;
@@ -555,6 +528,7 @@ __global__ __launch_bounds__(256, 3) void k_assemble_deriv_list(DerivListArgs A)
             const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
             const double Kdx = group_sum<GW>(gk.wk * fd.x), Kdy = group_sum<GW>(gk.wk * fd.y);
             ++item_intervals;
+            // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
             const double dKx = Kx - Gx, dKy = Ky - Gy;
             const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
             double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
@@ -590,7 +564,7 @@ __global__ __launch_bounds__(256, 3) void k_assemble_deriv_list(DerivListArgs A)
         const cd kd = mk(P.pref * sum_d.y, -(P.pref * sum_d.x));
         if (kappa_bad(kap) || kappa_bad(kd)) bad = 1;
         if (lane_in_group == 0) {
-            const double w = -(pair_weight(i, j, N) * P.dx);
+            const double w = pair_entry_weight(i, j, N, P.dx);
             const cd v = w * kap, vd = w * kd;
             double2* Mb = A.M + (size_t)b * dim * dim;
             double2* Mdb = A.Md + (size_t)b * dim * dim;

@@ -91,13 +91,7 @@ __global__ __launch_bounds__(256, EMME_WL_MIN_WAVES) void k_assemble_wl(AsmWlArg
     double2* Mpb = A.Mp ? A.Mp + (size_t)b * dim * dim : nullptr;
 
     auto store = [&](int r, int c, cd v) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        if (Moldb) {
-            const double2 o = Moldb[idx];
-            const cd d = (v - mk(o.x, o.y)) * rdw;
-            Mpb[idx] = make_double2(d.x, d.y);
-        }
+        store_entry_secant(Mb, Moldb, Mpb, rdw, (size_t)r * dim + c, v);
     };
 
     // diagonal (include/solver.h:442-443, 465-470): first block of every omega chunk
@@ -214,16 +208,8 @@ __global__ __launch_bounds__(256, EMME_WL_MIN_WAVES) void k_assemble_wl(AsmWlArg
                 }
                 ++my_intervals;
                 ++item_intervals;
-                // include/functions.h:203-208, 231-247
-                const double dKx = K.x - G.x, dKy = K.y - G.y;
-                const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
-                double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
                 const cd integral = mk(K.x * scale, K.y * scale);
-                err *= scale;
-                const double rel_abs = P.rel_tol * (absK * scale);
-                if (abs_tol == 0.0) abs_tol = rel_abs;
-                my_split = depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal &&
-                           err > rel_abs + P.prec_goal;
+                my_split = gk_split(K, G, scale, inv_scale, depth, P, abs_tol);
                 if (my_split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {
                     my_split = false;
                     bad = 1;
@@ -339,9 +325,7 @@ __global__ __launch_bounds__(256, EMME_WL_MIN_WAVES) void k_assemble_wl_deriv(As
     double2* Mdb = Md + (size_t)b * dim * dim;
     // an entry of M and the same entry of M'
     auto store = [&](int r, int c, cd v, cd vd) {
-        const size_t idx = (size_t)r * dim + c;
-        Mb[idx] = make_double2(v.x, v.y);
-        Mdb[idx] = make_double2(vd.x, vd.y);
+        store_entry_twin(Mb, Mdb, (size_t)r * dim + c, v, vd);
     };
     const cd zero = mk(0.0, 0.0);
 
@@ -466,7 +450,7 @@ __global__ __launch_bounds__(256, EMME_WL_MIN_WAVES) void k_assemble_wl_deriv(As
                 }
                 ++my_intervals;
                 ++item_intervals;
-                // include/functions.h:203-208, 231-247
+                // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
                 const double dKx = K.x - G.x, dKy = K.y - G.y;
                 const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
                 double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
