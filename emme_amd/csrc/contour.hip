@@ -363,7 +363,7 @@ int emme_contour_moments_batch(emme_ctx_t* c, int n, int nq, const double* M, co
         return EMME_ECONFIG;
     }
     HIP_TRY(hipSetDevice(c->device));
-    int rc = ctx_ensure_batch(c, nq);
+    int rc = ensure_batch(c, nq);
     if (rc) return rc;
     ContourState S;
     S.c = c, S.n = n;
@@ -373,7 +373,7 @@ int emme_contour_moments_batch(emme_ctx_t* c, int n, int nq, const double* M, co
         HIP_TRY(S.V.grow(sizeof(double) * 2 * (size_t)n * L));
         S.ldv = L;
         HIP_TRY(hipMemcpyAsync(S.V, V, sizeof(double) * 2 * (size_t)n * L,
-                               ptr_on_device(V) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+                               is_device_ptr(V) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     } else {
         rc = make_probes(S);
         if (rc) return rc;
@@ -383,7 +383,7 @@ int emme_contour_moments_batch(emme_ctx_t* c, int n, int nq, const double* M, co
     set.first = 0, set.count = nq;
     const size_t mbytes = sizeof(double) * 2 * (size_t)n * n * nq;
     HIP_TRY(set.A.grow(mbytes));
-    HIP_TRY(hipMemcpyAsync(set.A, M, mbytes, ptr_on_device(M) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(set.A, M, mbytes, is_device_ptr(M) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     rc = factor_set(S, set, "emme_contour_moments_batch");
     if (rc) return rc;
     rc = solve_set(S, set, 0, L);
@@ -449,7 +449,7 @@ int emme_find_roots_in_contour(emme_ctx_t* c, const emme_contour_t* ct, double t
     // fill, factor and solve a batch of new nodes
     auto add_nodes = [&](const std::vector<int>& ms) -> int {
         const int cnt = (int)ms.size();
-        int r = ctx_ensure_batch(c, cnt);
+        int r = ensure_batch(c, cnt);
         if (r) return r;
         std::vector<double> om(2 * (size_t)cnt);
         for (int k = 0; k < cnt; ++k) omega_at(ms[k], &om[2 * k]);

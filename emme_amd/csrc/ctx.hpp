@@ -1,6 +1,9 @@
 // ctx.hpp -- the context behind the C ABI (include/emme_hip.h) and the host-side helpers its translation
-// units share: emme_capi.hip (the ABI entry points and the Newton loop), ctx_cache.hip (buffer pool and the
-// HBM node cache's host side), ctx_fill.hip (the fill dispatcher; its host arithmetic is fill_plan.cpp).
+// units share: emme_capi.hip (context lifecycle, options, profile, the assembly entry points), ctx_linstep.hip (the
+// Newton linear step, the batched LU and the null-vector driver), ctx_search.hip (the two root searches),
+// ctx_cache.hip (buffer pool and the HBM node cache's host side), ctx_fill.hip (the fill dispatcher), probe.hip (the
+// probe entry points).  What needs no device is plain C++ under the sanitizer build (make host-sanitize): options.cpp,
+// fill_plan.cpp, linstep_plan.hpp, step_feedback.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -19,7 +22,8 @@
 #include "../../include/emme_hip.h"
 #include "buffers.hpp"
 #include "launch.hpp"
-
+#include "options.hpp"
+#include "step_feedback.hpp"
 
 namespace emme {
 
@@ -105,13 +109,11 @@ struct emme_ctx {
     PinnedBuffer<unsigned int> p_deferred;
     DeviceBuffer<unsigned int> d_overflow;  // per item: integrals that left the dense fill because a level list was full
     PinnedBuffer<unsigned int> p_overflow;  // ... published by k_retire
-    std::vector<unsigned char> h_wide;   // items whose chunks take the 128-entry build of the dense fill (root search)
-    bool pub_valid = false;        // last_deferred holds the previous fill's count (from p_deferred)
+    emme::StepFeedback fb;         // a root search's item costs and wide items; the previous fill's deferred count
     emme::StagingRing lists;       // per-launch index lists (omega order | chunks; LU items) on their way to the device
     bool ext_failed = false;
     DeviceBuffer<unsigned long long> d_defer_info;  // missing interval of every deferred integral
     double cache_bytes_used = 0.0;
-    unsigned int last_deferred = 0;            // integrals the previous cached fill deferred
     DeviceBuffer<double> d_scale;  // half-widths of the cached intervals
     DeviceBuffer<unsigned long long> d_worklist;  // integrals deferred to the cooperative kernel
     DeviceBuffer<unsigned int> d_worklist_count;
@@ -182,14 +184,36 @@ int fill(emme_ctx* c, const FillRequest& r);
 
 // ---- emme_capi.hip ----------------------------------------------------------------------------------------
 hipEvent_t get_event(emme_ctx* c);
-int ctx_ensure_batch(emme_ctx* c, int nb);  // batch scratch for nb items
+int require_device();                        // EMME_EDEVICE where there is no HIP device
+int check_npoints(const emme_params_t* p);  // EMME_EINVAL outside [2, 65535]
+// the kernels' scalars and tables (eta | g | b) of a parameter set
+void dev_params_from(const emme_params_t* p, DevParams& P, std::vector<double>& tab);
+bool is_device_ptr(const void* p);
+// *dev <- a and b are device pointers; EMME_EINVAL ("<names> must both be ...") if only one of them is
+int same_side(const void* a, const void* b, const char* names, bool* dev);
+// bytes of nbatch complex n x n matrices
+inline size_t batch_bytes(int n, int nbatch) { return (size_t)n * n * 2 * sizeof(double) * nbatch; }
+int ensure_batch(emme_ctx* c, int nb);            // batch scratch for nb items
+int ensure_mats(emme_ctx* c, int nb, int sets);  // matrix sets for nb items: bit0 M, bit1 Mold, bit2 Mp, bit3 work
 // around a fill: the batch's omegas into d_omega; interval counts and status flags zeroed; afterwards the counts
 // read back (into `intervals` if given, and the profile) -- synchronises; EMME_ENUMERIC if an item's flag is set
 // (*bad_item, if given: the first such item)
 int upload_omega(emme_ctx* c, const double* omega, int n, hipMemcpyKind kind = hipMemcpyHostToDevice);
 int reset_fill_counters(emme_ctx* c, int n);
 int collect_fill_status(emme_ctx* c, int n, long long* intervals, int* bad_item = nullptr);
-bool ptr_on_device(const void* p);
+// its two halves, for callers with read-backs of their own: queue the copies of d_intervals (and, st given, d_status)
+// into the caller's vectors; after the caller's synchronisation, add the counts to the profile (and to `intervals`)
+// and return the first flagged item, -1 if none
+int queue_fill_counters(emme_ctx* c, int n, std::vector<unsigned long long>& iv, std::vector<int>* st);
+int fold_fill_counters(emme_ctx* c, const std::vector<unsigned long long>& iv, const std::vector<int>* st,
+                       long long* intervals = nullptr);
+
+// ---- ctx_linstep.hip --------------------------------------------------------------------------------------
+int check_method(const emme_ctx* c, int method);
+// One Newton linear step on the batch: leaves tr[b] with domega = -1/tr[b] (h_active: host copy of `active`, null =
+// all live; work_ready: work holds M already)
+hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double* M, double* work, double* Mp,
+                       const int* active, double* tr, int* info, const int* h_active = nullptr, bool work_ready = false);
 // scratch of lu_factor_batch that the caller keeps until what it queued behind the factorisation has run
 struct LuScratch {
     DeviceBuffer<double> b;  // dummy right-hand sides of the chunked multi-workgroup factorisation

@@ -86,13 +86,13 @@ int stage_lists(emme_ctx* c, const std::vector<int>* chunks) {
 // intervals they were missing and cache a subtree around the most frequent one(s)
 int grow_cache_from_deferrals(emme_ctx* c, const AssembleLaunch& L) {
     if (!c->d_worklist_count || !c->d_defer_info) return EMME_OK;
-    if (!c->pub_valid) {  // (the Newton loop gets the count from k_retire through pinned memory)
-        HIP_TRY(hipMemcpyAsync(&c->last_deferred, c->d_worklist_count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
+    if (!c->fb.pub_valid) {  // (the Newton loop gets the count from k_retire through pinned memory)
+        HIP_TRY(hipMemcpyAsync(&c->fb.last_deferred, c->d_worklist_count, sizeof(unsigned int), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
-    c->pub_valid = false;
-    if (c->last_deferred < 32) return EMME_OK;
-    const size_t cnt = std::min<size_t>(c->last_deferred, 1u << 16);
+    c->fb.pub_valid = false;
+    if (c->fb.last_deferred < 32) return EMME_OK;
+    const size_t cnt = std::min<size_t>(c->fb.last_deferred, 1u << 16);
     std::vector<unsigned long long> info(cnt);
     HIP_TRY(hipMemcpy(info.data(), c->d_defer_info, cnt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     std::sort(info.begin(), info.end());
@@ -344,8 +344,8 @@ int fill(emme_ctx* c, const FillRequest& r) {
     // omegas whose level lists overflowed in their previous fill (root search only): first, a chunk each, through the
     // wide-list build of the dense fill
     // (a derivative request has no wide-list build)
-    const bool has_wide = r.newton_loop && !r.d_Md && c->tiled && c->nm == 1 && !c->h_wide.empty();
-    const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->h_wide.data() : nullptr, c->h_actidx);
+    const bool has_wide = r.newton_loop && !r.d_Md && c->tiled && c->nm == 1 && !c->fb.wide.empty();
+    const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->fb.wide.data() : nullptr, c->h_actidx);
     const int n_act = (int)c->h_actidx.size();
     if (n_act == 0) return EMME_OK;
     AssembleLaunch L = make_launch(c, r);

@@ -1,0 +1,257 @@
+// ctx_linstep.hip -- the Newton linear step and the batched LU above their kernels (linstep*.hip, nullspace.hip):
+// which kernel and how many workgroups a launch gets (linstep_plan.hpp), operands staged where the kernels can read
+// them, and the entry points emme_trace_solve_batch, emme_qr_secant_batch, emme_null_vectors_batch.
+#include "ctx.hpp"
+#include "linstep_plan.hpp"
+
+using namespace emme;
+
+namespace {
+
+// the Newton linear step: blocked kernel while its panel fits in LDS, else the unblocked one
+// `h_active`: host copy of `active` (null: all live).  With fewer live matrices than compute
+// units each gets several workgroups (lu_workgroups, linstep_plan.hpp).
+hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, const int* active,
+                       double* tr, int* info, const int* h_active) {
+    // n <= ~560: the whole L21 panel fits in LDS; up to 1024 the chunked build takes over, which
+    // needs helper workgroups (>= 2 per matrix, all resident); otherwise the unblocked kernel
+    const bool fits = trace_solve_blocked_lds(n) <= 150 * 1024;
+    if (c->opt.lu_unblocked == 0 && (fits || n <= 1024)) {
+        hipError_t e = c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, nbatch));
+        if (e != hipSuccess) return e;
+        // dense list of the live matrices (h_active: host copy of `active`, null = all live)
+        int n_live = nbatch;
+        int* lu_slot = nullptr;
+        if (h_active) {
+            e = c->d_lu_items.grow(sizeof(int) * nbatch);
+            if (e == hipSuccess) e = c->lists.take(nbatch, &lu_slot);
+            if (e != hipSuccess) return e;
+            n_live = 0;
+            for (int b = 0; b < nbatch; ++b)
+                if (h_active[b]) lu_slot[n_live++] = b;
+            if (n_live == 0) return hipSuccess;
+        }
+        const int nwg = lu_workgroups(n, n_live, c->n_cu, c->opt.lu_split, c->lu_one_wg, fits);
+        c->last_lu_nwg = nwg;
+        const int* d_items = nullptr;
+        if (nwg > 1 && h_active) {
+            e = launch_stage_ints(lu_slot, c->d_lu_items, n_live, nullptr, 0, c->stream);
+            if (e == hipSuccess) e = c->lists.read_on(c->stream);
+            if (e != hipSuccess) return e;
+            d_items = c->d_lu_items;
+        }
+        e = launch_trace_solve_blocked(n, nbatch, A, B, active, tr, info, nwg, d_items, n_live, c->d_lu_scratch, c->stream,
+                                       c->opt.lu_group_min_n, c->opt.lu_spin_limit);
+        if (e != hipErrorNotSupported) return e;
+        (void)hipGetLastError();  // chunked build not possible here (one workgroup per matrix, or no room)
+        c->last_lu_nwg = 1;
+    }
+    return launch_trace_solve(n, nbatch, A, B, active, tr, info, c->stream);
+}
+
+// The two operands of a linear step where the kernels can read them: A and B themselves if they are device
+// pointers, else copies that live as long as this object.  EMME_EINVAL if one is on the host and one on the device;
+// otherwise *e is the status of the allocations and copies, which each caller reports in its own words.
+struct DeviceOperands {
+    double *A = nullptr, *B = nullptr;  // (written only by a caller whose own operands are not const)
+    DeviceBuffer<double> st_a, st_b;
+    int stage(emme_ctx* c, const double* hA, const double* hB, size_t bytes, hipError_t* e) {
+        bool dev = false;
+        EMME_TRY(same_side(hA, hB, "A and B", &dev));
+        A = const_cast<double*>(hA), B = const_cast<double*>(hB), *e = hipSuccess;
+        if (dev) return EMME_OK;
+        if ((*e = st_a.grow(bytes)) == hipSuccess) *e = st_b.grow(bytes);
+        if (*e == hipSuccess) *e = hipMemcpyAsync(st_a, hA, bytes, hipMemcpyHostToDevice, c->stream);
+        if (*e == hipSuccess) *e = hipMemcpyAsync(st_b, hB, bytes, hipMemcpyHostToDevice, c->stream);
+        A = st_a, B = st_b;
+        return EMME_OK;
+    }
+};
+
+}  // namespace
+
+namespace emme {
+
+int check_method(const emme_ctx* c, int method) {
+    if (method != EMME_METHOD_TRACE_SECANT && method != EMME_METHOD_QR_SECANT) {
+        set_error("unknown iteration method");
+        return EMME_EINVAL;
+    }
+    if (method == EMME_METHOD_QR_SECANT && c->dim > 1024) {
+        set_error("QR-secant step: matrix dimension above 1024 is not supported");
+        return EMME_ECONFIG;
+    }
+    return EMME_OK;
+}
+
+// One Newton linear step on the batch: leaves tr[b] with domega = -1/tr[b].
+//   trace-secant (include/solver.h:113-160): work <- M, LU of [work | Mp], tr(M^-1 M')
+//   QR-secant    (include/solver.h:210-383): work <- M^T, pivoted QR of work, t_n / R_nn
+hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double* M, double* work,
+                       double* Mp, const int* active, double* tr, int* info, const int* h_active, bool work_ready) {
+    if (method == EMME_METHOD_QR_SECANT) {
+        hipError_t e = launch_transpose(n, nbatch, M, work, active, c->stream);
+        if (e != hipSuccess) return e;
+        return launch_qr_secant(n, nbatch, work, Mp, active, tr, info, c->stream);
+    }
+    if (!work_ready) {  // (the root search copies M -> work together with M -> Mold)
+        hipError_t e = hipMemcpyAsync(work, M, batch_bytes(n, nbatch), hipMemcpyDeviceToDevice, c->stream);
+        if (e != hipSuccess) return e;
+    }
+    return trace_solve(c, n, nbatch, work, Mp, active, tr, info, h_active);
+}
+
+// Partial-pivot LU of nbatch n x n matrices in place (P M = L U, rows never moved; n <= 2048), by the branch the
+// order allows: k_lu_inplace where the whole L21 panel fits one workgroup's LDS; above that, up to n = 1024, the chunked
+// multi-workgroup kernel of the Newton step (two workgroups per matrix, which must be resident together: slices of at
+// most half the compute units; its right-hand side is a dummy); beyond, k_lu_unblocked_inplace.  After each slice's
+// factorisation `after(b0, nb, maps, map_nb, lu_info)` queues what reads it: matrices b0 .. b0 + nb - 1, their row-order
+// snapshots (logical row x of slice item b is physical row maps[(b ceil(n / map_nb) + x / map_nb) n + x]) and their
+// info (0 or the column at which the factorisation stopped), both valid until the next slice is factored.  Used by
+// emme_null_vectors_batch and the contour solver (contour.hip); the launches are stream-ordered on c->stream.
+int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
+                    const std::function<hipError_t(int, int, const int*, int, const int*)>& after) {
+    const size_t mbytes = batch_bytes(n, 1);
+    const bool one_wg = trace_solve_blocked_lds(n) <= 150 * 1024;  // the whole L21 panel in one workgroup's LDS
+    if (one_wg || n <= 1024) {
+        const int slice_max = one_wg ? nbatch : std::max(1, c->n_cu / 2);
+        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, std::min(nbatch, slice_max))));
+        if (!one_wg) HIP_TRY(s.b.grow(mbytes * std::min(nbatch, slice_max)));
+        for (int b0 = 0; b0 < nbatch; b0 += slice_max) {
+            const int nb = std::min(slice_max, nbatch - b0);
+            double* a0 = work + (size_t)b0 * n * n * 2;
+            ScopedSpan sp(c, K_NULL);
+            if (one_wg) {
+                HIP_TRY(launch_lu_inplace(n, nb, a0, nullptr, nb, c->d_info, c->d_lu_scratch, c->stream));
+            } else {
+                HIP_TRY(hipMemsetAsync(s.b, 0, mbytes * nb, c->stream));
+                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, s.b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
+                                                                c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
+                if (e != hipSuccess) {
+                    (void)hipGetLastError();
+                    set_error(std::string(who) + ": the chunked factorisation could not be launched (its two workgroups per matrix must be resident together)");
+                    return EMME_EDEVICE;
+                }
+            }
+            HIP_TRY(after(b0, nb, trace_solve_rowmaps(c->d_lu_scratch, n, nb), trace_solve_nb(), c->d_info));
+        }
+    } else {
+        HIP_TRY(s.maps.grow(sizeof(int) * (size_t)n * nbatch));
+        ScopedSpan sp(c, K_NULL);
+        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, s.maps, c->d_info, c->stream));
+        HIP_TRY(after(0, nbatch, s.maps, n, c->d_info));
+    }
+    return EMME_OK;
+}
+
+}  // namespace emme
+
+extern "C" {
+
+int emme_trace_solve_batch(emme_ctx_t* c, int n, int nbatch, double* A, double* B, double* tr,
+                           int* info) {
+    if (!c || !A || !B || !tr || !info || n < 1 || nbatch < 1) return EMME_EINVAL;
+    if ((size_t)2 * n * sizeof(double2) > 64 * 1024) {
+        set_error("n too large for the LDS-staged pivot row");
+        return EMME_EINVAL;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    const size_t bytes = batch_bytes(n, nbatch);
+    DeviceOperands ops;
+    hipError_t staged = hipSuccess;
+    EMME_TRY(ops.stage(c, A, B, bytes, &staged));
+    HIP_TRY(staged);
+    {
+        ScopedSpan s(c, K_LIN);
+        HIP_TRY(trace_solve(c, n, nbatch, ops.A, ops.B, nullptr, c->d_tr, c->d_info, nullptr));
+    }
+    HIP_TRY(hipMemcpyAsync(tr, c->d_tr, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
+}
+
+int emme_qr_secant_batch(emme_ctx_t* c, int n, int nbatch, const double* A, const double* B,
+                         double* q, int* info) {
+    if (!c || !A || !B || !q || !info || n < 1 || nbatch < 1) return EMME_EINVAL;
+    if (n > 1024) {
+        set_error("QR-secant step: matrix dimension above 1024 is not supported");
+        return EMME_ECONFIG;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    const size_t bytes = batch_bytes(n, nbatch);
+    DeviceOperands ops;
+    DeviceBuffer<double> dW;  // transposed work copy
+    hipError_t e = hipSuccess;
+    EMME_TRY(ops.stage(c, A, B, bytes, &e));
+    if (e == hipErrorOutOfMemory || dW.grow(bytes) != hipSuccess) {
+        set_error("hipMalloc failed");
+        return EMME_ENOMEM;
+    }
+    {
+        ScopedSpan s(c, K_LIN);
+        if (e == hipSuccess) e = launch_transpose(n, nbatch, ops.A, dW, nullptr, c->stream);
+        if (e == hipSuccess) e = launch_qr_secant(n, nbatch, dW, ops.B, nullptr, c->d_tr, c->d_info, c->stream);
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(q, c->d_tr, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    if (e != hipSuccess) {
+        set_error(hipGetErrorString(e));
+        return EMME_EDEVICE;
+    }
+    return EMME_OK;
+}
+
+// nullSpace (reference include/solver.h:58-112), batched on the device: see nullspace.hip
+int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, double* vecs, int* info) {
+    if (!c || !vecs || !info || n < 1 || nbatch < 1) return EMME_EINVAL;
+    if (!M && (n != c->dim || nbatch > c->last_n || !c->d_M)) {
+        set_error("emme_null_vectors_batch: M = NULL needs a preceding emme_solve_roots call (n = emme_ctx_dim, nbatch <= its n)");
+        return EMME_EINVAL;
+    }
+    if (n > 2048) {
+        set_error("emme_null_vectors_batch: order above 2048 is not supported");
+        return EMME_ECONFIG;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    const size_t mbytes = batch_bytes(n, 1);
+    // device scratch of this call
+    DeviceBuffer<double> t_a, t_v;
+    DeviceBuffer<int> t_info;
+    // work copy the factorisation overwrites: the context's LU work set after a root search, else a buffer of its own
+    double* work = nullptr;
+    if (!M && c->d_work.bytes() >= mbytes * nbatch) {
+        work = c->d_work;
+        HIP_TRY(hipMemcpyAsync(work, c->d_M, mbytes * nbatch, hipMemcpyDeviceToDevice, c->stream));
+    } else {
+        HIP_TRY(t_a.grow(mbytes * nbatch));
+        work = t_a;
+        const double* src = M ? M : c->d_M;
+        HIP_TRY(hipMemcpyAsync(work, src, mbytes * nbatch, is_device_ptr(src) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    }
+    HIP_TRY(t_v.grow(sizeof(double) * 2 * (size_t)n * nbatch));
+    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
+    // two sweeps at a converged root; the rest is for matrices that are not singular (chains that never converged):
+    // a launch lasts as long as its slowest matrix, 0.18 ms per sweep at n = 256.  Measured on the 128 matrices of the
+    // headline search (worst 1 - overlap against the SVD where the SVD itself determines the vector): 60 sweeps
+    // 11.6 ms / 2.7e-14, 30 sweeps 6.7 ms / 8.9e-14, 20 sweeps 4.9 ms / 2.2e-9
+    const int max_sweeps = 30;
+    LuScratch scratch;
+    const int rc = lu_factor_batch(c, n, nbatch, work, scratch, "emme_null_vectors_batch",
+                              [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+                                  return launch_null_iterate(n, work + (size_t)b0 * n * n * 2, maps, map_nb, nullptr,
+                                                             nb, lu_info, t_v + (size_t)b0 * n * 2, t_info + b0,
+                                                             max_sweeps, c->stream);
+                              });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(vecs, t_v, sizeof(double) * 2 * (size_t)n * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
+}
+
+}  // extern "C"

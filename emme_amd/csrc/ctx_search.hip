@@ -1,0 +1,355 @@
+// ctx_search.hip -- the two root searches: what stands where the reference has EigenSolver's constructor and
+// newtonTraceSecantIteration (include/solver.h:396-415, 113-160) under the solve_once_eigen loop (src/main.cpp:19-80),
+// and the Newton search on the exact derivative.  Entry points: emme_solve_roots,
+// emme_solve_roots_newton, emme_newton_step_batch.
+#include "ctx.hpp"
+
+using namespace emme;
+
+namespace {
+
+// ---- the two root searches: what they share --------------------------------------------------------------------
+// One call's arguments and the host images its loop keeps.
+struct RootSearch {
+    const double* guesses;
+    int n;
+    double tol;
+    int step_limit;
+    bool want_iterates;
+    int method = 0;
+    std::vector<int> act, zeros;  // host image of d_active (every chain live at the start); n zeros
+    int stride() const { return step_limit + 1; }
+    // (d_iterates is sized by the last call that asked for iterates: a call that does not ask must not write it)
+    double* d_iterates(const emme_ctx* c) const { return want_iterates ? c->d_iterates.get() : nullptr; }
+};
+
+// buffers for n chains and the matrix sets of `mat_sets` (ensure_mats); the iterate record, if asked for, all NaN;
+// every chain live, no step taken, counters and flags clean
+int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
+    const int n = s.n;
+    EMME_TRY(ensure_batch(c, n));
+    EMME_TRY(ensure_mats(c, n, mat_sets));
+    if (s.want_iterates) {
+        const size_t need = (size_t)n * s.stride() * 2;
+        HIP_TRY(c->d_iterates.grow(need * sizeof(double)));
+        std::vector<double> nanv(need, std::numeric_limits<double>::quiet_NaN());
+        HIP_TRY(hipMemcpyAsync(c->d_iterates, nanv.data(), need * sizeof(double), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+    }
+    s.act.assign(n, 1), s.zeros.assign(n, 0);
+    HIP_TRY(hipMemcpyAsync(c->d_active, s.act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_iters, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_info, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
+    return reset_fill_counters(c, n);
+}
+
+// the results to the caller, per-chain failures marked.  *repeat: the search has to be run again (below).
+int search_end(emme_ctx* c, const RootSearch& s, double* roots, int* iters, int* info, double* iterates, bool* repeat) {
+    const int n = s.n;
+    std::vector<unsigned long long> iv;
+    std::vector<int> stv;
+    HIP_TRY(hipMemcpyAsync(roots, c->d_omega, sizeof(double) * 2 * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(iters, c->d_iters, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+    EMME_TRY(queue_fill_counters(c, n, iv, &stv));
+    if (iterates)
+        HIP_TRY(hipMemcpyAsync(iterates, c->d_iterates, sizeof(double) * 2 * (size_t)n * s.stride(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->last_n = n;
+    (void)fold_fill_counters(c, iv, nullptr);  // (flagged chains are marked one by one, below)
+    bool timed_out = false;
+    for (int b = 0; b < n; ++b) {
+        // a chain that met a non-finite integral or the quadrature depth cap is reported
+        // per item (the reference would carry the NaN to its "eigenvalue": "NaN" record,
+        // src/main.cpp:311-316); the other chains of the batch are unaffected
+        if (stv[b] != 0 && info[b] == 0) info[b] = EMME_ENUMERIC;
+        // whatever the cause, a non-finite omega is never handed back as a root
+        if (info[b] == 0 && !(std::isfinite(roots[2 * b]) && std::isfinite(roots[2 * b + 1]))) info[b] = EMME_ENUMERIC;
+        timed_out |= info[b] == EMME_EDEVICE;
+    }
+    // The multi-workgroup LU needs its workgroups resident together; if something else held
+    // compute units for seconds (a foreign kernel on a shared device) a hand-over wait timed out
+    // and retired those chains with EMME_EDEVICE.  Do the search again with one workgroup per
+    // matrix, and keep it that way for this context.
+    *repeat = timed_out && !c->lu_one_wg;
+    if (*repeat) {
+        c->lu_one_wg = true;
+        if (std::getenv("EMME_DEBUG")) fprintf(stderr, "[emme] LU hand-over timed out: repeating the search with one workgroup per matrix\n");
+    }
+    return EMME_OK;
+}
+
+// The secant search of emme_solve_roots (EigenSolver's constructor and newtonTraceSecantIteration, include/solver.h:
+// 396-415 and 113-160, under the loop of src/main.cpp:19-80), between search_begin and search_end.
+int secant_loop(emme_ctx* c, RootSearch& search) {
+    const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
+    const double* guesses = search.guesses;
+    const double tol = search.tol;
+    double* const d_iterates = search.d_iterates(c);
+    std::vector<int>& act = search.act;
+    // EigenSolver ctor (include/solver.h:396-415): eigen_value = 0.99 g, d = 0.01 g;
+    // M_old = M(eigen_value); eigen_value += d; M = M(eigen_value); M' = (M - M_old)/d
+    std::vector<double> w0(2 * (size_t)n), dw(2 * (size_t)n), w1(2 * (size_t)n);
+    for (int b = 0; b < 2 * n; ++b) {
+        w0[b] = 0.99 * guesses[b];
+        dw[b] = 0.01 * guesses[b];
+        w1[b] = w0[b] + dw[b];
+    }
+    HIP_TRY(hipMemcpyAsync(c->d_omega, w0.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(c->d_domega, dw.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    StepFeedback& fb = c->fb;
+    fb.begin(n);
+    HIP_TRY(hipMemsetAsync(c->d_overflow, 0, sizeof(unsigned int) * n, c->stream));
+    std::vector<double> h_w(2 * (size_t)n);
+    std::vector<unsigned long long> iv_now(n, 0), iv_prev_dbg(n, 0);
+    auto refresh_cost = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(iv_now.data(), c->d_intervals, sizeof(unsigned long long) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        fb.take(iv_now.data());
+        return EMME_OK;
+    };
+    FillRequest first(n, c->d_omega, c->d_Mold);
+    first.host_omega = w0.data(), first.newton_loop = true;
+    EMME_TRY(fill(c, first));
+    EMME_TRY(refresh_cost());  // synchronises; the first fill's interval counts order the second
+    HIP_TRY(hipMemcpyAsync(c->d_omega, w1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    // (the fills of a root search write M only: the secant M' = (M - M_old) / d, include/solver.h:157 and :412, is
+    // taken by k_secant_copy at the top of the step that uses it, in one coalesced pass)
+    FillRequest next(n, c->d_omega, c->d_M);
+    next.host_omega = w1.data(), next.cost = fb.cost.data(), next.newton_loop = true;
+    EMME_TRY(fill(c, next));
+    next.host_omega = h_w.data(), next.d_active = c->d_active, next.host_active = act.data();  // (the steps' fills)
+
+    EMME_TRY(refresh_cost());
+    // One stream synchronisation per Newton step: the host needs the new omegas (contour
+    // classes, cache growth) before it can launch the fill.  The active flags and interval
+    // counts a fill leaves behind travel to pinned memory asynchronously and are read after the
+    // NEXT step's synchronisation, so the LU and the update of that step are queued behind the
+    // fill without a bubble (their list of live matrices is one step old: a superset).
+    bool pending = false;
+    int j_pending = 0;
+    auto take_pending = [&]() {  // results of the previous step's fill + retire
+        std::copy(c->p_act.get(), c->p_act.get() + n, act.begin());
+        // (an item an eighth of whose integrals did not fit the 64-entry level lists: 128 entries from now on)
+        fb.take(c->p_iv, c->p_overflow, c->npairs, c->p_deferred);
+        pending = false;
+        if (std::getenv("EMME_DEBUG")) {
+            unsigned long long tot = 0, mx = 0;
+            int na = 0, nprev = 0;
+            for (int b = 0; b < n; ++b) {
+                if (fb.iv_prev[b] != iv_prev_dbg[b]) {  // (iv_prev: the counters just taken)
+                    const unsigned long long d = fb.iv_prev[b] - iv_prev_dbg[b];
+                    tot += d, mx = d > mx ? d : mx, ++nprev;
+                }
+                iv_prev_dbg[b] = fb.iv_prev[b];
+                na += act[b] != 0;
+            }
+            fprintf(stderr, "[emme] LU workgroups per matrix %d\n", c->last_lu_nwg);
+            fprintf(stderr, "[emme] iter %2d: assembled %3d, lane-intervals %10llu (max/item %9llu), still active %d\n",
+                    j_pending, nprev, tot, mx, na);
+        }
+    };
+    for (int j = 0; j <= step_limit; ++j) {  // src/main.cpp:43
+        const bool fused_copy = method == EMME_METHOD_TRACE_SECANT;
+        {
+            // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
+            // LU's work copy): one pass, for the chains still iterating only
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_secant_copy_sym(c->dim, n, c->d_M, c->d_Mold, fused_copy ? c->d_work : nullptr, c->d_Mp,
+                                           c->d_domega, c->d_active, c->stream));
+        }
+        {
+            ScopedSpan s(c, K_LIN);
+            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                act.data(), fused_copy));
+        }
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters,
+                                         c->d_info, tol, d_iterates, j, stride, c->stream, c->p_w,
+                                         c->opt.skip_lost ? c->d_status : nullptr));
+        }
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
+        if (pending) {
+            take_pending();
+            bool any = false;
+            for (int b = 0; b < n; ++b) any |= act[b] != 0;
+            if (!any) break;  // (this step's LU and update found nothing active: no-ops)
+        }
+        EMME_TRY(fill(c, next));
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_retire(n, c->d_active, c->stream, c->p_act, c->d_intervals, c->p_iv,
+                                  c->d_worklist_count, c->p_deferred, c->d_overflow, c->p_overflow));
+        }
+        pending = true, j_pending = j;
+    }
+    return EMME_OK;
+}
+
+// The Newton search of emme_solve_roots_newton, between search_begin and search_end.
+int newton_loop(emme_ctx* c, RootSearch& search) {
+    const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
+    const double tol = search.tol;
+    double* const d_iterates = search.d_iterates(c);
+    std::vector<int>& act = search.act;
+    // omega_0 = g: one fill of M and the exact M' there, no secant bootstrap
+    HIP_TRY(hipMemcpyAsync(c->d_omega, search.guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
+    FillRequest both(n, c->d_omega, c->d_M);
+    both.d_Md = c->d_Mp, both.d_active = c->d_active, both.host_active = act.data();
+    // Option deriv_cached: the fills may go through the node cache, which needs what the secant loop gives its fills --
+    // the live omegas on the host (contour classes), every omega's interval count of its previous fill (cost order)
+    // and the root-search flag (skip_lost).  They travel as there: k_newton_update writes the omegas, k_retire the
+    // counters and the deferred count into pinned memory, read after the step's one synchronisation.
+    const bool cached = c->opt.deriv_cached != 0;
+    std::vector<double> h_w;
+    StepFeedback& fb = c->fb;
+    bool pending = false;
+    if (cached) {
+        h_w.assign(search.guesses, search.guesses + 2 * (size_t)n);
+        fb.begin(n);
+        both.host_omega = h_w.data(), both.newton_loop = true;
+        fb.pub_valid = false;
+    }
+    auto publish = [&]() -> hipError_t {
+        if (!cached) return launch_retire(n, c->d_active, c->stream);
+        pending = true;
+        return launch_retire(n, c->d_active, c->stream, nullptr, c->d_intervals, c->p_iv, c->d_worklist_count, c->p_deferred);
+    };
+    EMME_TRY(fill(c, both));
+    if (cached) {
+        // (the first fill's counts order the second; no chain has been retired yet: every flag is 1)
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(publish());
+        both.cost = fb.cost.data();
+    }
+    for (int j = 0; j <= step_limit; ++j) {
+        {
+            // the step of the context's iteration_method on (M, M'): trace form on a work copy of M (the LU destroys
+            // both operands; M' is filled again before it is needed), QR form on the transpose
+            ScopedSpan s(c, K_LIN);
+            const bool trace = method == EMME_METHOD_TRACE_SECANT;
+            if (trace) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
+            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                act.data(), trace));
+        }
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
+                                         d_iterates, j, stride, c->stream, cached ? c->p_w.get() : nullptr,
+                                         c->opt.skip_lost ? c->d_status : nullptr));
+        }
+        // the live chains (2 = converged at this step: M and M' are filled at the new omega once more)
+        HIP_TRY(hipMemcpyAsync(c->p_act, c->d_active, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipStreamSynchronize(c->stream));
+        bool any = false;
+        for (int b = 0; b < n; ++b) {
+            act[b] = c->p_act[b];
+            any |= act[b] != 0;
+        }
+        if (!any) break;
+        if (cached) {
+            std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
+            if (pending) {  // what the previous fill left behind
+                fb.take(c->p_iv, nullptr, 0, c->p_deferred);
+                pending = false;
+            }
+        }
+        EMME_TRY(fill(c, both));
+        {
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(publish());
+        }
+    }
+    return EMME_OK;
+}
+
+int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_limit, double* roots, int* iters, int* info,
+               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&)) {
+    if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
+    RootSearch s{guesses, n, tol, step_limit, iterates != nullptr};
+    s.method = c->p.iteration_method;  // src/main.cpp:45-49
+    EMME_TRY(check_method(c, s.method));
+    HIP_TRY(hipSetDevice(c->device));
+    for (;;) {
+        bool repeat = false;
+        EMME_TRY(search_begin(c, s, mat_sets));
+        EMME_TRY(loop(c, s));
+        EMME_TRY(search_end(c, s, roots, iters, info, iterates, &repeat));
+        if (!repeat) return EMME_OK;
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nbatch, double* M,
+                           double* Mp, int method, int* info) {
+    if (!c || !omega || !domega || !M || !Mp || !info || nbatch < 1) return EMME_EINVAL;
+    EMME_TRY(check_method(c, method));
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    bool dev = false;
+    EMME_TRY(same_side(M, Mp, "M and Mp", &dev));
+    const size_t mbytes = batch_bytes(c->dim, nbatch);
+    EMME_TRY(ensure_mats(c, nbatch, dev ? (2 | 8) : (1 | 2 | 4 | 8)));
+    double *dM = M, *dMp = Mp;
+    if (!dev) {
+        dM = c->d_M, dMp = c->d_Mp;
+        HIP_TRY(hipMemcpyAsync(dM, M, mbytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(dMp, Mp, mbytes, hipMemcpyHostToDevice, c->stream));
+    }
+    const hipMemcpyKind in_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    EMME_TRY(upload_omega(c, omega, nbatch, in_kind));
+    EMME_TRY(reset_fill_counters(c, nbatch));
+    {
+        // eigen_matrix_old = eigen_matrix (include/solver.h:114); the factorisation then
+        // consumes a scratch copy so M_old survives for the secant update
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(hipMemcpyAsync(c->d_Mold, dM, mbytes, hipMemcpyDeviceToDevice, c->stream));
+    }
+    {
+        ScopedSpan s(c, K_LIN);
+        HIP_TRY(linear_step(c, method, c->dim, nbatch, dM, c->d_work, dMp, nullptr, c->d_tr, c->d_info));
+    }
+    {
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(launch_newton_update(nbatch, c->d_tr, c->d_omega, c->d_domega, nullptr, nullptr,
+                                     c->d_info, 0.0, nullptr, 0, 0, c->stream));
+    }
+    std::vector<double> h_w(2 * (size_t)nbatch);
+    HIP_TRY(hipMemcpyAsync(h_w.data(), c->d_omega, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    FillRequest secant_fill(nbatch, c->d_omega, dM);
+    secant_fill.host_omega = h_w.data();
+    secant_fill.d_Mold = c->d_Mold, secant_fill.d_Mp = dMp, secant_fill.d_domega = c->d_domega;
+    EMME_TRY(fill(c, secant_fill));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(M, dM, mbytes, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(Mp, dMp, mbytes, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(hipMemcpyAsync(omega, c->d_omega, sizeof(double) * 2 * nbatch, out_kind, c->stream));
+    HIP_TRY(hipMemcpyAsync(domega, c->d_domega, sizeof(double) * 2 * nbatch, out_kind, c->stream));
+    std::vector<unsigned long long> iv;
+    EMME_TRY(queue_fill_counters(c, nbatch, iv, nullptr));  // (the status flags are not this call's to report)
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch,
+                           is_device_ptr(info) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    (void)fold_fill_counters(c, iv, nullptr);
+    return EMME_OK;
+}
+
+int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit,
+                     double* roots, int* iters, int* info, double* iterates) {
+    return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 2 | 4 | 8, secant_loop);
+}
+
+int emme_solve_roots_newton(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit, double* roots,
+                            int* iters, int* info, double* iterates) {
+    return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop);  // (no M_old)
+}
+
+}  // extern "C"

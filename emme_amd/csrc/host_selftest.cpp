@@ -1,9 +1,11 @@
 // host_selftest.cpp -- the host layer above the C ABI (JSON dialect reader, parameters, tables,
-// scan generator, null vector, driver error paths, the fill planner) built WITHOUT the device code and run under
+// scan generator, null vector, driver error paths, the fill planner, the options, the LU workgroup count, a root
+// search's step feedback) built WITHOUT the device code and run under
 // AddressSanitizer + UBSan:   make -C emme_amd/csrc host-sanitize
 // (GPU sanitizers are not available on the target pool; this covers the CPU side.)
 // The device entry points the driver calls are stubbed to fail with EMME_EDEVICE, so
 // emme_run_json is exercised up to and including its "no device" error record.
+#include <cctype>
 #include <cmath>
 #include <complex>
 #include <cstdio>
@@ -14,6 +16,9 @@
 
 #include "../../include/emme_hip.h"
 #include "fill_plan.hpp"
+#include "linstep_plan.hpp"
+#include "options.hpp"
+#include "step_feedback.hpp"
 
 namespace emme {
 static thread_local std::string g_err;
@@ -214,6 +219,235 @@ static void check_fill_plans() {
           emme::contour_class(-0.0) == 0);
 }
 
+// ---- the options (options.cpp) ---------------------------------------------------------------------------------
+struct IntOpt {
+    const char* name;  // of the field; "EMME_" + its upper case is the environment override, unless `env` names it
+    int emme_options_t::*f;
+    int dflt;
+    int lo_ok, lo_bad, hi_ok, hi_bad;  // last accepted / first rejected value at either end (kNone: no bound there)
+    const char* env;                   // null: irregular override, with a case of its own below
+};
+struct DblOpt {
+    const char* name;
+    double emme_options_t::*f;
+    double dflt, lo_ok, lo_bad;
+    const char* env;
+};
+static const int kNone = 0x7fffffff;
+static const std::vector<IntOpt> kIntOpts = {
+    {"cache_min_batch", &emme_options_t::cache_min_batch, 8, 1, 0, kNone, kNone, "EMME_CACHE_MIN_BATCH"},
+    {"cache_min_depth", &emme_options_t::cache_min_depth, 0, 0, -1, kNone, kNone, "EMME_CACHE_MIN_DEPTH"},
+    {"fill", &emme_options_t::fill, EMME_FILL_AUTO, EMME_FILL_AUTO, -1, EMME_FILL_LANES, 3, nullptr},
+    {"phase_table", &emme_options_t::phase_table, 1, kNone, kNone, kNone, kNone, "EMME_PHASE_TABLE"},
+    {"em_shared", &emme_options_t::em_shared, 1, kNone, kNone, kNone, kNone, "EMME_EM_SHARED"},
+    {"wl_min", &emme_options_t::wl_min, 4, 1, 0, kNone, kNone, "EMME_WL_MIN"},
+    {"union_sel", &emme_options_t::union_sel, 2, 1, 0, 4, 5, "EMME_UNION_SEL"},
+    {"union_ipg_few", &emme_options_t::union_ipg_few, 2, 1, 0, kNone, kNone, "EMME_UNION_IPG_FEW"},
+    {"union_few_chunks", &emme_options_t::union_few_chunks, 3, 0, -1, kNone, kNone, "EMME_UNION_FEW_CHUNKS"},
+    {"coop_wide_min", &emme_options_t::coop_wide_min, 4096, -1, -2, kNone, kNone, "EMME_COOP_WIDE_MIN"},
+    {"defer_one_group", &emme_options_t::defer_one_group, 0, kNone, kNone, kNone, kNone, nullptr},
+    {"dense_min_cols", &emme_options_t::dense_min_cols, 3, 1, 0, 17, 18, "EMME_DENSE_MIN_COLS"},
+    {"dense_min_tasks", &emme_options_t::dense_min_tasks, 2000, 0, -1, kNone, kNone, "EMME_DENSE_MIN_TASKS"},
+    {"dense_wide", &emme_options_t::dense_wide, 0, kNone, kNone, kNone, kNone, "EMME_DENSE_WIDE"},
+    {"skip_lost", &emme_options_t::skip_lost, 1, kNone, kNone, kNone, kNone, "EMME_SKIP_LOST"},
+    {"lu_split", &emme_options_t::lu_split, 0, 0, -1, 16, 17, "EMME_LU_SPLIT"},
+    {"lu_group_min_n", &emme_options_t::lu_group_min_n, 256, kNone, kNone, kNone, kNone, nullptr},
+    {"lu_spin_limit", &emme_options_t::lu_spin_limit, 16000000, 1, 0, kNone, kNone, "EMME_LU_SPIN_LIMIT"},
+    {"lu_unblocked", &emme_options_t::lu_unblocked, 0, kNone, kNone, kNone, kNone, nullptr},
+    {"deriv_cached", &emme_options_t::deriv_cached, 0, 0, -1, 1, 2, "EMME_DERIV_CACHED"},
+};
+static const std::vector<DblOpt> kDblOpts = {
+    {"node_cache_gb", &emme_options_t::node_cache_gb, 176.0, 0.0, -1e-300, "EMME_NODE_CACHE_GB"},
+    {"dense_cost_ratio", &emme_options_t::dense_cost_ratio, 4.0, 1e-300, 0.0, "EMME_DENSE_COST_RATIO"},
+};
+static const char* const kIrregularEnv[] = {"EMME_DENSE", "EMME_UNION", "EMME_DEFER_ONE_GROUP", "EMME_LU_GROUP", "EMME_LU_UNBLOCKED"};
+
+static emme_options_t default_options() {
+    emme_options_t o;
+    emme::options_default(o);
+    return o;
+}
+
+// a and b agree in every field but (at most) the one `except` points at
+static bool same_options(const emme_options_t& a, const emme_options_t& b, const void* except = nullptr) {
+    bool same = a.size == b.size;
+    for (const IntOpt& k : kIntOpts) same &= &(a.*k.f) == except || a.*k.f == b.*k.f;
+    for (const DblOpt& k : kDblOpts) same &= &(a.*k.f) == except || a.*k.f == b.*k.f;
+    return same;
+}
+
+// options_default + the environment as it stands
+static emme_options_t overridden(int fill = EMME_FILL_AUTO) {
+    emme_options_t o = default_options();
+    o.fill = fill;
+    emme::options_env_overrides(o);
+    return o;
+}
+
+static void check_options(const emme_params_t& params) {
+    for (const IntOpt& k : kIntOpts)
+        if (k.env) unsetenv(k.env);
+    for (const DblOpt& k : kDblOpts) unsetenv(k.env);
+    for (const char* e : kIrregularEnv) unsetenv(e);
+
+    // defaults
+    const emme_options_t d = default_options();
+    CHECK(d.size == (int)sizeof(emme_options_t) && emme::options_check(&d) == EMME_OK);
+    for (const IntOpt& k : kIntOpts) CHECK(d.*k.f == k.dflt);
+    for (const DblOpt& k : kDblOpts) CHECK(d.*k.f == k.dflt);
+    CHECK(same_options(overridden(), d));  // (an empty environment overrides nothing)
+
+    // bounds: the last accepted and the first rejected value of each
+    auto accepts = [&](auto field, auto value) {
+        emme_options_t o = d;
+        o.*field = value;
+        emme::set_error("");
+        const int rc = emme::options_check(&o);
+        CHECK(rc == EMME_OK || (rc == EMME_EINVAL && std::strcmp(emme_last_error(), "emme_options_t: value out of range") == 0));
+        return rc == EMME_OK;
+    };
+    for (const IntOpt& k : kIntOpts) {
+        if (k.lo_ok != kNone) CHECK(accepts(k.f, k.lo_ok) && !accepts(k.f, k.lo_bad));
+        if (k.hi_ok != kNone) CHECK(accepts(k.f, k.hi_ok) && !accepts(k.f, k.hi_bad));
+    }
+    for (const DblOpt& k : kDblOpts) CHECK(accepts(k.f, k.lo_ok) && !accepts(k.f, k.lo_bad) && !accepts(k.f, std::nan("")));
+    for (int v = -1; v <= 9; ++v) CHECK(accepts(&emme_options_t::union_sel, v) == (v == 1 || v == 2 || v == 4));
+    CHECK(accepts(&emme_options_t::dense_min_cols, 1) && accepts(&emme_options_t::dense_min_cols, 17));
+    CHECK(!accepts(&emme_options_t::dense_min_cols, 0) && !accepts(&emme_options_t::dense_min_cols, 18));
+    CHECK(accepts(&emme_options_t::lu_split, 0) && accepts(&emme_options_t::lu_split, 16) && !accepts(&emme_options_t::lu_split, 17));
+    CHECK(accepts(&emme_options_t::deriv_cached, 1) && !accepts(&emme_options_t::deriv_cached, 2));
+    CHECK(!accepts(&emme_options_t::node_cache_gb, std::nan("")));
+    {
+        emme_options_t o = d;
+        o.size = (int)sizeof(emme_options_t) - 4;
+        CHECK(emme::options_check(&o) == EMME_EINVAL && std::strstr(emme_last_error(), "size field does not match") != nullptr);
+    }
+
+    // environment overrides: the regular ones set their field to the number they hold, and nothing else
+    for (const IntOpt& k : kIntOpts) {
+        if (!k.env) continue;
+        CHECK(std::string(k.env) == "EMME_" + [&] { std::string u(k.name); for (char& ch : u) ch = (char)std::toupper(ch); return u; }());
+        setenv(k.env, "7", 1);
+        const emme_options_t o = overridden();
+        CHECK(o.*k.f == 7 && same_options(o, d, &(o.*k.f)));
+        unsetenv(k.env);
+    }
+    for (const DblOpt& k : kDblOpts) {
+        setenv(k.env, "2.5", 1);
+        const emme_options_t o = overridden();
+        CHECK(o.*k.f == 2.5 && same_options(o, d, &(o.*k.f)));
+        unsetenv(k.env);
+    }
+    // EMME_DENSE=0 acts on FILL_AUTO only; EMME_UNION=0 on every mode, and wins
+    setenv("EMME_DENSE", "0", 1);
+    CHECK(overridden(EMME_FILL_AUTO).fill == EMME_FILL_UNION && overridden(EMME_FILL_UNION).fill == EMME_FILL_UNION &&
+          overridden(EMME_FILL_LANES).fill == EMME_FILL_LANES);
+    {
+        const emme_options_t o = overridden();
+        CHECK(same_options(o, d, &o.fill));
+    }
+    setenv("EMME_UNION", "0", 1);
+    CHECK(overridden(EMME_FILL_AUTO).fill == EMME_FILL_LANES);
+    setenv("EMME_DENSE", "1", 1);
+    CHECK(overridden(EMME_FILL_AUTO).fill == EMME_FILL_LANES && overridden(EMME_FILL_UNION).fill == EMME_FILL_LANES);
+    setenv("EMME_UNION", "1", 1);
+    CHECK(same_options(overridden(), d) && overridden(EMME_FILL_UNION).fill == EMME_FILL_UNION);
+    unsetenv("EMME_DENSE"), unsetenv("EMME_UNION");
+    // EMME_LU_GROUP: zero and below mean "never"
+    for (const char* v : {"0", "-3"}) {
+        setenv("EMME_LU_GROUP", v, 1);
+        const emme_options_t o = overridden();
+        CHECK(o.lu_group_min_n == -1 && same_options(o, d, &o.lu_group_min_n));
+    }
+    setenv("EMME_LU_GROUP", "128", 1);
+    CHECK(overridden().lu_group_min_n == 128);
+    unsetenv("EMME_LU_GROUP");
+    // EMME_DEFER_ONE_GROUP and EMME_LU_UNBLOCKED act by presence, whatever they hold
+    for (const char* v : {"", "0", "1"}) {
+        setenv("EMME_DEFER_ONE_GROUP", v, 1);
+        emme_options_t o = overridden();
+        CHECK(o.defer_one_group == 1 && same_options(o, d, &o.defer_one_group));
+        unsetenv("EMME_DEFER_ONE_GROUP");
+        setenv("EMME_LU_UNBLOCKED", v, 1);
+        o = overridden();
+        CHECK(o.lu_unblocked == 1 && same_options(o, d, &o.lu_unblocked));
+        unsetenv("EMME_LU_UNBLOCKED");
+    }
+    // an override is taken as it is; the range check that follows it at context creation refuses it
+    setenv("EMME_UNION_SEL", "3", 1);
+    {
+        const emme_options_t o = overridden();
+        CHECK(o.union_sel == 3 && emme::options_check(&o) == EMME_EINVAL);
+    }
+    unsetenv("EMME_UNION_SEL");
+
+    // wants_tiled: both quadrature orders, folded records, goal no tighter than 1e-9, the default fill mode
+    emme_params_t p = params;
+    p.integration_accuracy = 1e-9;
+    for (int pts : {15, 21, 31}) {
+        p.integration_start_points = pts;
+        CHECK(emme::wants_tiled(p, true, EMME_FILL_AUTO) == (pts != 21));
+        CHECK(!emme::wants_tiled(p, false, EMME_FILL_AUTO));
+        CHECK(!emme::wants_tiled(p, true, EMME_FILL_UNION) && !emme::wants_tiled(p, true, EMME_FILL_LANES));
+    }
+    p.integration_accuracy = 9e-10;
+    CHECK(!emme::wants_tiled(p, true, EMME_FILL_AUTO));
+}
+
+// ---- workgroups per matrix of the blocked LU (linstep_plan.hpp), on 256 compute units ----------------------------
+static void check_lu_workgroups() {
+    auto nwg = [](int n, int live, int lu_split = 0, bool one_wg = false, bool fits = true) {
+        return emme::lu_workgroups(n, live, 256, lu_split, one_wg, fits);
+    };
+    CHECK(nwg(256, 128) == 2);  // the headline search: two compute units per matrix
+    CHECK(nwg(256, 18) == 4);   // a late step: four are enough at this order
+    CHECK(nwg(512, 32) == 8);
+    CHECK(nwg(768, 4) == 16);
+    CHECK(nwg(64, 1) == 1);
+    CHECK(nwg(127, 1) == 1 && nwg(128, 1) == 4);
+    CHECK(nwg(256, 128, 40) == 16 && nwg(256, 128, 3) == 3);  // pinned, capped at 16
+    CHECK(nwg(256, 1, 0, true) == 1 && nwg(256, 1, 8, true) == 1 && nwg(600, 1, 0, true, false) == 1);
+    CHECK(nwg(600, 300, 0, false, false) == 2);  // (256 / 300 = 0 -> 1, and the chunked build needs two)
+    CHECK(nwg(600, 300, 0, false, true) == 1);
+    CHECK(nwg(600, 4, 1, false, false) == 1);    // pinned to one: the caller falls back to the unblocked kernel
+}
+
+// ---- a root search's step feedback (step_feedback.hpp): three takes over five items, N = 24 (276 pairs) ---------
+static void check_step_feedback() {
+    using V = std::vector<unsigned long long>;
+    using W = std::vector<unsigned char>;
+    const int npairs = 24 * 23 / 2;  // 276 / 8 = 34.5: 34 overflowed integrals stay below the eighth, 35 reach it
+    emme::StepFeedback fb;
+    fb.begin(5);
+    CHECK(fb.cost == V(5, 0) && fb.iv_prev == V(5, 0) && fb.wide == W(5, 0) && !fb.pub_valid);
+    // the bootstrap fill, read back by the host itself: counters only
+    const V iv1 = {100, 200, 300, 400, 0};
+    fb.take(iv1.data());
+    CHECK(fb.cost == (V{100, 200, 300, 400, 0}) && fb.iv_prev == iv1 && fb.wide == W(5, 0));
+    CHECK(!fb.pub_valid && fb.last_deferred == 0);
+    // a step's fill: item 3 was not filled (keeps its cost) and is wide from now on; item 2 just below the threshold
+    const V iv2 = {150, 260, 390, 400, 0};
+    const std::vector<unsigned int> ov2 = {0, 0, 34, 100, 0};
+    unsigned int deferred = 7;
+    fb.take(iv2.data(), ov2.data(), npairs, &deferred);
+    CHECK(fb.cost == (V{50, 60, 90, 400, 0}) && fb.iv_prev == iv2 && fb.wide == (W{0, 0, 0, 1, 0}));
+    CHECK(fb.pub_valid && fb.last_deferred == 7);
+    fb.pub_valid = false;  // (the next fill uses the count)
+    // the next: item 1 retired, item 2 reaches the threshold, item 3 overflows nothing and stays wide
+    const V iv3 = {175, 260, 400, 520, 0};
+    const std::vector<unsigned int> ov3 = {0, 0, 35, 0, 0};
+    deferred = 0;
+    fb.take(iv3.data(), ov3.data(), npairs, &deferred);
+    CHECK(fb.cost == (V{25, 60, 10, 120, 0}) && fb.iv_prev == iv3 && fb.wide == (W{0, 0, 1, 1, 0}));
+    CHECK(fb.pub_valid && fb.last_deferred == 0);
+    // a take without the deferred count (the Newton search's counters travel without overflow counts) leaves both
+    fb.pub_valid = false, fb.last_deferred = 9;
+    fb.take(iv3.data());
+    CHECK(!fb.pub_valid && fb.last_deferred == 9 && fb.cost == (V{25, 60, 10, 120, 0}) && fb.wide == (W{0, 0, 1, 1, 0}));
+    fb.begin(2);  // the next search
+    CHECK(fb.cost == V(2, 0) && fb.iv_prev == V(2, 0) && fb.wide == W(2, 0));
+}
+
 static const char* kInput =
     "{ \"conf\": \"tokamak\", \"method\": \"eigen\", \"iteration_method\": \"TraceSecant\", \"q\": 1.4, \"shat\": 0.78,"
     " \"tau\": 1.0, \"epsilon_n\": 0.45, \"epsilon_r\": 0.0, \"eta_i\": 3.13, \"eta_e\": 3.13, \"k_rho\": 0.3182,"
@@ -286,6 +520,9 @@ int main() {
     CHECK(rc != EMME_OK || out != nullptr);
     if (out) emme_free(out);
     check_fill_plans();
+    check_options(p);
+    check_lu_workgroups();
+    check_step_feedback();
     if (failures) {
         std::fprintf(stderr, "%d check(s) failed\n", failures);
         return 1;

@@ -4,7 +4,7 @@
 // arguments the fill kernels would hand it, and writes the result to the thread's own output slot.  The point
 // is to see a single node: the fill kernels only ever show sums over thousands of them.
 #include "assemble_common.hpp"
-#include "launch.hpp"
+#include "ctx.hpp"
 
 namespace emme {
 namespace {
@@ -161,3 +161,84 @@ hipError_t launch_integrand_probe(const IntegrandProbe& A, hipStream_t stream) {
 }
 
 }  // namespace emme
+
+// ---- the entry points (include/emme_hip.h): no context, buffers of the call's own, the default stream ---------------
+using namespace emme;
+
+extern "C" {
+
+int emme_bessel_batch(const double* z, int n, double* out) {
+    if (!z || !out || n < 1) return EMME_EINVAL;
+    EMME_TRY(require_device());
+    DeviceBuffer<double> dz, dout;
+    HIP_TRY(dz.grow(sizeof(double) * 2 * n));
+    HIP_TRY(dout.grow(sizeof(double) * 8 * n));
+    HIP_TRY(hipMemcpy(dz, z, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    HIP_TRY(launch_bessel_probe(dz, n, dout, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * 8 * n, hipMemcpyDeviceToHost));
+    return EMME_OK;
+}
+
+int emme_elementary_batch(int fn, const double* x, int n, double* out) {
+    if (!x || !out || n < 1 || fn < 0 || fn > EMME_FN_CRCP) return EMME_EINVAL;
+    EMME_TRY(require_device());
+    const size_t n_in = fn == EMME_FN_CRCP ? 2 : 1;
+    const size_t n_out = fn >= EMME_FN_SINCOS ? 2 : 1;
+    DeviceBuffer<double> dx, dout;
+    HIP_TRY(dx.grow(sizeof(double) * n_in * n));
+    HIP_TRY(dout.grow(sizeof(double) * n_out * n));
+    HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n_in * n, hipMemcpyHostToDevice));
+    HIP_TRY(launch_elementary_probe(fn, dx, n, dout, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * n_out * n, hipMemcpyDeviceToHost));
+    return EMME_OK;
+}
+
+int emme_integrand_batch(const emme_params_t* p, int form, int n, const int* i, const int* j, const int* m,
+                         const double* x, const double* omega, double* out) {
+    if (!p || !i || !j || !m || !x || !omega || !out || n < 1 || form < 0 || form > EMME_FORM_W) return EMME_EINVAL;
+    EMME_TRY(check_npoints(p));
+    // the scalars DevParams divides by: a zero or non-finite one would put inf / NaN into every item
+    for (const double v : {p->arc_coeff, p->vt, p->tau, p->q, p->R, p->omega_s_i}) {
+        if (!std::isfinite(v) || v == 0.0) {
+            set_error("emme_integrand_batch: arc_coeff, vt, tau, q, R and omega_s_i must be finite and non-zero");
+            return EMME_EINVAL;
+        }
+    }
+    const int nm = std::fpclassify(p->beta_e) == FP_ZERO ? 1 : 3;
+    for (int k = 0; k < n; ++k) {
+        const bool pair_ok = i[k] >= 0 && i[k] < j[k] && j[k] < p->npoints;
+        const bool x_ok = x[k] > 0.0 && x[k] < M_PI / 2;  // (false for NaN)
+        if (!pair_ok || m[k] < 0 || m[k] >= nm || !x_ok) {
+            set_error("emme_integrand_batch: item " + std::to_string(k) +
+                      " needs 0 <= i < j < npoints, a moment of the context (0, or 0..2 with beta_e != 0) and x in (0, pi/2)");
+            return EMME_EINVAL;
+        }
+    }
+    EMME_TRY(require_device());
+    IntegrandProbe A;
+    std::vector<double> tab;
+    dev_params_from(p, A.P, tab);
+    A.form = form, A.n = n;
+    const size_t per = (size_t)integrand_probe_doubles(form);
+    DeviceBuffer<double> dtab, dx, dw, dout;
+    DeviceBuffer<int> dijm;
+    HIP_TRY(dtab.grow(sizeof(double) * tab.size()));
+    HIP_TRY(dx.grow(sizeof(double) * n));
+    HIP_TRY(dw.grow(sizeof(double) * 2 * n));
+    HIP_TRY(dout.grow(sizeof(double) * per * n));
+    HIP_TRY(dijm.grow(sizeof(int) * 3 * (size_t)n));
+    HIP_TRY(hipMemcpy(dtab, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dx, x, sizeof(double) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(dw, omega, sizeof(double) * 2 * n, hipMemcpyHostToDevice));
+    int* d_ijm = dijm;
+    HIP_TRY(hipMemcpy(d_ijm, i, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ijm + n, j, sizeof(int) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ijm + 2 * (size_t)n, m, sizeof(int) * n, hipMemcpyHostToDevice));
+    A.tab = dtab, A.i = d_ijm, A.j = d_ijm + n, A.m = d_ijm + 2 * (size_t)n;
+    A.x = dx, A.omega = dw, A.out = dout;
+    HIP_TRY(launch_integrand_probe(A, nullptr));
+    HIP_TRY(hipMemcpy(out, dout, sizeof(double) * per * n, hipMemcpyDeviceToHost));
+    return EMME_OK;
+}
+
+}  // extern "C"
