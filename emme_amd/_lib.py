@@ -94,7 +94,9 @@ class Options(C.Structure):
         ("fill", C.c_int), ("phase_table", C.c_int), ("em_shared", C.c_int), ("wl_min", C.c_int),
         ("union_sel", C.c_int), ("union_ipg_few", C.c_int), ("union_few_chunks", C.c_int),
         ("coop_wide_min", C.c_int), ("defer_one_group", C.c_int),
-        ("dense_min_cols", C.c_int), ("dense_min_tasks", C.c_int), ("dense_cost_ratio", C.c_double),
+        ("dense_min_cols", C.c_int), ("dense_min_tasks", C.c_int),
+        ("tile_uncached", C.c_int),  # (in what was alignment padding: no other field moved)
+        ("dense_cost_ratio", C.c_double),
         ("dense_wide", C.c_int),
         ("skip_lost", C.c_int),
         ("lu_split", C.c_int), ("lu_group_min_n", C.c_int), ("lu_spin_limit", C.c_int),
@@ -158,6 +160,8 @@ def load():
     lib.emme_ctx_set_stream.argtypes = [P, P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
+    lib.emme_ctx_last_deferred.argtypes = [P]
+    lib.emme_ctx_last_deferred.restype = C.c_longlong
     lib.emme_ctx_node_cache_gib.argtypes = [P]
     lib.emme_ctx_node_cache_gib.restype = C.c_double
     lib.emme_ctx_cache_settle.argtypes = [P, P, C.c_int, P]
@@ -498,10 +502,18 @@ class Context:
     FILL_KERNELS = {0: "k_assemble (lanes=nodes)", 1: "k_assemble_wl (omega-lane)",
                     2: "k_assemble_cached (HBM node cache)",
                     3: "k_assemble_union (HBM node cache + phase table)",
-                    4: "k_assemble_dense (tiled HBM node cache + weighted phase tables, FP64 matrix cores)"}
+                    4: "k_assemble_dense (tiled HBM node cache + weighted phase tables, FP64 matrix cores)",
+                    5: "k_assemble_tile (table-free tile fill, FP64 matrix cores)"}
 
     def fill_kernel(self) -> str:
         return self.FILL_KERNELS.get(self.lib.emme_ctx_fill_mode(self.h), "none yet")
+
+    def last_deferred(self) -> int:
+        """Integrals the last fill handed to its work list (finished from scratch by a second launch)."""
+        n = self.lib.emme_ctx_last_deferred(self.h)
+        if n < 0:
+            _check(int(n))
+        return int(n)
 
     def fill_kernel_symbol(self) -> str:
         """Name of the last fill's main kernel as rocprofv3 prints it (key of profiles/*_pmc_summary.json)."""
@@ -512,6 +524,8 @@ class Context:
         folded = "true" if o.phase_table else "false"
         if mode == 4:
             return "k_assemble_dense<1, %d, %d>" % (pts, 3 if em else 1)
+        if mode == 5:
+            return "k_assemble_tile"
         if mode == 3:
             return "k_assemble_union<15, %d>" % o.union_sel
         if mode == 2:

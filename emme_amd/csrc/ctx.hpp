@@ -48,7 +48,7 @@ void set_error(const std::string& msg);
 enum Kind { K_ASM = 0, K_LIN = 1, K_OTHER = 2, K_DEFER = 3, K_CACHE = 4, K_NULL = 5 };
 
 // kernel family of a plain fill, as emme_ctx_fill_mode reports it (include/emme_hip.h)
-enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4 };
+enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4, FILL_TILE = 5 };
 
 // HBM node cache of one contour class (omi = +1, -1)
 struct NodeCacheClass {
@@ -87,6 +87,8 @@ struct emme_ctx {
     std::vector<int> h_chunks;
     std::vector<int> h_actidx; // its host image
     int last_fill_mode = -1;   // FillMode of the last plain fill (-1: none yet)
+    int last_fill_listed = 0;  // work list the last fill reset and used (emme_ctx_last_deferred): 0 none, 1 the cached
+                               // fills' (d_worklist), 2 the tile fill's (d_tile_worklist)
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
     // HBM cache of omega-independent node records, per contour class (omi = +1, -1)
     int cache_depth = -1;      // -1: not decided yet, -2: disabled / does not fit, else dfull
@@ -117,6 +119,10 @@ struct emme_ctx {
     DeviceBuffer<double> d_scale;  // half-widths of the cached intervals
     DeviceBuffer<unsigned long long> d_worklist;  // integrals deferred to the cooperative kernel
     DeviceBuffer<unsigned int> d_worklist_count;
+    // the tile fill's own work list: as the minority pass of a cached call it must leave the cached fill's list, count
+    // and missing intervals alone (the next fill grows the cache from them)
+    DeviceBuffer<unsigned long long> d_tile_worklist;
+    DeviceBuffer<unsigned int> d_tile_count;
     DeviceBuffer<double> d_M, d_Mold, d_Mp, d_work;  // matrix sets
     DeviceBuffer<double> d_iterates;
     int last_n = 0;

@@ -285,6 +285,7 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
     L.items_per_group = plan.items_per_group;
     EMME_TRY(stage_lists(c, &c->h_chunks));
     HIP_TRY(hipMemsetAsync(c->d_worklist_count, 0, sizeof(unsigned int), c->stream));
+    c->last_fill_listed = 1;
     if (r.d_Md) {
         // (make_launch leaves a derivative request on the struct defaults, which the uncached kernels keep; here the
         // context's options apply as to a plain dense fill.  last_fill_mode keeps naming the last plain fill.)
@@ -302,14 +303,50 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
     return EMME_OK;
 }
 
+// A plain request without a node cache that the table-free tile fill serves (option tile_uncached):
+// k_assemble_tile exists for electrostatic GK15 under the dense fill's accuracy precondition (the GEMM cannot apply
+// the safe_exp clamp), and its chunks need the omegas' host values (one contour class per chunk).
+bool tile_fill_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
+    return c->opt.tile_uncached != 0 && omega_lane && !r.d_Md && r.host_omega != nullptr && c->nm == 1 &&
+           c->p.integration_start_points == 15 && c->p.integration_accuracy >= 1e-9;
+}
+
+// the omegas of c->h_actidx through k_assemble_tile: chunk plan, lists to the device, the kernel, then the integrals it
+// handed over, from scratch
+int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
+    // a work list of its own (worst case: every integral of the omegas it fills): see ctx.hpp
+    const size_t need = (size_t)c->npairs * c->nm * c->h_actidx.size();
+    HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
+    HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int)));
+    const ChunkPlan plan = plan_tile_chunks(shape_of(c), c->h_actidx, r.host_omega, r.cost, c->h_chunks);
+    L.items_per_group = plan.items_per_group;
+    EMME_TRY(stage_lists(c, &c->h_chunks));
+    HIP_TRY(hipMemsetAsync(c->d_tile_count, 0, sizeof(unsigned int), c->stream));
+    c->last_fill_mode = FILL_TILE;
+    c->last_fill_listed = 2;
+    {
+        ScopedSpan s(c, K_ASM);
+        HIP_TRY(launch_assemble_tile(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
+                                     c->d_rounds, c->stream));
+    }
+    {
+        ScopedSpan s(c, K_DEFER);
+        HIP_TRY(launch_assemble_list(L, c->d_tile_worklist, c->d_tile_count, nullptr, c->folded, c->stream, false));
+    }
+    return EMME_OK;
+}
+
 // without the node cache, plain (L.Md null) or with the exact derivative: batches of wl_min or more items (and
 // the minority pass, whatever its size) go through the omega-lane kernel, which shares the omega-independent node
-// data between items; smaller ones through the lanes-are-nodes kernel.  last_fill_mode names the plain fills'
-// kernel: a derivative fill leaves it alone.
+// data between items -- or, with the option tile_uncached and where it applies, through the table-free tile fill;
+// smaller ones through the lanes-are-nodes kernel.  last_fill_mode names the plain fills' kernel: a derivative fill
+// leaves it alone.
 int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     const FillShape s = shape_of(c);
     const int n_act = (int)c->h_actidx.size(), gw = s.lane_group();
     const bool omega_lane = n_act >= c->opt.wl_min || r.force_uncached;
+    if (tile_fill_applies(c, r, omega_lane)) return launch_tile(c, L, r);
+    c->last_fill_listed = 0;
     L.items_per_group = items_per_group_for(s, omega_lane ? (n_act + gw - 1) / gw : r.nbatch);
     if (omega_lane) {
         EMME_TRY(stage_lists(c, nullptr));

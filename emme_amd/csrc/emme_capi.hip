@@ -339,6 +339,17 @@ int emme_ctx_dim(const emme_ctx_t* c) { return c ? c->dim : EMME_EINVAL; }
 
 int emme_ctx_fill_mode(const emme_ctx_t* c) { return c ? c->last_fill_mode : EMME_EINVAL; }
 
+long long emme_ctx_last_deferred(emme_ctx_t* c) {
+    if (!c) return EMME_EINVAL;
+    const unsigned int* src = c->last_fill_listed == 2 ? c->d_tile_count.get() : c->d_worklist_count.get();
+    if (!c->last_fill_listed || !src) return 0;
+    HIP_TRY(hipSetDevice(c->device));
+    unsigned int cnt = 0;
+    HIP_TRY(hipMemcpyAsync(&cnt, src, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return (long long)cnt;
+}
+
 double emme_ctx_node_cache_gib(const emme_ctx_t* c) {
     return c ? c->cache_bytes_used / (1024.0 * 1024.0 * 1024.0) : 0.0;
 }
@@ -365,7 +376,7 @@ int emme_ctx_profile_read(emme_ctx_t* c, emme_profile_t* out, int reset) {
                     (double)r[4], (double)r[5], (double)r[6], (double)r[7], (double)r[8], (double)r[9],
                     (double)r[4] / (double)(r[0] + r[1] + 1), (double)r[5] / (double)(r[0] + 1),
                     (double)r[6] / (double)(r[1] + 1), (double)r[7] / (double)(r[0] + r[1] + 1));
-        if (c->tiled) {
+        if (c->tiled || c->last_fill_mode == FILL_TILE) {
             c->acc.union_rounds = (long long)(r[0] + r[1]);
             c->acc.dense_rounds = (long long)r[0], c->acc.sparse_rounds = (long long)r[1];
             c->acc.sparse_columns = (long long)r[2], c->acc.tile_tasks = (long long)r[3];

@@ -109,4 +109,53 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
     return plan;
 }
 
+ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const double* host_omega,
+                           const unsigned long long* cost, std::vector<int>& ch) {
+    ChunkPlan plan;
+    ch.clear();
+    if (order.empty()) return plan;
+    // class by class; inside a class the order plan_order made (most expensive first where costs are given)
+    std::stable_partition(order.begin(), order.end(), [&](int b) { return contour_class(host_omega[2 * b]) == 0; });
+    const size_t n = order.size();
+    size_t n0 = 0;
+    while (n0 < n && contour_class(host_omega[2 * order[n0]]) == 0) ++n0;
+    std::vector<unsigned long long> cs;
+    for (int b : order) cs.push_back(cost ? cost[b] : 1ull);
+    std::vector<unsigned long long> sorted = cs;
+    std::sort(sorted.begin(), sorted.end());
+    const double typical = (double)std::max<unsigned long long>(sorted[n / 2], 1ull);
+    // one wave walks a (16-pair tile, chunk) serially and a launch needs several times more tile tasks than the chip
+    // holds waves: the widest chunk shrinks until there are dense_min_tasks of them (plan_chunks)
+    const int tile_cap = 16;
+    int cap_all = tile_cap;
+    const long ntiles = (s.npairs + 15) / 16;
+    auto chunks_at = [&](int cap) { return (long)((n0 + cap - 1) / cap + (n - n0 + cap - 1) / cap); };
+    while (cap_all > 2 && chunks_at(cap_all) * ntiles < (long)s.dense_min_tasks) cap_all >>= 1;
+    // an omega that costs dense_cost_ratio times the typical one gets a narrow chunk: its trees overlap nobody's
+    struct Chunk {
+        int first, size;
+        unsigned long long cost;
+    };
+    std::vector<Chunk> cut;
+    for (size_t q = 0; q < n;) {
+        const size_t end = q < n0 ? n0 : n;  // a chunk ends where its class does
+        int cap = cap_all;
+        while (cap > 2 && (double)cs[q] * cap > typical * (tile_cap * s.dense_cost_ratio)) cap >>= 1;
+        const int m = (int)std::min<size_t>((size_t)cap, end - q);
+        cut.push_back({(int)q, m, cs[q]});
+        q += (size_t)m;
+    }
+    // chunk-major launch order: the most expensive chunk first (its tasks are the longest)
+    std::stable_sort(cut.begin(), cut.end(), [](const Chunk& a, const Chunk& b) { return a.cost > b.cost; });
+    for (const Chunk& k : cut) ch.push_back(k.first), ch.push_back(k.size);
+    plan.nchunks = (int)cut.size();
+    ch.resize(ch.size() + n);
+    int* map = ch.data() + 2 * plan.nchunks;
+    for (int k = 0; k < plan.nchunks; ++k)
+        for (int w = 0; w < ch[2 * k + 1]; ++w) map[ch[2 * k] + w] = (k << 8) | w;
+    plan.union_walk = true;
+    plan.items_per_group = 1;
+    return plan;
+}
+
 }  // namespace emme

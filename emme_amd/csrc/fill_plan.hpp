@@ -50,4 +50,12 @@ struct ChunkPlan {
 ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const unsigned long long* cost, int n_wide,
                       std::vector<int>& chunks);
 
+// The tile fill's omega chunks (assemble_tile.hip: one wave builds the phase block of ONE contour class per interval).
+// `order` (from plan_order) is regrouped -- class by class, each class keeping its order -- and cut into chunks of
+// <= 16 omegas that never mix contour classes (contour_class(host_omega[2 b])): the dense_min_tasks halving on the
+// launch's chunk count, the dense_cost_ratio cut where costs are given.  chunks <- the dense fill's table, (first
+// position, size) per chunk with the most expensive chunk first, and behind it position -> (chunk << 8 | column).
+ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const double* host_omega,
+                           const unsigned long long* cost, std::vector<int>& chunks);
+
 }  // namespace emme

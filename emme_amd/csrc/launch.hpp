@@ -127,6 +127,15 @@ hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheV
 hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
                                       const unsigned int* count, hipStream_t stream);
 
+// ---- table-free tile fill: assemble_tile.hip (electrostatic GK15, plain fills, no node cache) ------
+// act_idx: the launch's omegas; chunks: int2 (first position, size <= 16) per chunk, ONE contour class per chunk
+// (plan_tile_chunks), the most expensive chunk first.  Integrals the kernel cannot finish (a full level list, a folded
+// amplitude that is not representable) are queued on the work list: launch_assemble_list without a cache finishes them.
+// stats (nullable): [0] MFMA rounds, [3] tile tasks
+hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
+                                const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
+                                hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

@@ -34,6 +34,7 @@ void options_default(emme_options_t& o) {
     o.lu_spin_limit = 16000000;  // about 4 s
     o.lu_unblocked = 0;
     o.deriv_cached = 0;
+    o.tile_uncached = 0;
 }
 
 void options_env_overrides(emme_options_t& o) {
@@ -68,6 +69,7 @@ void options_env_overrides(emme_options_t& o) {
     geti("EMME_LU_SPIN_LIMIT", o.lu_spin_limit);
     if (std::getenv("EMME_LU_UNBLOCKED")) o.lu_unblocked = 1;
     geti("EMME_DERIV_CACHED", o.deriv_cached);
+    geti("EMME_TILE_UNCACHED", o.tile_uncached);
 }
 
 int options_check(const emme_options_t* o) {
@@ -79,7 +81,8 @@ int options_check(const emme_options_t* o) {
         o->fill > EMME_FILL_LANES || o->wl_min < 1 || (o->union_sel != 1 && o->union_sel != 2 && o->union_sel != 4) ||
         o->union_ipg_few < 1 || o->union_few_chunks < 0 || o->coop_wide_min < -1 || o->dense_min_cols < 1 ||
         o->dense_min_cols > 17 || o->dense_min_tasks < 0 || !(o->dense_cost_ratio > 0.0) || o->lu_split < 0 ||
-        o->lu_split > 16 || o->lu_spin_limit < 1 || o->deriv_cached < 0 || o->deriv_cached > 1) {
+        o->lu_split > 16 || o->lu_spin_limit < 1 || o->deriv_cached < 0 || o->deriv_cached > 1 ||
+        o->tile_uncached < 0 || o->tile_uncached > 1) {
         set_error("emme_options_t: value out of range");
         return EMME_EINVAL;
     }

@@ -95,6 +95,12 @@ typedef struct emme_options {
     int defer_one_group;      /* 1: deferred integrals by one lane group each                            */
     int dense_min_cols;       /* dense fill: omega columns that must need an interval for the MFMA path   */
     int dense_min_tasks;      /* dense fill: chunk capacity is halved while a launch has fewer tile tasks */
+    int tile_uncached;        /* (addition within version 4, in the four bytes that used to pad dense_cost_ratio to its
+                                 alignment: every other field keeps its offset and the size is unchanged)
+                                 1: plain fills of electrostatic GK15 contexts (integration_accuracy >= 1e-9) that have no
+                                 node cache to read build the dense fill's operands in LDS and run on the FP64 matrix
+                                 cores (k_assemble_tile) instead of the omega-lane kernel; 0 (default):
+                                 the omega-lane kernel.  Not a layout option: it may change on a live context   */
     double dense_cost_ratio;  /* dense fill: a chunk ends where an omega costs less than 1/ratio of its first */
     int dense_wide;           /* dense fill, level lists of 128 instead of 64 entries: 0 = for the omegas of a root search
                                  whose lists overflowed in their previous fill, 1 = always (tests)                */
@@ -155,8 +161,11 @@ int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
 /* Kernel family used by the last fill: 0 lanes-are-nodes, 1 omega-lane, 2 HBM node cache
  * (independent lanes), 3 HBM node cache + phase table, union walk, 4 HBM node cache (tiled) +
- * dense fill on the FP64 matrix cores. */
+ * dense fill on the FP64 matrix cores, 5 table-free tile fill on the FP64 matrix cores. */
 int emme_ctx_fill_mode(const emme_ctx_t* ctx);
+/* Integrals the last fill handed to the work list (the cached fills and the tile fill finish them in a second
+ * launch, from scratch); 0 for fills that have no work list.  Synchronises the context's stream.  < 0: an EMME_* code. */
+long long emme_ctx_last_deferred(emme_ctx_t* ctx);
 /* GiB of HBM currently held by the node-record cache (0 if none). */
 double emme_ctx_node_cache_gib(const emme_ctx_t* ctx);
 /* The node cache grows at run time: a fill that had to hand integrals to the from-scratch kernel
