@@ -575,8 +575,8 @@ class Context:
 
     def assemble_derivative(self, omegas, want_intervals=False):
         """M(omega) and the exact M'(omega) of the same quadrature trees, through the uncached kernels
-        (option deriv_cached = 1: through the node cache where the context has the tiled one): returns
-        (M, Mp[, intervals])."""
+        (option deriv_cached = 1: through the node cache where the context has the tiled one; with tile_uncached = 1
+        as well, through the table-free tile fill where there is no cache to read): returns (M, Mp[, intervals])."""
         w = _c128(np.atleast_1d(omegas))
         nb = w.shape[0]
         iv = np.zeros(nb, dtype=np.int64)

@@ -336,16 +336,51 @@ int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     return EMME_OK;
 }
 
+// A derivative request without a node cache that the table-free tile fill serves: the option pair
+// tile_uncached (what the plain fills' policy says for batches without a cache) and deriv_cached (what hands a
+// derivative request the host omegas, costs and feedback, and so lets it follow that policy), under
+// k_assemble_tile's preconditions.  Neither a tiled layout nor a cache budget is asked for.
+bool tile_deriv_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
+    return c->opt.tile_uncached != 0 && c->opt.deriv_cached != 0 && omega_lane && r.d_Md && r.host_omega != nullptr &&
+           c->nm == 1 && c->p.integration_start_points == 15 && c->p.integration_accuracy >= 1e-9;
+}
+
+// the omegas of c->h_actidx through k_assemble_tile_deriv: launch_tile's steps; the integrals handed over get M and M'
+// from the list-driven from-scratch derivative kernel.  last_fill_mode keeps naming the last plain fill.
+int launch_tile_deriv(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
+    const size_t need = (size_t)c->npairs * c->nm * c->h_actidx.size();
+    HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
+    HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int)));
+    const ChunkPlan plan = plan_tile_chunks(shape_of(c), c->h_actidx, r.host_omega, r.cost, c->h_chunks);
+    L.items_per_group = plan.items_per_group;
+    // (make_launch leaves a derivative request on the struct defaults: as in fill_cached's derivative branch)
+    L.skip_lost = r.newton_loop && c->opt.skip_lost != 0;
+    EMME_TRY(stage_lists(c, &c->h_chunks));
+    HIP_TRY(hipMemsetAsync(c->d_tile_count, 0, sizeof(unsigned int), c->stream));
+    c->last_fill_listed = 2;
+    {
+        ScopedSpan s(c, K_ASM);
+        HIP_TRY(launch_assemble_tile_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
+                                           c->d_rounds, c->stream));
+    }
+    {
+        ScopedSpan s(c, K_DEFER);
+        HIP_TRY(launch_assemble_deriv_list(L, c->d_tile_worklist, c->d_tile_count, c->stream));
+    }
+    return EMME_OK;
+}
+
 // without the node cache, plain (L.Md null) or with the exact derivative: batches of wl_min or more items (and
 // the minority pass, whatever its size) go through the omega-lane kernel, which shares the omega-independent node
-// data between items -- or, with the option tile_uncached and where it applies, through the table-free tile fill;
-// smaller ones through the lanes-are-nodes kernel.  last_fill_mode names the plain fills' kernel: a derivative fill
-// leaves it alone.
+// data between items -- or, with the option tile_uncached and where it applies, through the table-free tile fill
+// (a derivative request: with deriv_cached as well, through its derivative form); smaller ones through the
+// lanes-are-nodes kernel.  last_fill_mode names the plain fills' kernel: a derivative fill leaves it alone.
 int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     const FillShape s = shape_of(c);
     const int n_act = (int)c->h_actidx.size(), gw = s.lane_group();
     const bool omega_lane = n_act >= c->opt.wl_min || r.force_uncached;
     if (tile_fill_applies(c, r, omega_lane)) return launch_tile(c, L, r);
+    if (tile_deriv_applies(c, r, omega_lane)) return launch_tile_deriv(c, L, r);
     c->last_fill_listed = 0;
     L.items_per_group = items_per_group_for(s, omega_lane ? (n_act + gw - 1) / gw : r.nbatch);
     if (omega_lane) {

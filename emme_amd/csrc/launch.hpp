@@ -136,6 +136,13 @@ hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* wor
                                 const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                 hipStream_t stream);
 
+// ---- M and the exact dM/domega from the table-free tile fill: assemble_tile_deriv.hip (L.Md set, L.Mold null) ------
+// same lists and chunks (<= 16 omegas, no twin columns); K' comes from a second GEMM on the operands built for K.  The
+// work list is finished by launch_assemble_deriv_list.  stats as above (the K' GEMMs are not counted as rounds)
+hipError_t launch_assemble_tile_deriv(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
+                                      const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
+                                      hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

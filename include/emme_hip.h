@@ -100,7 +100,10 @@ typedef struct emme_options {
                                  1: plain fills of electrostatic GK15 contexts (integration_accuracy >= 1e-9) that have no
                                  node cache to read build the dense fill's operands in LDS and run on the FP64 matrix
                                  cores (k_assemble_tile) instead of the omega-lane kernel; 0 (default):
-                                 the omega-lane kernel.  Not a layout option: it may change on a live context   */
+                                 the omega-lane kernel.  Together with deriv_cached = 1 the same holds for derivative
+                                 fills with host omegas (k_assemble_tile_deriv); alone it leaves them
+                                 on the omega-lane derivative kernel.  Not a layout option: it may change on a live
+                                 context   */
     double dense_cost_ratio;  /* dense fill: a chunk ends where an omega costs less than 1/ratio of its first */
     int dense_wide;           /* dense fill, level lists of 128 instead of 64 entries: 0 = for the omegas of a root search
                                  whose lists overflowed in their previous fill, 1 = always (tests)                */
@@ -112,7 +115,13 @@ typedef struct emme_options {
     int lu_unblocked;         /* 1: the unblocked LU                                                      */
     /* ---- exact derivative (addition within version 4: present if size covers it) ---- */
     int deriv_cached;         /* 1: derivative fills of electrostatic GK15 contexts with the tiled node cache read and
-                                 grow that cache (k_assemble_dense_deriv); 0 (default): always uncached.
+                                 grow that cache (k_assemble_dense_deriv): derivative fills follow the
+                                 plain fills' policy.  Where that policy finds no cache to read (no budget, a cache that
+                                 does not fit, a call below cache_min_batch, the minority contour class of a call) and
+                                 tile_uncached = 1 is set as well, they go through the table-free tile fill
+                                 (k_assemble_tile_deriv, DESIGN.md 12.3: electrostatic GK15, integration_accuracy >= 1e-9,
+                                 at least wl_min omegas; no tiled layout or cache budget needed); alone, such fills keep
+                                 the uncached kernels bit for bit.  0 (default): always the uncached vector kernels.
                                  Not a layout option: it may change on a live context                        */
 } emme_options_t;
 
@@ -233,7 +242,10 @@ int emme_solve_roots(emme_ctx_t* ctx, const double* guesses, int n, double tol, 
  * set, and emme_ctx_fill_mode keeps naming the last plain fill.  With the option deriv_cached, a call with host omegas
  * on an electrostatic GK15 context with the tiled cache follows the cache policy of emme_assemble_batch instead: M and
  * M' come from the cached records (k_assemble_dense_deriv), the same interval trees, M and M' within the project's
- * 1e-10 bar of the uncached fill, and the cache may be built or grown.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
+ * 1e-10 bar of the uncached fill, and the cache may be built or grown.  With deriv_cached and tile_uncached
+ * both set, what that policy leaves without a cache goes through k_assemble_tile_deriv where k_assemble_tile would serve
+ * the plain fill: M is the plain tile fill's bit for bit, the interval trees are the same, M' is within the same bar, and
+ * emme_ctx_last_deferred reports the integrals handed to the from-scratch list kernel.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
  * integral), and also when an entry of M' is non-finite or beyond the range M is held to: a fill whose M alone the
  * plain fill accepts can then fail. */
 int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nbatch, double* M, double* Mp,
@@ -243,7 +255,8 @@ int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nba
  * at the current omega of the live chains.  The step is the context's iteration_method on (M, M'): trace form
  * domega = -1/tr(M^-1 M'), QR form domega = -1/q.  emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) see the
  * last fill's M per chain afterwards.  Derivative fills count in the emme_profile_t fill counters.  With the option
- * deriv_cached the fills of the search go through the node cache where emme_assemble_derivative_batch's would. */
+ * deriv_cached the fills of the search go through the node cache where emme_assemble_derivative_batch's would, and
+ * with tile_uncached as well through the table-free tile fill (k_assemble_tile_deriv) where there is no cache. */
 int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
                             double* roots, int* iters, int* info, double* iterates);
 /* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton call (dim*dim complex). */
