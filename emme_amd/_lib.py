@@ -103,6 +103,18 @@ class Options(C.Structure):
         ("lu_unblocked", C.c_int),
         ("deriv_cached", C.c_int),
     ]
+    # emme_options_t::dense_stage sits in the four bytes behind deriv_cached that pad the struct to its alignment
+    # (the size is what it was): mirrored as a property on those bytes, so that the declared fields stay as they were
+    _DENSE_STAGE_OFFSET = 108
+
+    @property
+    def dense_stage(self) -> int:
+        return C.c_int.from_buffer(self, self._DENSE_STAGE_OFFSET).value
+
+    @dense_stage.setter
+    def dense_stage(self, v) -> None:
+        C.c_int.from_buffer(self, self._DENSE_STAGE_OFFSET).value = int(v)
+
 
 
 # options every new Context starts from (the tests build their node cache for a handful of omegas)
@@ -523,6 +535,8 @@ class Context:
         o = self.options()
         folded = "true" if o.phase_table else "false"
         if mode == 4:
+            if pts == 15 and not em and not o.dense_stage:
+                return "k_assemble_dense<-1, 15, 1>"  # (without the LDS operand stage)
             return "k_assemble_dense<1, %d, %d>" % (pts, 3 if em else 1)
         if mode == 5:
             return "k_assemble_tile"

@@ -223,12 +223,18 @@ __device__ __forceinline__ double gauss_ratio(int sn) {
     const int q = sn == 0 ? 0 : ((sn + 1) & ~1);  // slots (1,2) (3,4) (5,6) .. are nodes +-x2, +-x4, +-x6 ..
     return PTS == 15 ? kWg15[q >> 1] / kWk15[q] : kWg31[q >> 1] / kWk31[q];
 }
-// the pointer lane k holds (k wave-uniform): two v_readlane, not a bpermute through LDS
+// the pointer lane k holds (k wave-uniform): two v_readlane, not a bpermute through LDS.  It points to GLOBAL memory
+// and comes back as an address-space-1 pointer (as uniform() in linstep_blocked.hip): rebuilt from an integer as a
+// generic one, every load through it is a FLAT load, which counts in lgkmcnt as well as vmcnt and which the
+// compiler can only wait for with a full drain -- the 16 operand loads of an MFMA round then retire together
+// (vmcnt(0)) before the first MFMA instead of one k-step at a time.
 __device__ __forceinline__ const double* lane_ptr(const double* p, int k) {
     const unsigned long long bits = reinterpret_cast<unsigned long long>(p);
     const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bits, k);
     const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bits >> 32), k);
-    return reinterpret_cast<const double*>(((unsigned long long)hi << 32) | lo);
+    typedef const __attribute__((address_space(1))) double GD;
+    GD* g = (GD*)(((unsigned long long)hi << 32) | lo);
+    return (const double*)g;
 }
 
 __device__ __forceinline__ PairConst make_pair_const(const DevParams& P, double eta_i, double eta_j,

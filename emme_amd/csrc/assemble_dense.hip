@@ -271,8 +271,15 @@ struct DenseArgs {
 // moments = 15 COLUMNS (column 3 w + m) of the same GEMM, every (pair, omega, moment) integral decides for itself as
 // before, and the pair's real factor c_nv^m multiplies its sums before the decision (k_assemble_cached_em walks the
 // union of the three moments' trees per lane; here they are three columns of the tile's union).
-template <int LW, int PTS, int NM>
+//
+// STAGE (electrostatic GK15 only: the 16-KB blocks of the others do not fit): the operand blocks come through a stage
+// in LDS that is filled one entry ahead (see stage_issue / look_ahead below); same operands, same arithmetic.  LWS is
+// LW, or -1 for the 64-entry electrostatic GK15 build WITHOUT the stage (option dense_stage = 0): k_assemble_dense<-1, 15, 1>.
+// (The 128-entry build has no registers left for it: 17 spilled with the stage.)
+template <int LWS, int PTS, int NM>
 __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(DenseArgs A) {
+    constexpr int LW = LWS < 0 ? -LWS : LWS;
+    constexpr bool STAGE = LWS == 1 && PTS == 15 && NM == 1;
     constexpr int NS = tile_slots(PTS), KS = NS / 2, GKS = KS / 2;  // node slots, k-steps of K, k-steps that feed G too
     constexpr int TB = tile_block_doubles(PTS), BT = btab_block_doubles(PTS);
     const DevParams& P = A.P;
@@ -445,6 +452,134 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
             if (alive[r]) defer(r, 0, cls, 0ull);
     }
 
+    // slot of interval (d, pth) of contour class cc in the cache and its record block for this tile (CacheGeom::slot,
+    // one subtree per lane: see g_rd above); cslot < 0 or a null buffer: outside the cache
+    auto locate = [&](int d, int cc, unsigned long long pth, int& cslot, unsigned long long& blk, const double*& ebuf) {
+        if (d <= g_dfull) {
+            cslot = (1 << d) - 1 + (int)pth;
+            blk = g_blk_main + (unsigned long long)cslot;
+            ebuf = lane_ptr(cc ? g_ptr1 : g_ptr0, 0);
+        } else {
+            const int sd = (d - g_rd) & 63;
+            const bool hit = g_on && d <= g_dd && d >= g_rd && (pth >> sd) == g_rp;
+            const unsigned long long hb = __ballot(hit);
+            const int k = hb ? __builtin_ctzll(hb) : 0;  // (the first subtree that holds it, as the scalar loop)
+            const int rel = (int)((1u << sd) - 1u) + (int)(unsigned)(pth & ((1ull << sd) - 1ull));
+            cslot = hb ? __builtin_amdgcn_readlane(g_base + rel, k) : -1;
+            const unsigned long long bl = g_blk0 + (unsigned long long)rel;
+            blk = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bl >> 32), k) << 32) |
+                  (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bl, k);
+            ebuf = lane_ptr(cc ? g_ptr1 : g_ptr0, k);
+        }
+    };
+
+    // ---- staged build (STAGE): the operand blocks of an entry -- 8 KB of records, 4 KB of phases -- come through a
+    // 12-KB stage in LDS per wave, written by direct-to-LDS loads (no destination registers) that are issued ONE ENTRY
+    // AHEAD: an entry's blocks travel while its predecessor's products, sums and decisions run, instead of at the head
+    // of its own dependent chain.  The image of a block is its global layout in 16-byte pieces, permuted inside
+    // 128-byte (records) / 256-byte (phases) groups so that the vector round's reads (16 nodes 512 bytes apart: 4-way
+    // bank conflicts; 16 nodes of one column 256 bytes apart: 16-way) spread over the banks; the permutation is applied
+    // to the SOURCE address of the copy, whose destination is lane-linear (wave-uniform base + 16 lane).
+    // place of 16-byte piece c of a record block (node slot c >> 5) / of piece (sn, w) of a phase block in the stage
+    auto stage_rec = [](int c) -> int { return c ^ ((((c >> 5) & 1) << 2) | ((c >> 6) & 1)); };
+    auto stage_phase = [](int sn, int w) -> int { return sn * 16 + (w ^ sn); };
+    auto stage_tag = [](int d, int ent) -> int { return d * 256 + ent; };
+    // s_waitcnt vmcnt(0) / lgkmcnt(0) as the instruction itself (gfx9 encoding: vmcnt in bits 3:0 and 15:14, expcnt
+    // 6:4, lgkmcnt 11:8; the other counters at their maximum): the compiler's own wait insertion takes such a wait
+    // into account -- after one hidden in inline assembly it waits again, vmcnt(0), at the first use of `scale`, and
+    // that wait would retire the copies of the next entry too.  (The empty asm keeps the compiler from moving LDS
+    // reads across.)
+    auto stage_wait_copies = []() {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0x0f70);
+        asm volatile("" ::: "memory");
+    };
+    auto stage_wait_reads = []() {
+        asm volatile("" ::: "memory");
+        __builtin_amdgcn_s_waitcnt(0xc07f);
+        asm volatile("" ::: "memory");
+    };
+    // this lane's piece of an MFMA operand read in the stage, k-step 0 (as loff / eoff in a global block)
+    const int sloff = loff ^ (((rho >> 1) & 1) << 2), seoff = (lane >> 5) * 16 + (col ^ (lane >> 5));
+    double2* stage2 = nullptr;
+    if constexpr (STAGE) {
+        __shared__ __attribute__((aligned(16))) double s_stage[4][TB + BT];
+        stage2 = reinterpret_cast<double2*>(s_stage[wave]);
+    }
+    // what the look-ahead found for entry st_tag (-1: nothing): its slot and block, and whether its blocks were sent
+    // to the stage (an entry outside the cache is located and left alone)
+    int st_tag = -1, st_cslot = -1;
+    unsigned long long st_blk = 0ull;
+    const double* st_ebuf = nullptr;
+    bool st_loaded = false;
+    double st_scale = 0.0;
+    auto stage_issue = [&](const double* ablk, const double* bblk) {
+        // Instruction i moves pieces 64 i .. 64 i + 63, and both permutations stay inside it: piece 64 i + lane comes
+        // from piece 64 i + lane' of the block -- records: stage_rec(64 i + lane) = 64 i + (lane ^ f), f from bit 5 of
+        // the lane and the parity of i; phases: stage_phase(4 j + (lane >> 4), lane & 15) = 64 j + (lane ^ (lane >> 4) ^ 4 j).
+        // The instruction's offset field (< 4 KB) moves source and destination alike; M0 holds the destination's base.
+        // In assembly, not through __builtin_amdgcn_global_load_lds: while a copy the compiler knows of is in flight
+        // it puts s_waitcnt vmcnt(0) in front of LDS accesses it cannot tell from the stage -- here the abs_tol reads
+        // of the first two element slots in the decisions -- and the copies would retire there, a third of the
+        // way through the entry.  Copies it does not know of can only make its own waits longer (they count in
+        // vmcnt, and memory operations retire in order), and there is no load to wait for between a look-ahead and the
+        // next stage_wait_copies().
+        typedef __attribute__((address_space(3))) char LC;
+        const unsigned int rl = (unsigned)lane ^ (((unsigned)lane >> 5) << 2), pl = (unsigned)lane ^ ((unsigned)lane >> 4);
+        const char* ga = (const char*)ablk;
+        const char* gb = (const char*)bblk;
+        const unsigned int ls = (unsigned int)__builtin_amdgcn_readfirstlane((int)(unsigned int)(unsigned long long)(LC*)stage2);
+        auto copy4 = [](const char* s0, const char* s1, const char* s2, const char* s3, unsigned int dst) {
+            unsigned int keep;
+            asm volatile(
+                "s_mov_b32 %0, m0\n\t"
+                "s_mov_b32 m0, %5\n\t"
+                "s_nop 0\n\t"
+                "global_load_lds_dwordx4 %1, off\n\t"
+                "global_load_lds_dwordx4 %2, off offset:1024\n\t"
+                "global_load_lds_dwordx4 %3, off offset:2048\n\t"
+                "global_load_lds_dwordx4 %4, off offset:3072\n\t"
+                "s_mov_b32 m0, %0"
+                : "=&s"(keep)
+                : "v"(s0), "v"(s1), "v"(s2), "v"(s3), "s"(dst)
+                : "memory");
+        };
+        const char* r0 = ga + 16u * rl;           // (i even)
+        const char* r1 = ga + 16u * (rl ^ 1u);    // (i odd)
+        copy4(r0, r1, r0, r1, ls);
+        copy4(r0 + 4096, r1 + 4096, r0 + 4096, r1 + 4096, ls + 4096u);
+        copy4(gb + 16u * pl, gb + 16u * (pl ^ 4u), gb + 16u * (pl ^ 8u), gb + 16u * (pl ^ 12u), ls + 8u * TB);
+    };
+    // The entry that follows entry e of this level in the walk: the next one of the level's list, or -- at its end --
+    // the first of the next level's list, which is fixed as soon as an earlier entry of this level has split.  If
+    // some element needs it, it is located (once: the entry loop takes the result over) and, inside the cache, its
+    // blocks and its scale are sent for.  Whoever is deferred in the meantime only wastes the copy.
+    auto look_ahead = [&](int depth, int e, int n_cur, int n_next) {
+        const bool same = e + 1 < n_cur;
+        if (!same && n_next == 0) return;
+        const int nd = same ? depth : depth + 1, ne = same ? e + 1 : 0;
+        const bool hiw = LW > 1 && ne >= 64;  // (the next level's first entry lives in word 0)
+        const unsigned int wlo = same ? (hiw ? ecur_lo[LW - 1] : ecur_lo[0]) : enext_lo[0];
+        const unsigned int whi = same ? (hiw ? ecur_hi[LW - 1] : ecur_hi[0]) : enext_hi[0];
+        const unsigned int nlo = (unsigned)__builtin_amdgcn_readlane((int)wlo, ne & 63);
+        const unsigned int nhi = (unsigned)__builtin_amdgcn_readlane((int)whi, ne & 63);
+        bool want = false;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const unsigned long long m = same ? (hiw ? mcur[r][LW - 1] : mcur[r][0]) : mnext[r][0];
+            want = want || ((m >> (ne & 63)) & 1ull) != 0ull;
+        }
+        if (__ballot(want) == 0ull) return;
+        const unsigned long long npath = (((unsigned long long)(nhi & 0x3fffffffu)) << 32) | nlo;
+        locate(nd, (int)(nhi >> 30), npath, st_cslot, st_blk, st_ebuf);
+        st_tag = stage_tag(nd, ne);
+        st_loaded = st_cslot >= 0 && st_ebuf != nullptr;
+        if (st_loaded) {
+            stage_issue(st_ebuf + st_blk * TB, A.btab + ((size_t)st_cslot * A.nchunks + chunk) * BT);
+            st_scale = A.scale[st_cslot];
+        }
+    };
+
     for (int depth = 0; n_cur > 0; ++depth) {
         int n_next = 0;
         for (int e = 0; e < n_cur; ++e) {
@@ -459,26 +594,23 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
             for (int r = 0; r < 4; ++r) match[r] = (((LW > 1 && e >= 64 ? mcur[r][LW - 1] : mcur[r][0]) >> (e & 63)) & 1ull) != 0ull;
             const unsigned long long need = __ballot(match[0] || match[1] || match[2] || match[3]);
             if (need == 0ull) continue;  // (its owners were deferred meanwhile)
-            // slot of the interval in the cache and its record block for this tile (CacheGeom::slot, one subtree
-            // per lane: see g_rd above)
+            // slot of the interval in the cache and its record block for this tile: from the look-ahead of the
+            // previous entry where that one located this entry (staged build), else looked up here
             int cslot;
             unsigned long long blk;
             const double* ebuf;
-            if (depth <= g_dfull) {
-                cslot = (1 << depth) - 1 + (int)path;
-                blk = g_blk_main + (unsigned long long)cslot;
-                ebuf = lane_ptr(ccls ? g_ptr1 : g_ptr0, 0);
+            bool staged = false;  // the wave's stage holds (or is receiving) this entry's blocks
+            double scale_staged = 0.0;
+            if constexpr (STAGE) {
+                if (st_tag == stage_tag(depth, e)) {
+                    cslot = st_cslot, blk = st_blk, ebuf = st_ebuf, scale_staged = st_scale;
+                    staged = st_loaded;
+                } else {
+                    locate(depth, ccls, path, cslot, blk, ebuf);
+                }
+                st_tag = -1;
             } else {
-                const int sd = (depth - g_rd) & 63;
-                const bool hit = g_on && depth <= g_dd && depth >= g_rd && (path >> sd) == g_rp;
-                const unsigned long long hb = __ballot(hit);
-                const int k = hb ? __builtin_ctzll(hb) : 0;  // (the first subtree that holds it, as the scalar loop)
-                const int rel = (int)((1u << sd) - 1u) + (int)(unsigned)(path & ((1ull << sd) - 1ull));
-                cslot = hb ? __builtin_amdgcn_readlane(g_base + rel, k) : -1;
-                const unsigned long long bl = g_blk0 + (unsigned long long)rel;
-                blk = ((unsigned long long)(unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bl >> 32), k) << 32) |
-                      (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bl, k);
-                ebuf = lane_ptr(ccls ? g_ptr1 : g_ptr0, k);
+                locate(depth, ccls, path, cslot, blk, ebuf);
             }
             if (cslot < 0 || ebuf == nullptr) {
                 // outside the cache: the integrals that need this interval go, whole, to the cooperative kernel
@@ -494,6 +626,15 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
             unsigned int colmask = (unsigned int)((need | (need >> 16) | (need >> 32) | (need >> 48)) & 0xffffull);
             v4d Kre = {0.0, 0.0, 0.0, 0.0}, Kim = Kre, Gre = Kre, Gim = Kre;
             const bool dense_round = __popc(colmask) >= A.dense_min_cols;
+            // ---- staged build: the operands of this entry leave the stage for registers, then the stage takes the
+            // blocks of the entry that comes next while this one's products, sums and decisions run
+            if constexpr (STAGE) {
+                if (!staged) {  // (nobody looked ahead to this entry: it loads here, exposed, as in the unstaged build)
+                    stage_issue(ablk, bblk);
+                    scale_staged = A.scale[cslot];
+                }
+                stage_wait_copies();  // the stage is complete
+            }
             STAMP(ts1);
 #ifdef EMME_DENSE_STAMPS
             unsigned long long ts1x = ts1;
@@ -509,7 +650,17 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 for (int h = 0; h < KS / 8; ++h) {  // (GK31: two batches of eight k-steps, the Gauss rule in the first)
                     double2 av[8], ev[8];
 #pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) av[ks] = a2[64 * (8 * h + ks) + loff], ev[ks] = b2[32 * (8 * h + ks) + eoff];
+                    for (int ks = 0; ks < 8; ++ks) {
+                        if constexpr (STAGE)
+                            // (stage_rec(64 ks + loff) and stage_phase(2 ks + (lane >> 5), col) with the k-step apart)
+                            av[ks] = stage2[64 * ks + (sloff ^ (ks & 1))], ev[ks] = stage2[TB / 2 + 32 * ks + (seoff ^ (2 * ks))];
+                        else
+                            av[ks] = a2[64 * (8 * h + ks) + loff], ev[ks] = b2[32 * (8 * h + ks) + eoff];
+                    }
+                    if constexpr (STAGE) {
+                        stage_wait_reads();   // the reads are done: the stage is free ..
+                        look_ahead(depth, e, n_cur, n_next);                // .. for the blocks of the entry that comes next
+                    }
 #ifndef EMME_DENSE_NO_SCHED_BARRIER
                     __builtin_amdgcn_sched_barrier(0);  // (the loads stay ahead of the first MFMA whatever else the scheduler weighs)
 #endif
@@ -536,7 +687,11 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
             }
             // ---- every element that owns the interval decides for itself; an entry somebody splits puts its two
             // children on the next level's list
-            const double scale = A.scale[cslot];
+            double scale;
+            if constexpr (STAGE)
+                scale = scale_staged;  // (fetched with the blocks: no global load is waited for while the stage fills)
+            else
+                scale = A.scale[cslot];
             bool split[4] = {false, false, false, false};
             // one decision: sums (kx, ky) / (gx, gy) of the element whose accumulators are slot [r][owner]
             // (gk_split<SqrtSeeded>, assemble_common.hpp, spelled out: the call renames registers in the NM = 1 builds)
@@ -576,10 +731,31 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 unsigned long long mb[4];  // who owns the entry, per element slot
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mb[r] = __ballot(match[r]);
+                // staged build: (Q1, Q0) of this lane's node for its four pairs and E' of the entry's first two columns
+                // leave the stage first; then it takes the next entry's blocks.  (More than two columns -- only with
+                // dense_min_cols > 3 -- read the stage column by column: no look-ahead from such an entry.)
+                double2 sq1[4], sq0[4], sep[2];
+                if constexpr (STAGE) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const int p = rho + 4 * (r ^ ((col >= 8 ? 2 : 0) | ((col >> 2) & 1)));  // (r ^ pmask, below)
+                        sq1[r] = stage2[stage_rec(tile_index(2 * sn, p))];
+                        sq0[r] = stage2[stage_rec(tile_index(2 * sn + 1, p))];
+                    }
+                    const unsigned int rest = colmask & (colmask - 1);
+                    sep[0] = stage2[TB / 2 + stage_phase(sn, __builtin_ctz(colmask))];
+                    sep[1] = stage2[TB / 2 + stage_phase(sn, rest ? __builtin_ctz(rest) : __builtin_ctz(colmask))];
+                    if ((rest & (rest - 1)) == 0u) {
+                        stage_wait_reads();   // the reads are done: the stage is free
+                        look_ahead(depth, e, n_cur, n_next);
+                    }
+                }
+                int ci = 0;  // (staged build) position of the column among the entry's columns
                 while (colmask) {
                     const int c = __builtin_ctz(colmask);
                     colmask &= colmask - 1;
                     ++n_cols;
+                    const int ck = ci++;
                     double mkx = 0.0, mky = 0.0, mgx = 0.0, mgy = 0.0;
                     // (omega of column c: it lives in lane c; c is wave-uniform, so v_readlane, not a bpermute through LDS)
                     auto lane_value = [&](double v) -> double {
@@ -601,13 +777,27 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
 #pragma unroll
                     for (int h = 0; h < NS / 16; ++h) {  // (GK31: a lane takes node slots col and col + 16)
                         const int snh = sn + 16 * h;
-                        const double2 ep = b2[snh * 16 + c];  // E' of the node; BK0 = E', BK1 = omega_c E'
+                        double2 ep;  // E' of the node; BK0 = E', BK1 = omega_c E'
+                        if constexpr (STAGE) {  // (ck is wave-uniform)
+                            if (ck == 0)  // (a third column finds the stage untouched, see above)
+                                ep = sep[0];
+                            else if (ck == 1)
+                                ep = sep[1];
+                            else
+                                ep = stage2[TB / 2 + stage_phase(snh, c)];
+                        } else {
+                            ep = b2[snh * 16 + c];
+                        }
                         const cd bk0 = mk(ep.x, ep.y);
                         const cd bk1 = mk(fma(wcx, ep.x, -(wcy * ep.y)), fma(wcx, ep.y, wcy * ep.x));
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
                             const int p = rho + 4 * (r ^ pmask);
-                            const double4 ra = *reinterpret_cast<const double4*>(a2 + tile_index(2 * snh, p));  // (Q1, Q0): 32 bytes
+                            double4 ra;  // (Q1, Q0): 32 bytes
+                            if constexpr (STAGE)
+                                ra = make_double4(sq1[r].x, sq1[r].y, sq0[r].x, sq0[r].y);
+                            else
+                                ra = *reinterpret_cast<const double4*>(a2 + tile_index(2 * snh, p));
                             const cd q1 = mk(ra.x, ra.y), q0 = mk(ra.z, ra.w);
                             // fk = q1 bk1 + q0 bk0, one multiplication and three FMAs per component
                             const cd fk = mk(fma(q1.x, bk1.x, fma(-q1.y, bk1.y, fma(q0.x, bk0.x, -(q0.y * bk0.y)))),
@@ -734,6 +924,8 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
 #pragma unroll
             for (int q = 0; q < LW; ++q) mcur[r][q] = mnext[r][q], mnext[r][q] = 0ull;
     }
+    // (a copy nobody took -- its entry's owners were all deferred -- must have landed before the wave gives up its LDS)
+    if constexpr (STAGE) stage_wait_copies();
 
     // ---- results (include/solver.h:448-455: mat(i,j) = -kappa W_ij dx, mirrored) ---------------------
     unsigned long long my_intervals = 0;
@@ -949,7 +1141,11 @@ hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& c
     if (A.nchunks > n_wide) {
         A.chunk0 = n_wide;
         A.nch_launch = A.nchunks - n_wide;
-        hipLaunchKernelGGL((k_assemble_dense<1, 15, 1>), dim3((unsigned)(ntg_l * (A.nchunks - n_wide))), dim3(256), 0, stream, A);
+        const dim3 grid((unsigned)(ntg_l * (A.nchunks - n_wide)));
+        if (L.dense_stage)
+            hipLaunchKernelGGL((k_assemble_dense<1, 15, 1>), grid, dim3(256), 0, stream, A);
+        else
+            hipLaunchKernelGGL((k_assemble_dense<-1, 15, 1>), grid, dim3(256), 0, stream, A);
     }
     return hipGetLastError();
 }

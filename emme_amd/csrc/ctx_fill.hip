@@ -55,6 +55,7 @@ AssembleLaunch make_launch(const emme_ctx* c, const FillRequest& r) {
     L.coop_wide_min = c->opt.coop_wide_min;
     L.defer_one_group = c->opt.defer_one_group;
     L.dense_min_cols = c->opt.dense_min_cols;
+    L.dense_stage = c->opt.dense_stage;
     return L;
 }
 

@@ -256,6 +256,7 @@ static const std::vector<IntOpt> kIntOpts = {
     {"lu_unblocked", &emme_options_t::lu_unblocked, 0, kNone, kNone, kNone, kNone, nullptr},
     {"deriv_cached", &emme_options_t::deriv_cached, 0, 0, -1, 1, 2, "EMME_DERIV_CACHED"},
     {"tile_uncached", &emme_options_t::tile_uncached, 0, 0, -1, 1, 2, "EMME_TILE_UNCACHED"},
+    {"dense_stage", &emme_options_t::dense_stage, 1, 0, -1, 1, 2, "EMME_DENSE_STAGE"},
 };
 static const std::vector<DblOpt> kDblOpts = {
     {"node_cache_gb", &emme_options_t::node_cache_gb, 176.0, 0.0, -1e-300, "EMME_NODE_CACHE_GB"},

@@ -41,6 +41,7 @@ struct AssembleLaunch {
     int coop_wide_min = 4096;  // deferred list: length from which the one-wave cooperative kernel takes over (-1 never)
     int defer_one_group = 0;   // deferred integrals by one lane group each
     int dense_min_cols = 3;    // dense fill: columns that must need an interval for the MFMA path
+    int dense_stage = 1;       // dense fill (electrostatic GK15): operands through the LDS stage, fetched one entry ahead
     double* Md = nullptr;      // device or null: exact dM/domega beside M (Mold must be null)
 };
 // What the launchers that read the node cache see of it: its geometry and, per contour class (omi = +1, -1), the

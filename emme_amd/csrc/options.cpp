@@ -35,6 +35,7 @@ void options_default(emme_options_t& o) {
     o.lu_unblocked = 0;
     o.deriv_cached = 0;
     o.tile_uncached = 0;
+    o.dense_stage = 1;
 }
 
 void options_env_overrides(emme_options_t& o) {
@@ -70,6 +71,7 @@ void options_env_overrides(emme_options_t& o) {
     if (std::getenv("EMME_LU_UNBLOCKED")) o.lu_unblocked = 1;
     geti("EMME_DERIV_CACHED", o.deriv_cached);
     geti("EMME_TILE_UNCACHED", o.tile_uncached);
+    geti("EMME_DENSE_STAGE", o.dense_stage);
 }
 
 int options_check(const emme_options_t* o) {
@@ -82,7 +84,7 @@ int options_check(const emme_options_t* o) {
         o->union_ipg_few < 1 || o->union_few_chunks < 0 || o->coop_wide_min < -1 || o->dense_min_cols < 1 ||
         o->dense_min_cols > 17 || o->dense_min_tasks < 0 || !(o->dense_cost_ratio > 0.0) || o->lu_split < 0 ||
         o->lu_split > 16 || o->lu_spin_limit < 1 || o->deriv_cached < 0 || o->deriv_cached > 1 ||
-        o->tile_uncached < 0 || o->tile_uncached > 1) {
+        o->tile_uncached < 0 || o->tile_uncached > 1 || o->dense_stage < 0 || o->dense_stage > 1) {
         set_error("emme_options_t: value out of range");
         return EMME_EINVAL;
     }

@@ -123,6 +123,12 @@ typedef struct emme_options {
                                  at least wl_min omegas; no tiled layout or cache budget needed); alone, such fills keep
                                  the uncached kernels bit for bit.  0 (default): always the uncached vector kernels.
                                  Not a layout option: it may change on a live context                        */
+    int dense_stage;          /* (addition within version 4, in the four bytes that used to pad the struct to its
+                                 alignment: every other field keeps its offset and the size is unchanged)
+                                 1 (default): the dense fill of electrostatic GK15 contexts takes its operand blocks
+                                 through a stage in LDS that is filled one entry ahead; 0: every entry
+                                 loads its own operands.  Same results bit for bit.  Not a layout option: it may
+                                 change on a live context                                                    */
 } emme_options_t;
 
 const char* emme_last_error(void);
