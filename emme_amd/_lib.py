@@ -170,6 +170,8 @@ def load():
     lib.emme_release_pooled_memory.argtypes = []
     lib.emme_release_pooled_memory.restype = None
     lib.emme_ctx_set_stream.argtypes = [P, P]
+    lib.emme_ctx_set_tile_shapes.argtypes = [P, C.c_int]
+    lib.emme_ctx_get_tile_shapes.argtypes = [P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
     lib.emme_ctx_last_deferred.argtypes = [P]
@@ -385,6 +387,10 @@ def release_pooled_memory() -> None:
 
 COMM_ID_BYTES = 128
 
+# emme_ctx_set_tile_shapes (include/emme_hip.h)
+TILE_SHAPES_ES15 = 0
+TILE_SHAPES_ALL = 1
+
 
 def comm_available() -> bool:
     """Can RCCL be bound in this process?  Not a collective (see emme_comm_available)."""
@@ -491,6 +497,17 @@ class Context:
             setattr(o, k, v)
         _check(self.lib.emme_ctx_set_options(self.h, C.byref(o)))
 
+    def set_tile_shapes(self, shapes: int) -> None:
+        """Which shapes the option tile_uncached serves: TILE_SHAPES_ES15 (default: electrostatic GK15 only) or
+        TILE_SHAPES_ALL (electromagnetic and GK31 contexts as well, k_assemble_tile_shape).  From the next call on."""
+        _check(self.lib.emme_ctx_set_tile_shapes(self.h, int(shapes)))
+
+    def tile_shapes(self) -> int:
+        v = self.lib.emme_ctx_get_tile_shapes(self.h)
+        if v < 0:
+            _check(v)
+        return v
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.emme_ctx_destroy(self.h)
@@ -539,6 +556,8 @@ class Context:
                 return "k_assemble_dense<-1, 15, 1>"  # (without the LDS operand stage)
             return "k_assemble_dense<1, %d, %d>" % (pts, 3 if em else 1)
         if mode == 5:
+            if em or pts != 15:
+                return "k_assemble_tile_shape<%d, %d>" % (pts, 3 if em else 1)
             return "k_assemble_tile"
         if mode == 3:
             return "k_assemble_union<15, %d>" % o.union_sel

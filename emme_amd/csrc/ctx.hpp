@@ -89,6 +89,8 @@ struct emme_ctx {
     int last_fill_mode = -1;   // FillMode of the last plain fill (-1: none yet)
     int last_fill_listed = 0;  // work list the last fill reset and used (emme_ctx_last_deferred): 0 none, 1 the cached
                                // fills' (d_worklist), 2 the tile fill's (d_tile_worklist)
+    int tile_shapes = EMME_TILE_SHAPES_ES15;  // shapes the option tile_uncached serves (emme_ctx_set_tile_shapes;
+                               // EMME_TILE_SHAPES read at creation)
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
     // HBM cache of omega-independent node records, per contour class (omi = +1, -1)
     int cache_depth = -1;      // -1: not decided yet, -2: disabled / does not fit, else dfull

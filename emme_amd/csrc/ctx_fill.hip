@@ -306,13 +306,16 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
 
 // A plain request without a node cache that the table-free tile fill serves (option tile_uncached):
 // k_assemble_tile exists for electrostatic GK15 under the dense fill's accuracy precondition (the GEMM cannot apply
-// the safe_exp clamp), and its chunks need the omegas' host values (one contour class per chunk).
+// the safe_exp clamp), and its chunks need the omegas' host values (one contour class per chunk).  Electromagnetic and
+// GK31 contexts have k_assemble_tile_shape under the same preconditions once the context's tile shapes
+// are EMME_TILE_SHAPES_ALL (emme_ctx_set_tile_shapes).
+bool tile_shape_is_es15(const emme_ctx* c) { return c->nm == 1 && c->p.integration_start_points == 15; }
 bool tile_fill_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
-    return c->opt.tile_uncached != 0 && omega_lane && !r.d_Md && r.host_omega != nullptr && c->nm == 1 &&
-           c->p.integration_start_points == 15 && c->p.integration_accuracy >= 1e-9;
+    return c->opt.tile_uncached != 0 && omega_lane && !r.d_Md && r.host_omega != nullptr &&
+           (tile_shape_is_es15(c) || c->tile_shapes == EMME_TILE_SHAPES_ALL) && c->p.integration_accuracy >= 1e-9;
 }
 
-// the omegas of c->h_actidx through k_assemble_tile: chunk plan, lists to the device, the kernel, then the integrals it
+// the omegas of c->h_actidx through k_assemble_tile (or, by shape, k_assemble_tile_shape): chunk plan, lists to the device, the kernel, then the integrals it
 // handed over, from scratch
 int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     // a work list of its own (worst case: every integral of the omegas it fills): see ctx.hpp
@@ -327,8 +330,12 @@ int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     c->last_fill_listed = 2;
     {
         ScopedSpan s(c, K_ASM);
-        HIP_TRY(launch_assemble_tile(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
-                                     c->d_rounds, c->stream));
+        if (tile_shape_is_es15(c))
+            HIP_TRY(launch_assemble_tile(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
+                                         c->d_rounds, c->stream));
+        else
+            HIP_TRY(launch_assemble_tile_shape(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
+                                               plan.nchunks, c->d_rounds, c->stream));
     }
     {
         ScopedSpan s(c, K_DEFER);

@@ -126,7 +126,8 @@ ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const do
     const double typical = (double)std::max<unsigned long long>(sorted[n / 2], 1ull);
     // one wave walks a (16-pair tile, chunk) serially and a launch needs several times more tile tasks than the chip
     // holds waves: the widest chunk shrinks until there are dense_min_tasks of them (plan_chunks)
-    const int tile_cap = 16;
+    // (a chunk is 16 COLUMNS -- 16 omegas, or 5 omegas x 3 moments: plan_chunks)
+    const int tile_cap = 16 / s.nm;
     int cap_all = tile_cap;
     const long ntiles = (s.npairs + 15) / 16;
     auto chunks_at = [&](int cap) { return (long)((n0 + cap - 1) / cap + (n - n0 + cap - 1) / cap); };

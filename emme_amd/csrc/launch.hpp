@@ -137,6 +137,14 @@ hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* wor
                                 const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                 hipStream_t stream);
 
+// ---- the same for electromagnetic and GK31 contexts: assemble_tile_shape.hip (k_assemble_tile_shape<PTS, NM> for
+// (15, 3), (31, 1), (31, 3); hipErrorNotSupported for electrostatic GK15) ------
+// chunks hold <= 16 / nm omegas (column 3 w + m of an electromagnetic chunk); work-list entries are the dense fill's,
+// (b << 32) | (pair nm + moment)
+hipError_t launch_assemble_tile_shape(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
+                                      const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
+                                      hipStream_t stream);
+
 // ---- M and the exact dM/domega from the table-free tile fill: assemble_tile_deriv.hip (L.Md set, L.Mold null) ------
 // same lists and chunks (<= 16 omegas, no twin columns); K' comes from a second GEMM on the operands built for K.  The
 // work list is finished by launch_assemble_deriv_list.  stats as above (the K' GEMMs are not counted as rounds)

@@ -171,6 +171,18 @@ void emme_ctx_destroy(emme_ctx_t* ctx);
  * and reused by the next context (allocating them costs seconds, a parameter sweep creates one
  * context per parameter set); this returns them to the driver. */
 void emme_release_pooled_memory(void);
+/* Which shapes the option tile_uncached serves (additions within version 4, found by symbol lookup).  The table-free
+ * tile fill exists for all four shapes the project fills: k_assemble_tile for electrostatic GK15, and
+ * k_assemble_tile_shape<PTS, NM> for electromagnetic contexts (NM = 3: a chunk is 5 omegas x 3
+ * moments) and the 31-point rule.  With EMME_TILE_SHAPES_ALL, plain fills of such contexts that have no node cache to
+ * read take it under tile_uncached's other preconditions (host omegas, integration_accuracy >= 1e-9, at least wl_min
+ * omegas or the minority pass); their derivative fills stay on the omega-lane derivative kernel.  No effect while
+ * tile_uncached = 0.  Not a layout setting: it may change on a live context and takes effect from the next call.
+ * emme_ctx_fill_mode reports 5 for either kernel. */
+#define EMME_TILE_SHAPES_ES15 0 /* default: tile_uncached serves electrostatic GK15 only */
+#define EMME_TILE_SHAPES_ALL  1 /* tile_uncached serves electromagnetic and GK31 contexts as well */
+int emme_ctx_set_tile_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range */
+int emme_ctx_get_tile_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
 /* Launch everything on this hipStream_t (e.g. torch's current stream). NULL = default. */
 int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
