@@ -347,14 +347,18 @@ int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
 // A derivative request without a node cache that the table-free tile fill serves: the option pair
 // tile_uncached (what the plain fills' policy says for batches without a cache) and deriv_cached (what hands a
 // derivative request the host omegas, costs and feedback, and so lets it follow that policy), under
-// k_assemble_tile's preconditions.  Neither a tiled layout nor a cache budget is asked for.
+// k_assemble_tile's preconditions.  Neither a tiled layout nor a cache budget is asked for.  Derivative fills follow the
+// context's tile shapes as the plain fills do: electromagnetic and GK31 contexts have k_assemble_tile_shape_deriv
+//  once the shapes are EMME_TILE_SHAPES_ALL -- on contexts that have a node cache too, since no
+// derivative request of those shapes reads it (deriv_from_cache).
 bool tile_deriv_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
     return c->opt.tile_uncached != 0 && c->opt.deriv_cached != 0 && omega_lane && r.d_Md && r.host_omega != nullptr &&
-           c->nm == 1 && c->p.integration_start_points == 15 && c->p.integration_accuracy >= 1e-9;
+           (tile_shape_is_es15(c) || c->tile_shapes == EMME_TILE_SHAPES_ALL) && c->p.integration_accuracy >= 1e-9;
 }
 
-// the omegas of c->h_actidx through k_assemble_tile_deriv: launch_tile's steps; the integrals handed over get M and M'
-// from the list-driven from-scratch derivative kernel.  last_fill_mode keeps naming the last plain fill.
+// the omegas of c->h_actidx through k_assemble_tile_deriv (or, by shape, k_assemble_tile_shape_deriv): launch_tile's
+// steps; the integrals handed over get M and M' from the shape's list-driven from-scratch derivative kernel.
+// last_fill_mode keeps naming the last plain fill.
 int launch_tile_deriv(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     const size_t need = (size_t)c->npairs * c->nm * c->h_actidx.size();
     HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
@@ -368,12 +372,19 @@ int launch_tile_deriv(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     c->last_fill_listed = 2;
     {
         ScopedSpan s(c, K_ASM);
-        HIP_TRY(launch_assemble_tile_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
-                                           c->d_rounds, c->stream));
+        if (tile_shape_is_es15(c))
+            HIP_TRY(launch_assemble_tile_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
+                                               plan.nchunks, c->d_rounds, c->stream));
+        else
+            HIP_TRY(launch_assemble_tile_shape_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
+                                                     plan.nchunks, c->d_rounds, c->stream));
     }
     {
         ScopedSpan s(c, K_DEFER);
-        HIP_TRY(launch_assemble_deriv_list(L, c->d_tile_worklist, c->d_tile_count, c->stream));
+        if (tile_shape_is_es15(c))
+            HIP_TRY(launch_assemble_deriv_list(L, c->d_tile_worklist, c->d_tile_count, c->stream));
+        else
+            HIP_TRY(launch_assemble_deriv_list_shape(L, c->d_tile_worklist, c->d_tile_count, c->stream));
     }
     return EMME_OK;
 }
@@ -381,7 +392,8 @@ int launch_tile_deriv(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
 // without the node cache, plain (L.Md null) or with the exact derivative: batches of wl_min or more items (and
 // the minority pass, whatever its size) go through the omega-lane kernel, which shares the omega-independent node
 // data between items -- or, with the option tile_uncached and where it applies, through the table-free tile fill
-// (a derivative request: with deriv_cached as well, through its derivative form); smaller ones through the
+// (a derivative request: with deriv_cached as well, through its derivative form, which follows the context's tile
+// shapes like the plain one); smaller ones through the
 // lanes-are-nodes kernel.  last_fill_mode names the plain fills' kernel: a derivative fill leaves it alone.
 int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     const FillShape s = shape_of(c);

@@ -152,6 +152,18 @@ hipError_t launch_assemble_tile_deriv(const AssembleLaunch& L, unsigned long lon
                                       const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                       hipStream_t stream);
 
+// ---- the same for electromagnetic and GK31 contexts: assemble_tile_shape_deriv.hip (k_assemble_tile_shape_deriv<PTS, NM>
+// for (15, 3), (31, 1), (31, 3); hipErrorInvalidValue for electrostatic GK15, without L.Md or with L.Mold) ------
+// chunks and work-list entries are launch_assemble_tile_shape's; the work list is finished by
+// launch_assemble_deriv_list_shape
+hipError_t launch_assemble_tile_shape_deriv(const AssembleLaunch& L, unsigned long long* worklist,
+                                            unsigned int* worklist_count, const int* act_idx, const void* chunks,
+                                            int nchunks, unsigned long long* stats, hipStream_t stream);
+// the integrals that kernel handed over (work list of batch << 32 | pair nm + moment): M and M' from scratch, a lane
+// group of 16 (GK15) or 32 (GK31) each, every moment's scatter
+hipError_t launch_assemble_deriv_list_shape(const AssembleLaunch& L, const unsigned long long* worklist,
+                                            const unsigned int* count, hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

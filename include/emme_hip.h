@@ -176,7 +176,9 @@ void emme_release_pooled_memory(void);
  * k_assemble_tile_shape<PTS, NM> for electromagnetic contexts (NM = 3: a chunk is 5 omegas x 3
  * moments) and the 31-point rule.  With EMME_TILE_SHAPES_ALL, plain fills of such contexts that have no node cache to
  * read take it under tile_uncached's other preconditions (host omegas, integration_accuracy >= 1e-9, at least wl_min
- * omegas or the minority pass); their derivative fills stay on the omega-lane derivative kernel.  No effect while
+ * omegas or the minority pass).  Derivative fills follow the shapes too: with deriv_cached = 1 as well they take
+ * k_assemble_tile_shape_deriv<PTS, NM>, also on contexts that have a node cache, which no derivative
+ * request of these shapes reads; with deriv_cached = 0 they stay on the omega-lane derivative kernel.  No effect while
  * tile_uncached = 0.  Not a layout setting: it may change on a live context and takes effect from the next call.
  * emme_ctx_fill_mode reports 5 for either kernel. */
 #define EMME_TILE_SHAPES_ES15 0 /* default: tile_uncached serves electrostatic GK15 only */
