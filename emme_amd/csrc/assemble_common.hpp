@@ -1,8 +1,10 @@
 // assemble_common.hpp -- the leaf pieces that the fill kernels share (assemble.hip, assemble_wl.hip,
-// assemble_cached.hip, assemble_dense.hip, assemble_dense_deriv.hip; probe.hip for the tables): the Gauss-Kronrod
+// assemble_cached.hip, assemble_dense.hip, assemble_dense_deriv.hip, the table-free tile fills assemble_tile*.hip
+// through assemble_tile_text.hpp and assemble_tile_shape_text.hpp; probe.hip for the tables): the Gauss-Kronrod
 // tables, the caps, the accept / split rule of the adaptive quadrature, kappa_e, the pair weights, the three ways an
-// entry of M is stored and the small helpers of the dense fills.  The kernel BODIES stay separate texts (DESIGN.md
-// 12): what is here are forceinline leaves that perform the same operations in the same order at every call site.
+// entry of M is stored, the small helpers of the dense fills and the leaves of the tile fills.  The kernel BODIES stay
+// separate texts: what is here are forceinline leaves that perform the same operations in the same
+// order at every call site, and that left the device assembly of every caller unchanged when they moved here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -249,6 +251,61 @@ __device__ __forceinline__ PairConst make_pair_const(const DevParams& P, double 
     pc.c_lam = 0.5 * P.vt / qRd * pc.beta1;
     pc.c_nv = qRd / P.vt;
     return pc;
+}
+
+// one MFMA accumulator: the 4 rows of a 16 x 16 FP64 tile that a lane holds
+typedef double v4d __attribute__((ext_vector_type(4)));
+
+// The interval at bisection depth `depth` with path bits `path` (most significant = first split, 1 = right half), by
+// the reference's bisection arithmetic, so that every abscissa is bit-identical to the CPU's
+__device__ __forceinline__ void interval_bounds_d(int depth, unsigned long long path, double& l, double& r) {
+    l = 0.0;
+    r = M_PI / 2.0;
+    for (int s = depth - 1; s >= 0; --s) {
+        const double mid = (r + l) / 2;
+        if ((path >> s) & 1)
+            l = mid;
+        else
+            r = mid;
+    }
+}
+
+// ---- leaves of the table-free tile fills (assemble_tile_text.hpp, assemble_tile_shape_text.hpp) ----------------------
+// what the lanes of a wave wrote to LDS is visible to every lane of the wave afterwards
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+// a PairConst to and from its LDS row of 8 doubles (the last one padding)
+__device__ __forceinline__ void pair_const_to_row(double* row, const PairConst& pc) {
+    row[0] = pc.de, row[1] = pc.beta1, row[2] = pc.s, row[3] = pc.inv_s;
+    row[4] = pc.bsum, row[5] = pc.c_lam, row[6] = pc.c_nv, row[7] = 0.0;
+}
+__device__ __forceinline__ PairConst pair_const_of_row(const double* row) {
+    PairConst pc;
+    pc.de = row[0], pc.beta1 = row[1], pc.s = row[2], pc.inv_s = row[3];
+    pc.bsum = row[4], pc.c_lam = row[5], pc.c_nv = row[6];
+    return pc;
+}
+// One element of a phase block by k_btab's rule: wk exp(T omega), with T, omega and wk read from *tp, *omp and *wkp
+// HERE and in this order (passed by value the surrounding kernels change).  exp(T omega) beyond 1e304 gives NaN: an
+// integral of this omega that uses the node ends non-finite and flags its matrix (EMME_ENUMERIC) instead of dropping
+// the term; a NaN omega goes through and poisons its own column only.
+__device__ __forceinline__ cd weighted_phase(const double2* tp, const double2* omp, const double* wkp) {
+    const double2 t = *tp, omw = *omp;
+    const double ax = fma(t.x, omw.x, -(t.y * omw.y)), ay = fma(t.x, omw.y, t.y * omw.x);
+    cd ev;
+    if (!(ax > 700.0)) {
+        double sa, ca;
+        sincos(ay, &sa, &ca);
+        const double ea = exp(ax);
+        ev = mk(ea * ca, ea * sa);
+    } else {
+        ev = mk(__builtin_nan(""), __builtin_nan(""));
+    }
+    const double wk = *wkp;
+    return mk(wk * ev.x, wk * ev.y);
 }
 
 }  // namespace

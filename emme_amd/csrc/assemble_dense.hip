@@ -38,20 +38,6 @@ namespace emme {
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void interval_bounds_d(int depth, unsigned long long path, double& l, double& r) {
-    l = 0.0;
-    r = M_PI / 2.0;
-    for (int s = depth - 1; s >= 0; --s) {
-        const double mid = (r + l) / 2;
-        if ((path >> s) & 1)
-            l = mid;
-        else
-            r = mid;
-    }
-}
-
 struct TiledCacheArgs {
     DevParams P;
     const double* tab;

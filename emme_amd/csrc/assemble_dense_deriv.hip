@@ -28,8 +28,6 @@ namespace emme {
 
 namespace {
 
-typedef double v4d __attribute__((ext_vector_type(4)));
-
 constexpr int DERIV_CHUNK = 8;  // omegas per chunk: columns c (K) and c + 8 (K')
 
 // Weighted phase tables of one derivative launch: per (interval slot, chunk) a 4-KB block [sn][16] of (re, im)

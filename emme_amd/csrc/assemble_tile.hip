@@ -1,433 +1,5 @@
-// assemble_tile.hip -- the table-free tile fill: the dense (matrix-core) formulation for batches that have no node cache.
-//
-// assemble_dense.hip reads both operands of its small complex GEMMs from HBM: the 8-KB tile block Q[p, 2n] = e^{A0} Q1,
-// Q[p, 2n + 1] = e^{A0} Q0 of 16 pairs and one interval (node cache) and the 4-KB phase block E'[n, w] = wk_n exp(T_n w)
-// (k_btab).  A batch without a cache -- node_cache_gb = 0, a cache that does not fit (npoints 1024), a one-shot call
-// below cache_min_batch, the minority contour class of a call -- went through k_assemble_wl, which shares the node data
-// of a (pair, interval) between 16 omega lanes but still spends one complex exponential per (pair, node, omega).  Here
-// one wave BUILDS both operands of an interval in LDS -- 16 pairs x 15 nodes of node_data for the tile block, 15 nodes x
-// <= 16 omegas of exp for the phase block (T = i t~ depends on the abscissa and the contour sense only) -- and then runs
-// the dense fill's 48 v_mfma_f64_16x16x4_f64 and its per-element decisions.  One wave owns (tile of 16 pairs, chunk of
-// <= 16 omegas of ONE contour class, plan_tile_chunks) = 256 integrals and walks the union of their trees level by level
-// exactly as k_assemble_dense<1, 15, 1> does; the walk, the decisions and the epilogue are that kernel's text, copied
-// (DESIGN.md 12.2).  Only MFMA rounds exist: a column that does not need an interval costs the matrix cores nothing, and
-// pairs that no element needs are not evaluated.
-//
-// Same preconditions as the dense fill (electrostatic, GK15, integration_accuracy >= 1e-9: the GEMM cannot apply the
-// safe_exp clamp per (pair, node, omega)), same rounding-level differences from the reference, same interval sets.
-// An element whose split does not fit the next 64-entry level list, or that meets a (pair, interval) whose folded
-// amplitude is not representable, goes whole to the work list; the host finishes the list from scratch
-// (launch_assemble_list without a cache view).
-#include <hip/hip_runtime.h>
-
-#include "assemble_common.hpp"
-#include "launch.hpp"
-#include "node_cache.hpp"
-
-namespace emme {
-
-namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// (assemble_dense.hip: the reference's bisection arithmetic, so that every abscissa is bit-identical to the CPU's)
-__device__ __forceinline__ void interval_bounds_d(int depth, unsigned long long path, double& l, double& r) {
-    l = 0.0;
-    r = M_PI / 2.0;
-    for (int s = depth - 1; s >= 0; --s) {
-        const double mid = (r + l) / 2;
-        if ((path >> s) & 1)
-            l = mid;
-        else
-            r = mid;
-    }
-}
-
-struct TileArgs {
-    DevParams P;
-    const double* tab;  // eta | g | b
-    const ushort2* pairs;
-    int npairs;
-    unsigned long long* worklist;
-    unsigned int* worklist_count;
-    const int* act_idx;
-    const int2* chunks;  // (first position, size <= 16) of every omega chunk; one contour class per chunk
-    int nchunks;
-    const double2* omega;
-    double2* M;
-    const double2* Mold;
-    double2* Mp;
-    const double2* domega;
-    unsigned long long* intervals;
-    int* status;
-    unsigned long long* stats;  // [0] MFMA rounds, [3] tile tasks
-    int skip_lost;              // columns whose matrix is already flagged (status) are left alone
-};
-
-// LDS of one wave: the two GEMM operands of the current entry and the pair constants of the tile
-struct TileWaveLds {
-    double2 q[TILE_BLOCK / 2];   // tile block: tile_index(2 sn + which, p)
-    double2 e[BTAB_BLOCK / 2];   // phase block: E'[sn][column]
-    double2 t[16];               // T per node slot
-    double wk[16];               // Kronrod weight per node slot (slot 15: 0)
-    double pc[TILE_PAIRS][8];    // PairConst of the tile's pairs
-    double sumx[64][4], sumy[64][4], abstol[64][4];  // per element [lane][r]: accepted pieces, abs_tol of the root
-};
-
-#ifndef EMME_TILE_MIN_WAVES
-#define EMME_TILE_MIN_WAVES 2
-#endif
-
-__global__ __launch_bounds__(256, EMME_TILE_MIN_WAVES) void k_assemble_tile(TileArgs A) {
-    constexpr int KS = 8, GKS = 4;  // k-steps of K, k-steps that feed G too
-    const DevParams& P = A.P;
-    const int N = P.N, dim = P.dim;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, rho = lane >> 4;
-    // chunk-major, the most expensive chunk first (plan_tile_chunks): its tasks are the longest and all start at once
-    const int ntiles = (A.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
-    const int ntg = (ntiles + 3) / 4;  // tile groups: 4 tiles (one per wave) per workgroup
-    const int chunk = blockIdx.x / ntg;
-    const int tile = (blockIdx.x - chunk * ntg) * 4 + wave;
-    // Counters leave the workgroup once: its waves add them up in LDS and the last one to finish carries the sums to
-    // memory (assemble_dense.hip).
-    __shared__ unsigned long long s_iv[16];
-    __shared__ unsigned int s_st[4];
-    __shared__ int s_arrived;
-    __shared__ TileWaveLds s_w[4];
-    if (threadIdx.x < 16) s_iv[threadIdx.x] = 0ull;
-    if (threadIdx.x < 4) s_st[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) s_arrived = 0;
-    __syncthreads();
-    if (tile >= ntiles) return;
-    const int waves_here = min(4, ntiles - (tile - wave));  // waves of this workgroup that own a tile
-    TileWaveLds& W = s_w[wave];
-
-    const int2 ch = A.chunks[chunk];
-    const bool in_chunk = col < ch.y;
-    const int wpos = ch.x + (in_chunk ? col : 0);
-    const int b = A.act_idx[wpos];
-    const double2 omw = A.omega[b];  // this lane's column omega
-    const int cls = -copysign(1.0, omw.x) > 0.0 ? 0 : 1;
-    // the chunk's contour class is its first column's; a column of the other class (the planner never makes one)
-    // is not filled and flags its matrix
-    const int ccls = __builtin_amdgcn_readfirstlane(cls);
-    const bool wrong_class = in_chunk && cls != ccls;
-    if (wrong_class) A.status[b] = 1;
-    // A matrix that already holds a non-finite integral is lost: nobody works on it any more (assemble_dense.hip)
-    const bool has_w = in_chunk && !wrong_class && !(A.skip_lost && A.status[b] != 0);
-    const double omi = ccls == 0 ? 1.0 : -1.0;  // -copysign(1, Re omega)
-    auto store = [&](int r, int c, cd v, cd rdw) {
-        const size_t idx = (size_t)b * dim * dim + (size_t)r * dim + c;
-        store_entry_secant(A.M, A.Mold, A.Mp, rdw, idx, v);
-    };
-    if (tile == 0 && has_w) {  // diagonal (include/solver.h:442-443)
-        const cd rdw0 = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
-        for (int i = rho; i < N; i += 4) store(i, i, mk(P.diag_a, 0.0), rdw0);
-    }
-
-    // ---- what does not change during the task: the pair constants of the tile's 16 pairs, the node weights ----
-    const GkLane gk = gk_lane<15>(col);            // build phase: lane = (pair row rho, node lane col)
-    const int sn = slotnode_of_lane_t<15>(col);    // its node slot (Gauss nodes first, slot 15 padding)
-    if (lane < 16) {
-        const int pidx = tile * TILE_PAIRS + lane;
-        const ushort2 ij = A.pairs[pidx < A.npairs ? pidx : 0];
-        const int i = ij.x, j = ij.y;
-        const PairConst pc = make_pair_const(P, A.tab[i], A.tab[j], A.tab[2 * N + i], A.tab[2 * N + j], A.tab[N + i] - A.tab[N + j]);
-        W.pc[lane][0] = pc.de, W.pc[lane][1] = pc.beta1, W.pc[lane][2] = pc.s, W.pc[lane][3] = pc.inv_s;
-        W.pc[lane][4] = pc.bsum, W.pc[lane][5] = pc.c_lam, W.pc[lane][6] = pc.c_nv, W.pc[lane][7] = 0.0;
-        W.wk[sn] = gk.wk;  // (lane 15 is the padding lane: weight 0 into slot 15)
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-    const double inv_scale = 2. / (M_PI / 2.0);
-    // (wg / wk) of this lane's rows as MFMA A operand (row 4 ks + (lane >> 4), ks < 4)
-    double grat[GKS];
-#pragma unroll
-    for (int ks = 0; ks < GKS; ++ks) grat[ks] = gauss_ratio<15>((4 * ks + (lane >> 4)) >> 1);
-    const int loff = tile_index(lane >> 4, lane & 15);  // this lane's element of an MFMA operand load, k-step 0
-    const int eoff = (lane >> 5) * 16 + (lane & 15);    // the same for the phase block: node 2 ks + (rho >> 1)
-    // ---- the wave's 256 integrals: element r of this lane = (pair tile*16 + rho + 4 r, omega col) -----
-    unsigned long long mcur[4], mnext[4];  // entries of the current / next level this element needs
-    // (sums and tolerances live in LDS, touched only by their owner lane: 24 vector registers less across node_data)
-    double* const sumx = W.sumx[lane];
-    double* const sumy = W.sumy[lane];
-    double* const abstol = W.abstol[lane];
-    int count[4];
-    bool deferred[4], alive[4];
-    // level lists: entry e of a level = its path in lane e of (E_lo, E_hi)
-    unsigned int ecur_lo = 0, ecur_hi = 0, enext_lo = 0, enext_hi = 0;
-    int n_cur = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int pidx = tile * TILE_PAIRS + rho + 4 * r;
-        alive[r] = has_w && pidx < A.npairs;
-        mcur[r] = alive[r] ? 1ull : 0ull, mnext[r] = 0ull;  // level 0: the root interval
-        abstol[r] = 0.0, sumx[r] = 0.0, sumy[r] = 0.0, count[r] = 0, deferred[r] = false;
-    }
-    if (__ballot(has_w) != 0ull) n_cur = 1;
-    unsigned int n_dense = 0;
-    int bad = 0;
-
-    // (no record of the interval an element left at: there is no cache to grow around it)
-    auto defer = [&](int r) {
-        const unsigned int slot = atomicAdd(A.worklist_count, 1u);
-        A.worklist[slot] = ((unsigned long long)b << 32) | (unsigned int)(tile * TILE_PAIRS + rho + 4 * r);
-        deferred[r] = true, alive[r] = false;
-        mcur[r] = 0ull, mnext[r] = 0ull;
-    };
-
-    for (int depth = 0; n_cur > 0; ++depth) {
-        int n_next = 0;
-        for (int e = 0; e < n_cur; ++e) {
-            // (entry e: lane e of the list -- e is wave-uniform)
-            const unsigned int elo = (unsigned)__builtin_amdgcn_readlane((int)ecur_lo, e);
-            const unsigned int ehi = (unsigned)__builtin_amdgcn_readlane((int)ecur_hi, e);
-            const unsigned long long path = (((unsigned long long)ehi) << 32) | elo;
-            bool match[4];
-            unsigned long long mb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) match[r] = ((mcur[r] >> e) & 1ull) != 0ull, mb[r] = __ballot(match[r]);
-            const unsigned long long need = mb[0] | mb[1] | mb[2] | mb[3];
-            if (need == 0ull) continue;  // (its owners were deferred meanwhile)
-            const unsigned int colmask = (unsigned int)((need | (need >> 16) | (need >> 32) | (need >> 48)) & 0xffffull);
-
-            // ---- the interval and this lane's abscissa (k_node_cache_tiled's form) ----
-            double l, rr;
-            interval_bounds_d(depth, path, l, rr);
-            const double mid = (rr + l) / 2, scale = (rr - l) / 2;
-            const double x = __dadd_rn(__dmul_rn(scale, gk.x), mid);
-
-            // ---- tile block: pass r = pairs rho + 4 r, lane = node; a pair that no element needs is not evaluated ----
-            bool have_t = false;
-            cd tn = mk(0.0, 0.0);
-#pragma unroll 1
-            for (int r = 0; r < 4; ++r) {
-                const int p = rho + 4 * r;
-                const unsigned long long mbr = r == 0 ? mb[0] : r == 1 ? mb[1] : r == 2 ? mb[2] : mb[3];
-                const bool wanted = ((mbr >> (lane & 48)) & 0xffffull) != 0ull;  // (uniform over the row of 16 lanes)
-                cd q1 = mk(0.0, 0.0), q0 = mk(0.0, 0.0);
-                bool over = false;
-                if (wanted) {
-                    PairConst pc;
-                    pc.de = W.pc[p][0], pc.beta1 = W.pc[p][1], pc.s = W.pc[p][2], pc.inv_s = W.pc[p][3];
-                    pc.bsum = W.pc[p][4], pc.c_lam = W.pc[p][5], pc.c_nv = W.pc[p][6];
-                    const NodeData d = node_data(x, P, pc, omi, 0);
-                    tn = d.T, have_t = true;
-                    if (col < 15) {
-                        double sa, ca;
-                        sincos(d.A0.y, &sa, &ca);
-                        const double ea = exp(d.A0.x);
-                        const cd ex = mk(ea * ca, ea * sa);
-                        q1 = ex * d.Q1, q0 = ex * d.Q0;
-                        if (!(isfinite(q1.x) && isfinite(q1.y) && isfinite(q0.x) && isfinite(q0.y))) {
-                            // Re A0 << 0: exp(A0) = 0 against an overflowing amplitude -- the reference's clamp makes the
-                            // node contribute exactly 0.  Otherwise the folded amplitude is not representable: the
-                            // (pair, interval) is POISONED (k_node_cache_tiled)
-                            over = d.A0.x > -700.0;
-                            q1 = mk(0.0, 0.0), q0 = mk(0.0, 0.0);
-                        }
-                    }
-                }
-                // poisoned (pair, interval): its records are zeroed (the GEMM of the tile's other pairs stays finite) and
-                // every element of the pair that needs the interval goes to the work list
-                const bool poisoned = ((__ballot(over) >> (lane & 48)) & 0xffffull) != 0ull;
-                if (poisoned) q1 = mk(0.0, 0.0), q0 = mk(0.0, 0.0);
-                W.q[tile_index(2 * sn, p)] = make_double2(q1.x, q1.y);
-                W.q[tile_index(2 * sn + 1, p)] = make_double2(q0.x, q0.y);
-                if (poisoned) {
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (q == r && match[q]) defer(q), match[q] = false;
-                }
-            }
-            // T of the node slots: pair-independent, the same bits in every row that evaluated a pair
-            if (have_t) W.t[sn] = make_double2(tn.x, tn.y);
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-            // ---- phase block: lane = (slots rho, rho + 4, rho + 8, rho + 12; column col), k_btab's rule ----
-            const bool col_on = has_w && ((colmask >> col) & 1u) != 0u;
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {
-                const int s = rho + 4 * k;
-                cd bv = mk(0.0, 0.0);
-                if (col_on && s < 15) {
-                    const double2 t = W.t[s];
-                    const double ax = fma(t.x, omw.x, -(t.y * omw.y)), ay = fma(t.x, omw.y, t.y * omw.x);
-                    cd ev;
-                    if (!(ax > 700.0)) {  // (a NaN omega goes through and poisons its own column only)
-                        double sa, ca;
-                        sincos(ay, &sa, &ca);
-                        const double ea = exp(ax);
-                        ev = mk(ea * ca, ea * sa);
-                    } else {
-                        // exp(T omega) beyond 1e304: NaN -- an integral of this omega that uses the node ends non-finite
-                        // and flags its matrix (EMME_ENUMERIC) instead of dropping the term
-                        ev = mk(__builtin_nan(""), __builtin_nan(""));
-                    }
-                    const double wk = W.wk[s];
-                    bv = mk(wk * ev.x, wk * ev.y);
-                }
-                W.e[s * 16 + col] = make_double2(bv.x, bv.y);
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-            // ---- the two GEMMs (assemble_dense.hip: dense round) ----
-            v4d Kre = {0.0, 0.0, 0.0, 0.0}, Kim = Kre, Gre = Kre, Gim = Kre;
-            {
-                ++n_dense;
-                v4d K2re = {0.0, 0.0, 0.0, 0.0}, K2im = K2re, G2re = K2re, G2im = K2re;
-                const double2* a2 = W.q;
-                const double2* b2 = W.e;
-                double2 av[KS], ev[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) av[ks] = a2[64 * ks + loff], ev[ks] = b2[32 * ks + eoff];
-#pragma unroll
-                for (int ks = 0; ks < KS; ++ks) {
-                    // (B rows 4 ks + rho belong to node 2 ks + (rho >> 1): row rho even = omega E', odd = E')
-                    const double2 a = av[ks], ep = ev[ks];
-                    const double2 bk = (rho & 1) ? ep : make_double2(fma(omw.x, ep.x, -(omw.y * ep.y)), fma(omw.x, ep.y, omw.y * ep.x));
-                    Kre = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bk.x, Kre, 0, 0, 0);
-                    Kim = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bk.y, Kim, 0, 0, 0);
-                    K2re = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, -bk.y, K2re, 0, 0, 0);
-                    K2im = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bk.x, K2im, 0, 0, 0);
-                    if (ks < GKS) {  // G = sum_k (rho_k Q[p][k]) BK[k][w]: the A operand scaled, the same B
-                        const double gx = a.x * grat[ks], gy = a.y * grat[ks];
-                        Gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gx, bk.x, Gre, 0, 0, 0);
-                        Gim = __builtin_amdgcn_mfma_f64_16x16x4f64(gx, bk.y, Gim, 0, 0, 0);
-                        G2re = __builtin_amdgcn_mfma_f64_16x16x4f64(gy, -bk.y, G2re, 0, 0, 0);
-                        G2im = __builtin_amdgcn_mfma_f64_16x16x4f64(gy, bk.x, G2im, 0, 0, 0);
-                    }
-                }
-                Kre += K2re, Kim += K2im, Gre += G2re, Gim += G2im;
-            }
-            // (the operands are in registers: the next entry may overwrite the blocks)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-
-            // ---- every element that owns the interval decides for itself; an entry somebody splits puts its two
-            // children on the next level's list
-            bool split[4] = {false, false, false, false};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (match[r]) {
-                    const int cnt = count[r] + 1;
-                    count[r] = cnt;
-                    bool sp = gk_split<SqrtSeeded>(mk(Kre[r], Kim[r]), mk(Gre[r], Gim[r]), scale, inv_scale, depth, P, abstol[r]);
-                    if (sp && (depth >= EMME_MAX_DEPTH || cnt >= EMME_MAX_INTERVALS)) {
-                        sp = false;
-                        bad = 1;
-                    }
-                    if (!sp) {
-                        sumx[r] += Kre[r] * scale;
-                        sumy[r] += Kim[r] * scale;
-                    }
-                    split[r] = sp;
-                }
-            }
-            if (__ballot(split[0] || split[1] || split[2] || split[3]) != 0ull) {
-                if (n_next + 2 <= 64) {
-                    const unsigned long long c0 = path << 1;
-                    // (values and positions are wave-uniform: a lane-select writes lanes n_next and n_next + 1)
-                    const int nl = n_next;
-                    enext_lo = lane == nl ? (unsigned)c0 : (lane == nl + 1 ? (unsigned)(c0 | 1ull) : enext_lo);
-                    enext_hi = (lane == nl || lane == nl + 1) ? (unsigned)(c0 >> 32) : enext_hi;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (split[r]) mnext[r] |= 3ull << nl;
-                    n_next += 2;
-                } else {
-                    // the next level's list is full: these integrals start over in the list kernel
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (split[r]) defer(r);
-                }
-            }
-        }
-        ecur_lo = enext_lo, ecur_hi = enext_hi;
-        n_cur = n_next;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mcur[r] = mnext[r], mnext[r] = 0ull;
-    }
-
-    // ---- results (include/solver.h:448-455: mat(i,j) = -kappa W_ij dx, mirrored) ---------------------
-    unsigned long long my_intervals = 0;
-    const cd rdw = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int pidx = tile * TILE_PAIRS + rho + 4 * r;
-        if (has_w && pidx < A.npairs && !deferred[r]) {
-            my_intervals += (unsigned long long)count[r];
-            const ushort2 ij = A.pairs[pidx];
-            const int i = ij.x, j = ij.y;
-            const cd kap = mk(P.pref * sumy[r], -(P.pref * sumx[r]));  // -i pref sum, Parameters.cpp:182
-            if (kappa_bad(kap)) bad = 1;
-            const cd v = pair_entry_weight(i, j, N, P.dx) * kap;
-            store(i, j, v, rdw);
-            store(j, i, v, rdw);
-        }
-    }
-    // interval count of this wave's 16 pairs per omega column: the four row lanes of a column, then the
-    // workgroup's sum in LDS
-    my_intervals += __shfl_xor(my_intervals, 16);
-    my_intervals += __shfl_xor(my_intervals, 32);
-    if (has_w) {
-        if (my_intervals && rho == 0) atomicAdd(&s_iv[col], my_intervals);
-        if (bad) A.status[b] = 1;
-    }
-    if (lane == 0) {
-        atomicAdd(&s_st[0], n_dense);
-        atomicAdd(&s_st[3], 1u);
-    }
-    __threadfence_block();
-    int arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&s_arrived, 1) + 1;  // (LDS operations of a wave are performed in order)
-    arrived = __builtin_amdgcn_readfirstlane(arrived);
-    if (arrived == waves_here) {
-        // the last wave of the workgroup: the sums go out (the lanes of row 0 hold the columns' items; every wave of
-        // a workgroup serves the same chunk)
-        __threadfence_block();
-        if (lane < 16 && has_w && A.intervals && s_iv[lane] != 0ull) atomicAdd(&A.intervals[b], s_iv[lane]);
-        if (A.stats && lane < 4) atomicAdd(&A.stats[lane], (unsigned long long)s_st[lane]);
-    }
-}
-
-}  // namespace
-
-hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
-                                const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
-                                hipStream_t stream) {
-    if (L.gk_points != 15 || L.P.dim != L.P.N || L.Md) return hipErrorNotSupported;
-    if (nchunks < 1) return hipSuccess;
-    TileArgs A;
-    A.P = L.P;
-    A.tab = L.tab;
-    A.pairs = (const ushort2*)L.pairs;
-    A.npairs = L.npairs;
-    A.worklist = worklist;
-    A.worklist_count = worklist_count;
-    A.act_idx = act_idx;
-    A.chunks = (const int2*)chunks;
-    A.nchunks = nchunks;
-    A.omega = (const double2*)L.omega;
-    A.M = (double2*)L.M;
-    A.Mold = (const double2*)L.Mold;
-    A.Mp = (double2*)L.Mp;
-    A.domega = (const double2*)L.domega;
-    A.intervals = L.intervals;
-    A.status = L.status;
-    A.stats = stats;
-    A.skip_lost = L.skip_lost;
-    const int ntiles = (L.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
-    const int ntg = (ntiles + 3) / 4;
-    hipLaunchKernelGGL(k_assemble_tile, dim3((unsigned)((long)ntg * nchunks)), dim3(256), 0, stream, A);
-    return hipGetLastError();
-}
-
-}  // namespace emme
+// assemble_tile.hip -- the table-free tile fill of electrostatic GK15 batches that have no node cache: k_assemble_tile
+// and launch_assemble_tile, the plain (M, fused secant) reading of assemble_tile_text.hpp.  Its own translation unit,
+// so that the kernel is compiled from a token stream that holds nothing of the derivative kernel.
+#define EMME_TILE_DERIV 0
+#include "assemble_tile_text.hpp"

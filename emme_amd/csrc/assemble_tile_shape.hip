@@ -1,557 +1,6 @@
-// assemble_tile_shape.hip -- the table-free tile fill for the shapes k_assemble_tile does not serve: electromagnetic
-// contexts (three velocity moments per pair) and the 31-point rule.
-//
-// k_assemble_tile (assemble_tile.hip) builds both GEMM operands of a quadrature interval in LDS and runs the dense
-// fill's MFMA rounds for electrostatic GK15 batches that have no node cache.  k_assemble_tile_shape<PTS, NM> is the same
-// walk for (PTS, NM) = (15, 3), (31, 1) and (31, 3), with the operand shapes of k_assemble_dense<1, PTS, NM>
-// (assemble_dense.hip):
-//   PTS = 31: 32 node slots (15 Gauss nodes, the 16 Kronrod-only ones, one padding slot: slotnode_of_lane_t<31>), a
-//             16-KB tile block and an 8-KB phase block, 16 k-steps of which the first 8 feed G: 96 v_mfma_f64_16x16x4_f64
-//             per entry.  A lane of the build takes two node slots (gk lanes col and col + 16), one after the other.
-//   NM = 3:   a chunk is <= 5 omegas x 3 moments = 15 columns, column 3 w + m (column 15 idle).  The moment factor of
-//             F_m = F_0 (c_nv W)^m has a pair-independent part W^m, which sits in the phase operand (k_btab<PTS, 3>'s
-//             successive products; W = node_w is computed once per node slot and entry), and the pair's real c_nv^m,
-//             which multiplies the element's sums before its decision.  The tile block holds moment-0 amplitudes only.
-// The walk, the zero / poison rules, the decisions and the hand-over are k_assemble_tile's text, the epilogue is
-// k_assemble_dense's, copied; the leaves are assemble_common.hpp's and emme_device.hpp's.  Work-list
-// entries are the dense fill's: (b << 32) | (pair NM + moment); the host finishes the list from scratch
-// (launch_assemble_list without a cache view).
-//
-// LDS per wave: 20 224 bytes for GK15, 33 152 for GK31.  GK15 workgroups have 4 waves as k_assemble_tile's (81 048 bytes,
-// two per CU); GK31 workgroups have 2 (66 456 bytes), so that two of them share a CU's 160 KB and a CU is not held by
-// the slowest of four tiles.
-#include <hip/hip_runtime.h>
-
-#include "assemble_common.hpp"
-#include "launch.hpp"
-#include "node_cache.hpp"
-
-namespace emme {
-
-namespace {
-
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// (assemble_dense.hip: the reference's bisection arithmetic, so that every abscissa is bit-identical to the CPU's)
-__device__ __forceinline__ void interval_bounds_d(int depth, unsigned long long path, double& l, double& r) {
-    l = 0.0;
-    r = M_PI / 2.0;
-    for (int s = depth - 1; s >= 0; --s) {
-        const double mid = (r + l) / 2;
-        if ((path >> s) & 1)
-            l = mid;
-        else
-            r = mid;
-    }
-}
-
-struct TileShapeArgs {
-    DevParams P;
-    const double* tab;  // eta | g | b
-    const ushort2* pairs;
-    int npairs;
-    unsigned long long* worklist;
-    unsigned int* worklist_count;
-    const int* act_idx;
-    const int2* chunks;  // (first position, size <= 16 / NM) of every omega chunk; one contour class per chunk
-    int nchunks;
-    const double2* omega;
-    double2* M;
-    const double2* Mold;
-    double2* Mp;
-    const double2* domega;
-    unsigned long long* intervals;
-    int* status;
-    unsigned long long* stats;  // [0] MFMA rounds, [3] tile tasks
-    int skip_lost;              // columns whose matrix is already flagged (status) are left alone
-};
-
-// LDS of one wave: the two GEMM operands of the current entry and the pair constants of the tile
-template <int PTS>
-struct TileShapeWaveLds {
-    double2 q[tile_block_doubles(PTS) / 2];  // tile block: tile_index(2 sn + which, p)
-    double2 e[btab_block_doubles(PTS) / 2];  // phase block: E'[sn][column]
-    double2 t[tile_slots(PTS)];              // T per node slot
-    double2 w[tile_slots(PTS)];              // W per node slot (electromagnetic)
-    double wk[tile_slots(PTS)];              // Kronrod weight per node slot (padding slot: 0)
-    double2 om[8];                           // omega per position of the chunk (electromagnetic: the phase build's)
-    double pc[TILE_PAIRS][8];                // PairConst of the tile's pairs
-    double sumx[64][4], sumy[64][4], abstol[64][4];  // per element [lane][r]: accepted pieces, abs_tol of the root
-};
-
-// waves (tiles) per workgroup
-__host__ __device__ constexpr int tile_shape_waves(int pts) { return pts == 15 ? 4 : 2; }
-
-template <int PTS, int NM>
-__global__ __launch_bounds__(64 * tile_shape_waves(PTS), PTS == 15 ? 2 : 1) void k_assemble_tile_shape(TileShapeArgs A) {
-    constexpr int NS = tile_slots(PTS), KS = NS / 2, GKS = KS / 2;  // node slots, k-steps of K, k-steps that feed G too
-    constexpr int NH = NS / 16;                                      // node slots a lane of the build takes
-    constexpr int WPG = tile_shape_waves(PTS);
-    constexpr int NW = 16 / NM;                                      // omegas per chunk
-    const DevParams& P = A.P;
-    const int N = P.N, dim = P.dim;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int col = lane & 15, rho = lane >> 4;
-    const int wcol = NM == 1 ? col : col / NM;      // omega position of this lane's column in its chunk
-    const int mom = NM == 1 ? 0 : col - wcol * NM;  // its velocity moment
-    // chunk-major, the most expensive chunk first (plan_tile_chunks): its tasks are the longest and all start at once
-    const int ntiles = (A.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
-    const int ntg = (ntiles + WPG - 1) / WPG;  // tile groups: one tile per wave of a workgroup
-    const int chunk = blockIdx.x / ntg;
-    const int tile = (blockIdx.x - chunk * ntg) * WPG + wave;
-    // Counters leave the workgroup once: its waves add them up in LDS and the last one to finish carries the sums to
-    // memory (assemble_dense.hip).
-    __shared__ unsigned long long s_iv[16];
-    __shared__ unsigned int s_st[4];
-    __shared__ int s_arrived;
-    __shared__ TileShapeWaveLds<PTS> s_w[WPG];
-    if (threadIdx.x < 16) s_iv[threadIdx.x] = 0ull;
-    if (threadIdx.x < 4) s_st[threadIdx.x] = 0u;
-    if (threadIdx.x == 0) s_arrived = 0;
-    __syncthreads();
-    if (tile >= ntiles) return;
-    const int waves_here = min(WPG, ntiles - (tile - wave));  // waves of this workgroup that own a tile
-    TileShapeWaveLds<PTS>& W = s_w[wave];
-
-    const int2 ch = A.chunks[chunk];
-    const bool in_chunk = wcol < ch.y && wcol < NW;
-    const int wpos = ch.x + (in_chunk ? wcol : 0);
-    const int b = A.act_idx[wpos];
-    const double2 omw = A.omega[b];  // this lane's column omega
-    const int cls = -copysign(1.0, omw.x) > 0.0 ? 0 : 1;
-    // the chunk's contour class is its first column's; a column of the other class (the planner never makes one)
-    // is not filled and flags its matrix
-    const int ccls = __builtin_amdgcn_readfirstlane(cls);
-    const bool wrong_class = in_chunk && cls != ccls;
-    if (wrong_class) A.status[b] = 1;
-    // A matrix that already holds a non-finite integral is lost: nobody works on it any more (assemble_dense.hip)
-    const bool has_w = in_chunk && !wrong_class && !(A.skip_lost && A.status[b] != 0);
-    const double omi = ccls == 0 ? 1.0 : -1.0;  // -copysign(1, Re omega)
-    auto store = [&](int r, int c, cd v, cd rdw) {
-        const size_t idx = (size_t)b * dim * dim + (size_t)r * dim + c;
-        store_entry_secant(A.M, A.Mold, A.Mp, rdw, idx, v);
-    };
-    if (tile == 0 && has_w && mom == 0) {  // diagonal (include/solver.h:442-443; electromagnetic: 465-470)
-        const cd rdw0 = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
-        for (int i = rho; i < N; i += 4) {
-            store(i, i, mk(P.diag_a, 0.0), rdw0);
-            if (NM > 1) {
-                store(i, i + N, mk(0.0, 0.0), rdw0);
-                store(i + N, i, mk(0.0, 0.0), rdw0);
-                store(i + N, i + N, mk(P.diag_d * A.tab[2 * N + i], 0.0), rdw0);
-            }
-        }
-    }
-
-    // ---- what does not change during the task: the pair constants of the tile's 16 pairs, the node weights, the
-    // chunk's omegas ----
-    // build phase: lane = (pair row rho, gk lanes col and, GK31, col + 16); their abscissae and node slots
-    const double gx0 = gk_lane<PTS>(col).x, gx1 = gk_lane<PTS>(NH > 1 ? col + 16 : col).x;
-    const int sn0 = slotnode_of_lane_t<PTS>(col), sn1 = slotnode_of_lane_t<PTS>(NH > 1 ? col + 16 : col);
-    if (lane < 16) {
-        const int pidx = tile * TILE_PAIRS + lane;
-        const ushort2 ij = A.pairs[pidx < A.npairs ? pidx : 0];
-        const int i = ij.x, j = ij.y;
-        const PairConst pc = make_pair_const(P, A.tab[i], A.tab[j], A.tab[2 * N + i], A.tab[2 * N + j], A.tab[N + i] - A.tab[N + j]);
-        W.pc[lane][0] = pc.de, W.pc[lane][1] = pc.beta1, W.pc[lane][2] = pc.s, W.pc[lane][3] = pc.inv_s;
-        W.pc[lane][4] = pc.bsum, W.pc[lane][5] = pc.c_lam, W.pc[lane][6] = pc.c_nv, W.pc[lane][7] = 0.0;
-    }
-    if (lane < NS) W.wk[slotnode_of_lane_t<PTS>(lane)] = gk_lane<PTS>(lane).wk;  // (the padding lane: weight 0)
-    if (NM > 1) {
-        if (rho == 0 && mom == 0 && wcol < NW) W.om[wcol] = omw;
-        // (column 15 belongs to no omega: the phase build never writes it)
-#pragma unroll 1
-        for (int s = lane; s < NS; s += 64) W.e[s * 16 + 15] = make_double2(0.0, 0.0);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    // c_nv^m of pair slot q of this tile (1 for electrostatic fills); m is the column's moment
-    auto moment_factor = [&](int q, int m) -> double {
-        if (NM == 1) return 1.0;
-        const double cv = W.pc[q][6];
-        return m == 0 ? 1.0 : (m == 1 ? cv : cv * cv);
-    };
-
-    const double inv_scale = 2. / (M_PI / 2.0);
-    // (wg / wk) of this lane's rows as MFMA A operand (row 4 ks + (lane >> 4), ks < GKS)
-    double grat[GKS];
-#pragma unroll
-    for (int ks = 0; ks < GKS; ++ks) grat[ks] = gauss_ratio<PTS>((4 * ks + (lane >> 4)) >> 1);
-    const int loff = tile_index(lane >> 4, lane & 15);  // this lane's element of an MFMA operand load, k-step 0
-    const int eoff = (lane >> 5) * 16 + (lane & 15);    // the same for the phase block: node 2 ks + (rho >> 1)
-    // ---- the wave's 256 integrals: element r of this lane = (pair tile*16 + rho + 4 r, column col) -----
-    unsigned long long mcur[4], mnext[4];  // entries of the current / next level this element needs
-    // (sums and tolerances live in LDS, touched only by their owner lane)
-    double* const sumx = W.sumx[lane];
-    double* const sumy = W.sumy[lane];
-    double* const abstol = W.abstol[lane];
-    int count[4];
-    bool deferred[4], alive[4];
-    // level lists: entry e of a level = its path in lane e of (E_lo, E_hi)
-    unsigned int ecur_lo = 0, ecur_hi = 0, enext_lo = 0, enext_hi = 0;
-    int n_cur = 0;
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int pidx = tile * TILE_PAIRS + rho + 4 * r;
-        alive[r] = has_w && pidx < A.npairs;
-        mcur[r] = alive[r] ? 1ull : 0ull, mnext[r] = 0ull;  // level 0: the root interval
-        abstol[r] = 0.0, sumx[r] = 0.0, sumy[r] = 0.0, count[r] = 0, deferred[r] = false;
-    }
-    if (__ballot(has_w) != 0ull) n_cur = 1;
-    unsigned int n_dense = 0;
-    int bad = 0;
-
-    // (no record of the interval an element left at: there is no cache to grow around it)
-    auto defer = [&](int r) {
-        const unsigned int slot = atomicAdd(A.worklist_count, 1u);
-        A.worklist[slot] = ((unsigned long long)b << 32) | (unsigned int)((tile * TILE_PAIRS + rho + 4 * r) * NM + mom);
-        deferred[r] = true, alive[r] = false;
-        mcur[r] = 0ull, mnext[r] = 0ull;
-    };
-
-    for (int depth = 0; n_cur > 0; ++depth) {
-        int n_next = 0;
-        for (int e = 0; e < n_cur; ++e) {
-            // (entry e: lane e of the list -- e is wave-uniform)
-            const unsigned int elo = (unsigned)__builtin_amdgcn_readlane((int)ecur_lo, e);
-            const unsigned int ehi = (unsigned)__builtin_amdgcn_readlane((int)ecur_hi, e);
-            const unsigned long long path = (((unsigned long long)ehi) << 32) | elo;
-            bool match[4];
-            unsigned long long mb[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) match[r] = ((mcur[r] >> e) & 1ull) != 0ull, mb[r] = __ballot(match[r]);
-            const unsigned long long need = mb[0] | mb[1] | mb[2] | mb[3];
-            if (need == 0ull) continue;  // (its owners were deferred meanwhile)
-            const unsigned int colmask = (unsigned int)((need | (need >> 16) | (need >> 32) | (need >> 48)) & 0xffffull);
-
-            // ---- the interval (k_node_cache_tiled's form) ----
-            double l, rr;
-            interval_bounds_d(depth, path, l, rr);
-            const double mid = (rr + l) / 2, scale = (rr - l) / 2;
-
-            // ---- moment factor W of the node slots (electromagnetic): pair-independent, once per slot and entry ----
-            if (NM > 1) {
-#pragma unroll 1
-                for (int h = 0; h < NH; ++h) {
-                    if (lane < 16) {
-                        const double x = __dadd_rn(__dmul_rn(scale, h ? gx1 : gx0), mid);
-                        const cd wv = node_w(x, P, omi);
-                        W.w[h ? sn1 : sn0] = make_double2(wv.x, wv.y);
-                    }
-                }
-            }
-
-            // ---- tile block: pass r = pairs rho + 4 r, lane = node(s); a pair that no element needs is not evaluated ----
-#pragma unroll 1
-            for (int r = 0; r < 4; ++r) {
-                const int p = rho + 4 * r;
-                const unsigned long long mbr = r == 0 ? mb[0] : r == 1 ? mb[1] : r == 2 ? mb[2] : mb[3];
-                const bool wanted = ((mbr >> (lane & 48)) & 0xffffull) != 0ull;  // (uniform over the row of 16 lanes)
-                bool over = false;
-#pragma unroll 1
-                for (int h = 0; h < NH; ++h) {
-                    const int sn = h ? sn1 : sn0;
-                    const bool real_node = col + 16 * h < PTS;  // (the last gk lane is the padding lane)
-                    cd q1 = mk(0.0, 0.0), q0 = mk(0.0, 0.0);
-                    if (wanted) {
-                        const double x = __dadd_rn(__dmul_rn(scale, h ? gx1 : gx0), mid);
-                        PairConst pc;
-                        pc.de = W.pc[p][0], pc.beta1 = W.pc[p][1], pc.s = W.pc[p][2], pc.inv_s = W.pc[p][3];
-                        pc.bsum = W.pc[p][4], pc.c_lam = W.pc[p][5], pc.c_nv = W.pc[p][6];
-                        const NodeData d = node_data(x, P, pc, omi, 0);
-                        // T of the node slot: pair-independent, the same bits from every row that evaluates a pair
-                        W.t[sn] = make_double2(d.T.x, d.T.y);
-                        if (real_node) {
-                            double sa, ca;
-                            sincos(d.A0.y, &sa, &ca);
-                            const double ea = exp(d.A0.x);
-                            const cd ex = mk(ea * ca, ea * sa);
-                            q1 = ex * d.Q1, q0 = ex * d.Q0;
-                            if (!(isfinite(q1.x) && isfinite(q1.y) && isfinite(q0.x) && isfinite(q0.y))) {
-                                // Re A0 << 0: exp(A0) = 0 against an overflowing amplitude -- the reference's clamp makes the
-                                // node contribute exactly 0.  Otherwise the folded amplitude is not representable: the
-                                // (pair, interval) is POISONED (k_node_cache_tiled)
-                                over = over || d.A0.x > -700.0;
-                                q1 = mk(0.0, 0.0), q0 = mk(0.0, 0.0);
-                            }
-                        }
-                    }
-                    W.q[tile_index(2 * sn, p)] = make_double2(q1.x, q1.y);
-                    W.q[tile_index(2 * sn + 1, p)] = make_double2(q0.x, q0.y);
-                }
-                // poisoned (pair, interval): its records are zeroed (the GEMM of the tile's other pairs stays finite) and
-                // every element of the pair that needs the interval goes to the work list, whatever its moment
-                const bool poisoned = ((__ballot(over) >> (lane & 48)) & 0xffffull) != 0ull;
-                if (poisoned) {
-#pragma unroll
-                    for (int h = 0; h < NH; ++h) {
-                        const int sn = h ? sn1 : sn0;
-                        W.q[tile_index(2 * sn, p)] = make_double2(0.0, 0.0);
-                        W.q[tile_index(2 * sn + 1, p)] = make_double2(0.0, 0.0);
-                    }
-#pragma unroll
-                    for (int q = 0; q < 4; ++q)
-                        if (q == r && match[q]) defer(q), match[q] = false;
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-            // ---- phase block, k_btab's rule ----
-            if (NM == 1) {
-                // lane = (slots rho, rho + 4, ..; column col)
-                const bool col_on = has_w && ((colmask >> col) & 1u) != 0u;
-#pragma unroll 1
-                for (int k = 0; k < NS / 4; ++k) {
-                    const int s = rho + 4 * k;
-                    cd bv = mk(0.0, 0.0);
-                    if (col_on && s < PTS) {
-                        const double2 t = W.t[s];
-                        const double ax = fma(t.x, omw.x, -(t.y * omw.y)), ay = fma(t.x, omw.y, t.y * omw.x);
-                        cd ev;
-                        if (!(ax > 700.0)) {  // (a NaN omega goes through and poisons its own column only)
-                            double sa, ca;
-                            sincos(ay, &sa, &ca);
-                            const double ea = exp(ax);
-                            ev = mk(ea * ca, ea * sa);
-                        } else {
-                            // exp(T omega) beyond 1e304: NaN -- an integral of this omega that uses the node ends non-finite
-                            // and flags its matrix (EMME_ENUMERIC) instead of dropping the term
-                            ev = mk(__builtin_nan(""), __builtin_nan(""));
-                        }
-                        const double wk = W.wk[s];
-                        bv = mk(wk * ev.x, wk * ev.y);
-                    }
-                    W.e[s * 16 + col] = make_double2(bv.x, bv.y);
-                }
-            } else {
-                // one exponential per (node slot, omega): item = slot * NW + omega position, its three columns
-                // 3 w + m are the successive products with W
-#pragma unroll 1
-                for (int it = lane; it < NW * NS; it += 64) {
-                    const int s = it / NW, w = it - s * NW;
-                    cd bv = mk(0.0, 0.0), wv = mk(0.0, 0.0);
-                    if (((colmask >> (NM * w)) & ((1u << NM) - 1u)) != 0u && s < PTS) {
-                        const double2 t = W.t[s], om = W.om[w];
-                        const double ax = fma(t.x, om.x, -(t.y * om.y)), ay = fma(t.x, om.y, t.y * om.x);
-                        cd ev;
-                        if (!(ax > 700.0)) {  // (a NaN omega goes through and poisons its own columns only)
-                            double sa, ca;
-                            sincos(ay, &sa, &ca);
-                            const double ea = exp(ax);
-                            ev = mk(ea * ca, ea * sa);
-                        } else {
-                            // exp(T omega) beyond 1e304: NaN in this omega's columns only (see above)
-                            ev = mk(__builtin_nan(""), __builtin_nan(""));
-                        }
-                        const double wk = W.wk[s];
-                        bv = mk(wk * ev.x, wk * ev.y);
-                        const double2 w2 = W.w[s];
-                        wv = mk(w2.x, w2.y);
-                    }
-                    W.e[s * 16 + NM * w] = make_double2(bv.x, bv.y);
-#pragma unroll
-                    for (int m = 1; m < NM; ++m) {
-                        bv = bv * wv;
-                        W.e[s * 16 + NM * w + m] = make_double2(bv.x, bv.y);
-                    }
-                }
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-
-            // ---- the two GEMMs (assemble_dense.hip: dense round) ----
-            v4d Kre = {0.0, 0.0, 0.0, 0.0}, Kim = Kre, Gre = Kre, Gim = Kre;
-            {
-                ++n_dense;
-                v4d K2re = {0.0, 0.0, 0.0, 0.0}, K2im = K2re, G2re = K2re, G2im = K2re;
-                const double2* a2 = W.q;
-                const double2* b2 = W.e;
-#pragma unroll
-                for (int h = 0; h < KS / 8; ++h) {  // (GK31: two batches of eight k-steps, the Gauss rule in the first)
-                    double2 av[8], ev[8];
-#pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) av[ks] = a2[64 * (8 * h + ks) + loff], ev[ks] = b2[32 * (8 * h + ks) + eoff];
-#pragma unroll
-                    for (int ks = 0; ks < 8; ++ks) {
-                        // (B rows 4 ks + rho belong to node 2 ks + (rho >> 1): row rho even = omega E', odd = E')
-                        const double2 a = av[ks], ep = ev[ks];
-                        const double2 bk = (rho & 1) ? ep : make_double2(fma(omw.x, ep.x, -(omw.y * ep.y)), fma(omw.x, ep.y, omw.y * ep.x));
-                        Kre = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bk.x, Kre, 0, 0, 0);
-                        Kim = __builtin_amdgcn_mfma_f64_16x16x4f64(a.x, bk.y, Kim, 0, 0, 0);
-                        K2re = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, -bk.y, K2re, 0, 0, 0);
-                        K2im = __builtin_amdgcn_mfma_f64_16x16x4f64(a.y, bk.x, K2im, 0, 0, 0);
-                        if (8 * h + ks < GKS) {  // G = sum_k (rho_k Q[p][k]) BK[k][w]: the A operand scaled, the same B
-                            const double gx = a.x * grat[(8 * h + ks) % GKS], gy = a.y * grat[(8 * h + ks) % GKS];
-                            Gre = __builtin_amdgcn_mfma_f64_16x16x4f64(gx, bk.x, Gre, 0, 0, 0);
-                            Gim = __builtin_amdgcn_mfma_f64_16x16x4f64(gx, bk.y, Gim, 0, 0, 0);
-                            G2re = __builtin_amdgcn_mfma_f64_16x16x4f64(gy, -bk.y, G2re, 0, 0, 0);
-                            G2im = __builtin_amdgcn_mfma_f64_16x16x4f64(gy, bk.x, G2im, 0, 0, 0);
-                        }
-                    }
-                }
-                Kre += K2re, Kim += K2im, Gre += G2re, Gim += G2im;
-            }
-            // (the operands are in registers: the next entry may overwrite the blocks)
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-
-            // ---- every element that owns the interval decides for itself, on its sums times the pair's c_nv^m; an
-            // entry somebody splits puts its two children on the next level's list
-            bool split[4] = {false, false, false, false};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (match[r]) {
-                    const int cnt = count[r] + 1;
-                    count[r] = cnt;
-                    const double cf = moment_factor(rho + 4 * r, mom);
-                    const double kx = NM == 1 ? Kre[r] : Kre[r] * cf, ky = NM == 1 ? Kim[r] : Kim[r] * cf;
-                    const double gx = NM == 1 ? Gre[r] : Gre[r] * cf, gy = NM == 1 ? Gim[r] : Gim[r] * cf;
-                    bool sp = gk_split<SqrtSeeded>(mk(kx, ky), mk(gx, gy), scale, inv_scale, depth, P, abstol[r]);
-                    if (sp && (depth >= EMME_MAX_DEPTH || cnt >= EMME_MAX_INTERVALS)) {
-                        sp = false;
-                        bad = 1;
-                    }
-                    if (!sp) {
-                        sumx[r] += kx * scale;
-                        sumy[r] += ky * scale;
-                    }
-                    split[r] = sp;
-                }
-            }
-            if (__ballot(split[0] || split[1] || split[2] || split[3]) != 0ull) {
-                if (n_next + 2 <= 64) {
-                    const unsigned long long c0 = path << 1;
-                    // (values and positions are wave-uniform: a lane-select writes lanes n_next and n_next + 1)
-                    const int nl = n_next;
-                    enext_lo = lane == nl ? (unsigned)c0 : (lane == nl + 1 ? (unsigned)(c0 | 1ull) : enext_lo);
-                    enext_hi = (lane == nl || lane == nl + 1) ? (unsigned)(c0 >> 32) : enext_hi;
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (split[r]) mnext[r] |= 3ull << nl;
-                    n_next += 2;
-                } else {
-                    // the next level's list is full: these integrals start over in the list kernel
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (split[r]) defer(r);
-                }
-            }
-        }
-        ecur_lo = enext_lo, ecur_hi = enext_hi;
-        n_cur = n_next;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) mcur[r] = mnext[r], mnext[r] = 0ull;
-    }
-
-    // ---- results (include/solver.h:448-455: mat(i,j) = -kappa W_ij dx, mirrored; electromagnetic: 472-509) ---------
-    unsigned long long my_intervals = 0;
-    const cd rdw = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-        const int pidx = tile * TILE_PAIRS + rho + 4 * r;
-        if (has_w && pidx < A.npairs && !deferred[r]) {
-            my_intervals += (unsigned long long)count[r];
-            const ushort2 ij = A.pairs[pidx];
-            const int i = ij.x, j = ij.y;
-            cd kap = mk(P.pref * sumy[r], -(P.pref * sumx[r]));  // -i pref sum, Parameters.cpp:182
-            if (kappa_bad(kap)) bad = 1;
-            if (NM == 1) {
-                const cd v = pair_entry_weight(i, j, N, P.dx) * kap;
-                store(i, j, v, rdw);
-                store(j, i, v, rdw);
-            } else {
-                // blocks A (m = 0), B and its mirrors (m = 1), D (m = 2): include/solver.h:472-509
-                const double de = A.tab[i] - A.tab[j], dg = A.tab[N + i] - A.tab[N + j];
-                kap = kap + kappa_e(mom, P, de, dg, mk(omw.x, omw.y));
-                if (mom == 0) {
-                    const cd v = (-(pair_weight(i, j, N) * P.dx)) * kap;
-                    store(i, j, v, rdw);
-                    store(j, i, v, rdw);
-                } else if (mom == 1) {
-                    const cd v = P.dx * kap;
-                    store(i, j + N, v, rdw);
-                    store(j, i + N, -v, rdw);
-                    store(i + N, j, -v, rdw);
-                    store(j + N, i, v, rdw);
-                } else {
-                    const cd v = P.dx * kap;
-                    store(i + N, j + N, v, rdw);
-                    store(j + N, i + N, v, rdw);
-                }
-            }
-        }
-    }
-    // interval count of this wave's 16 pairs per column: the four row lanes of a column, then the workgroup's sum in
-    // LDS (the three moment columns of an omega add to the same matrix's counter)
-    my_intervals += __shfl_xor(my_intervals, 16);
-    my_intervals += __shfl_xor(my_intervals, 32);
-    if (has_w) {
-        if (my_intervals && rho == 0) atomicAdd(&s_iv[col], my_intervals);
-        if (bad) A.status[b] = 1;
-    }
-    if (lane == 0) {
-        atomicAdd(&s_st[0], n_dense);
-        atomicAdd(&s_st[3], 1u);
-    }
-    __threadfence_block();
-    int arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&s_arrived, 1) + 1;  // (LDS operations of a wave are performed in order)
-    arrived = __builtin_amdgcn_readfirstlane(arrived);
-    if (arrived == waves_here) {
-        // the last wave of the workgroup: the sums go out (the lanes of row 0 hold the columns' items; every wave of
-        // a workgroup serves the same chunk)
-        __threadfence_block();
-        if (lane < 16 && has_w && A.intervals && s_iv[lane] != 0ull) atomicAdd(&A.intervals[b], s_iv[lane]);
-        if (A.stats && lane < 4) atomicAdd(&A.stats[lane], (unsigned long long)s_st[lane]);
-    }
-}
-
-template <int PTS, int NM>
-void launch_shape(const TileShapeArgs& A, int ntiles, hipStream_t stream) {
-    constexpr int WPG = tile_shape_waves(PTS);
-    const int ntg = (ntiles + WPG - 1) / WPG;
-    hipLaunchKernelGGL((k_assemble_tile_shape<PTS, NM>), dim3((unsigned)((long)ntg * A.nchunks)), dim3(64 * WPG), 0, stream, A);
-}
-
-}  // namespace
-
-hipError_t launch_assemble_tile_shape(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
-                                      const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
-                                      hipStream_t stream) {
-    const int nm = L.P.dim == L.P.N ? 1 : 3;
-    if ((L.gk_points != 15 && L.gk_points != 31) || (L.gk_points == 15 && nm == 1) || L.Md) return hipErrorNotSupported;
-    if (nchunks < 1) return hipSuccess;
-    TileShapeArgs A;
-    A.P = L.P;
-    A.tab = L.tab;
-    A.pairs = (const ushort2*)L.pairs;
-    A.npairs = L.npairs;
-    A.worklist = worklist;
-    A.worklist_count = worklist_count;
-    A.act_idx = act_idx;
-    A.chunks = (const int2*)chunks;
-    A.nchunks = nchunks;
-    A.omega = (const double2*)L.omega;
-    A.M = (double2*)L.M;
-    A.Mold = (const double2*)L.Mold;
-    A.Mp = (double2*)L.Mp;
-    A.domega = (const double2*)L.domega;
-    A.intervals = L.intervals;
-    A.status = L.status;
-    A.stats = stats;
-    A.skip_lost = L.skip_lost;
-    const int ntiles = (L.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
-    if (L.gk_points == 15)
-        launch_shape<15, 3>(A, ntiles, stream);
-    else if (nm == 3)
-        launch_shape<31, 3>(A, ntiles, stream);
-    else
-        launch_shape<31, 1>(A, ntiles, stream);
-    return hipGetLastError();
-}
-
-}  // namespace emme
+// assemble_tile_shape.hip -- the table-free tile fill for electromagnetic contexts and the 31-point rule:
+// k_assemble_tile_shape<PTS, NM> and launch_assemble_tile_shape, the plain (M, fused secant) reading of
+// assemble_tile_shape_text.hpp.  Its own translation unit, so that the kernels are compiled from a token stream that holds
+// nothing of the derivative kernels.
+#define EMME_TILE_DERIV 0
+#include "assemble_tile_shape_text.hpp"

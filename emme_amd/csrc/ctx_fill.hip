@@ -304,103 +304,65 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
     return EMME_OK;
 }
 
-// A plain request without a node cache that the table-free tile fill serves (option tile_uncached):
+// A request without a node cache that the table-free tile fill serves (option tile_uncached):
 // k_assemble_tile exists for electrostatic GK15 under the dense fill's accuracy precondition (the GEMM cannot apply
 // the safe_exp clamp), and its chunks need the omegas' host values (one contour class per chunk).  Electromagnetic and
 // GK31 contexts have k_assemble_tile_shape under the same preconditions once the context's tile shapes
 // are EMME_TILE_SHAPES_ALL (emme_ctx_set_tile_shapes).
+// A derivative request asks for the option deriv_cached as well: it is what hands such a request
+// the host omegas, costs and feedback, and so lets it follow the plain fills' policy.  Neither a tiled layout nor a
+// cache budget is asked for, and the tile shapes count on contexts that have a node cache too, since no derivative
+// request of those shapes reads it (deriv_from_cache).
 bool tile_shape_is_es15(const emme_ctx* c) { return c->nm == 1 && c->p.integration_start_points == 15; }
 bool tile_fill_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
-    return c->opt.tile_uncached != 0 && omega_lane && !r.d_Md && r.host_omega != nullptr &&
+    if (r.d_Md && c->opt.deriv_cached == 0) return false;
+    return c->opt.tile_uncached != 0 && omega_lane && r.host_omega != nullptr &&
            (tile_shape_is_es15(c) || c->tile_shapes == EMME_TILE_SHAPES_ALL) && c->p.integration_accuracy >= 1e-9;
 }
 
-// the omegas of c->h_actidx through k_assemble_tile (or, by shape, k_assemble_tile_shape): chunk plan, lists to the device, the kernel, then the integrals it
-// handed over, from scratch
+// the omegas of c->h_actidx through the tile fill: chunk plan, lists to the device, the kernel picked by (derivative
+// request?, shape) -- k_assemble_tile, k_assemble_tile_shape or their _deriv forms -- then the integrals it handed
+// over, from scratch, by the list kernel of the same pick (a derivative request: M and M').  last_fill_mode names the
+// plain fills' kernel: a derivative fill leaves it alone.
 int launch_tile(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
+    const bool deriv = r.d_Md != nullptr, es15 = tile_shape_is_es15(c);
     // a work list of its own (worst case: every integral of the omegas it fills): see ctx.hpp
     const size_t need = (size_t)c->npairs * c->nm * c->h_actidx.size();
     HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int)));
     const ChunkPlan plan = plan_tile_chunks(shape_of(c), c->h_actidx, r.host_omega, r.cost, c->h_chunks);
     L.items_per_group = plan.items_per_group;
-    EMME_TRY(stage_lists(c, &c->h_chunks));
-    HIP_TRY(hipMemsetAsync(c->d_tile_count, 0, sizeof(unsigned int), c->stream));
-    c->last_fill_mode = FILL_TILE;
-    c->last_fill_listed = 2;
-    {
-        ScopedSpan s(c, K_ASM);
-        if (tile_shape_is_es15(c))
-            HIP_TRY(launch_assemble_tile(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks,
-                                         c->d_rounds, c->stream));
-        else
-            HIP_TRY(launch_assemble_tile_shape(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
-                                               plan.nchunks, c->d_rounds, c->stream));
-    }
-    {
-        ScopedSpan s(c, K_DEFER);
-        HIP_TRY(launch_assemble_list(L, c->d_tile_worklist, c->d_tile_count, nullptr, c->folded, c->stream, false));
-    }
-    return EMME_OK;
-}
-
-// A derivative request without a node cache that the table-free tile fill serves: the option pair
-// tile_uncached (what the plain fills' policy says for batches without a cache) and deriv_cached (what hands a
-// derivative request the host omegas, costs and feedback, and so lets it follow that policy), under
-// k_assemble_tile's preconditions.  Neither a tiled layout nor a cache budget is asked for.  Derivative fills follow the
-// context's tile shapes as the plain fills do: electromagnetic and GK31 contexts have k_assemble_tile_shape_deriv
-//  once the shapes are EMME_TILE_SHAPES_ALL -- on contexts that have a node cache too, since no
-// derivative request of those shapes reads it (deriv_from_cache).
-bool tile_deriv_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
-    return c->opt.tile_uncached != 0 && c->opt.deriv_cached != 0 && omega_lane && r.d_Md && r.host_omega != nullptr &&
-           (tile_shape_is_es15(c) || c->tile_shapes == EMME_TILE_SHAPES_ALL) && c->p.integration_accuracy >= 1e-9;
-}
-
-// the omegas of c->h_actidx through k_assemble_tile_deriv (or, by shape, k_assemble_tile_shape_deriv): launch_tile's
-// steps; the integrals handed over get M and M' from the shape's list-driven from-scratch derivative kernel.
-// last_fill_mode keeps naming the last plain fill.
-int launch_tile_deriv(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
-    const size_t need = (size_t)c->npairs * c->nm * c->h_actidx.size();
-    HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
-    HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int)));
-    const ChunkPlan plan = plan_tile_chunks(shape_of(c), c->h_actidx, r.host_omega, r.cost, c->h_chunks);
-    L.items_per_group = plan.items_per_group;
     // (make_launch leaves a derivative request on the struct defaults: as in fill_cached's derivative branch)
-    L.skip_lost = r.newton_loop && c->opt.skip_lost != 0;
+    if (deriv) L.skip_lost = r.newton_loop && c->opt.skip_lost != 0;
     EMME_TRY(stage_lists(c, &c->h_chunks));
     HIP_TRY(hipMemsetAsync(c->d_tile_count, 0, sizeof(unsigned int), c->stream));
+    if (!deriv) c->last_fill_mode = FILL_TILE;
     c->last_fill_listed = 2;
     {
         ScopedSpan s(c, K_ASM);
-        if (tile_shape_is_es15(c))
-            HIP_TRY(launch_assemble_tile_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
-                                               plan.nchunks, c->d_rounds, c->stream));
-        else
-            HIP_TRY(launch_assemble_tile_shape_deriv(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks,
-                                                     plan.nchunks, c->d_rounds, c->stream));
+        const auto kernel = deriv ? (es15 ? launch_assemble_tile_deriv : launch_assemble_tile_shape_deriv)
+                                  : (es15 ? launch_assemble_tile : launch_assemble_tile_shape);
+        HIP_TRY(kernel(L, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_chunks, plan.nchunks, c->d_rounds, c->stream));
     }
-    {
-        ScopedSpan s(c, K_DEFER);
-        if (tile_shape_is_es15(c))
-            HIP_TRY(launch_assemble_deriv_list(L, c->d_tile_worklist, c->d_tile_count, c->stream));
-        else
-            HIP_TRY(launch_assemble_deriv_list_shape(L, c->d_tile_worklist, c->d_tile_count, c->stream));
-    }
+    ScopedSpan s(c, K_DEFER);
+    if (!deriv)
+        HIP_TRY(launch_assemble_list(L, c->d_tile_worklist, c->d_tile_count, nullptr, c->folded, c->stream, false));
+    else if (es15)
+        HIP_TRY(launch_assemble_deriv_list(L, c->d_tile_worklist, c->d_tile_count, c->stream));
+    else
+        HIP_TRY(launch_assemble_deriv_list_shape(L, c->d_tile_worklist, c->d_tile_count, c->stream));
     return EMME_OK;
 }
 
 // without the node cache, plain (L.Md null) or with the exact derivative: batches of wl_min or more items (and
 // the minority pass, whatever its size) go through the omega-lane kernel, which shares the omega-independent node
-// data between items -- or, with the option tile_uncached and where it applies, through the table-free tile fill
-// (a derivative request: with deriv_cached as well, through its derivative form, which follows the context's tile
-// shapes like the plain one); smaller ones through the
+// data between items -- or, where tile_fill_applies, through the table-free tile fill; smaller ones through the
 // lanes-are-nodes kernel.  last_fill_mode names the plain fills' kernel: a derivative fill leaves it alone.
 int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     const FillShape s = shape_of(c);
     const int n_act = (int)c->h_actidx.size(), gw = s.lane_group();
     const bool omega_lane = n_act >= c->opt.wl_min || r.force_uncached;
     if (tile_fill_applies(c, r, omega_lane)) return launch_tile(c, L, r);
-    if (tile_deriv_applies(c, r, omega_lane)) return launch_tile_deriv(c, L, r);
     c->last_fill_listed = 0;
     L.items_per_group = items_per_group_for(s, omega_lane ? (n_act + gw - 1) / gw : r.nbatch);
     if (omega_lane) {

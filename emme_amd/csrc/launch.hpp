@@ -128,7 +128,12 @@ hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheV
 hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
                                       const unsigned int* count, hipStream_t stream);
 
-// ---- table-free tile fill: assemble_tile.hip (electrostatic GK15, plain fills, no node cache) ------
+// ---- table-free tile fill (no node cache).  Two texts, one per shape family, each compiled as a plain and a
+// derivative translation unit: assemble_tile_text.hpp -> assemble_tile.hip, assemble_tile_deriv.hip
+// (electrostatic GK15); assemble_tile_shape_text.hpp -> assemble_tile_shape.hip, assemble_tile_shape_deriv.hip
+// (electromagnetic, GK31).  A plain launcher refuses L.Md with hipErrorNotSupported, a derivative launcher a missing
+// L.Md or a set L.Mold with hipErrorInvalidValue; both answer so to a shape of the other family. ------
+// -- assemble_tile.hip: electrostatic GK15, plain fills --
 // act_idx: the launch's omegas; chunks: int2 (first position, size <= 16) per chunk, ONE contour class per chunk
 // (plan_tile_chunks), the most expensive chunk first.  Integrals the kernel cannot finish (a full level list, a folded
 // amplitude that is not representable) are queued on the work list: launch_assemble_list without a cache finishes them.
@@ -137,23 +142,23 @@ hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* wor
                                 const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                 hipStream_t stream);
 
-// ---- the same for electromagnetic and GK31 contexts: assemble_tile_shape.hip (k_assemble_tile_shape<PTS, NM> for
-// (15, 3), (31, 1), (31, 3); hipErrorNotSupported for electrostatic GK15) ------
+// -- assemble_tile_shape.hip: the same for electromagnetic and GK31 contexts (k_assemble_tile_shape<PTS, NM> for
+// (15, 3), (31, 1), (31, 3); hipErrorNotSupported for electrostatic GK15) --
 // chunks hold <= 16 / nm omegas (column 3 w + m of an electromagnetic chunk); work-list entries are the dense fill's,
 // (b << 32) | (pair nm + moment)
 hipError_t launch_assemble_tile_shape(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
                                       const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                       hipStream_t stream);
 
-// ---- M and the exact dM/domega from the table-free tile fill: assemble_tile_deriv.hip (L.Md set, L.Mold null) ------
+// -- assemble_tile_deriv.hip: M and the exact dM/domega, electrostatic GK15 (L.Md set, L.Mold null) --
 // same lists and chunks (<= 16 omegas, no twin columns); K' comes from a second GEMM on the operands built for K.  The
 // work list is finished by launch_assemble_deriv_list.  stats as above (the K' GEMMs are not counted as rounds)
 hipError_t launch_assemble_tile_deriv(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
                                       const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                       hipStream_t stream);
 
-// ---- the same for electromagnetic and GK31 contexts: assemble_tile_shape_deriv.hip (k_assemble_tile_shape_deriv<PTS, NM>
-// for (15, 3), (31, 1), (31, 3); hipErrorInvalidValue for electrostatic GK15, without L.Md or with L.Mold) ------
+// -- assemble_tile_shape_deriv.hip: the same for electromagnetic and GK31 contexts (k_assemble_tile_shape_deriv<PTS, NM>
+// for (15, 3), (31, 1), (31, 3); hipErrorInvalidValue for electrostatic GK15, without L.Md or with L.Mold) --
 // chunks and work-list entries are launch_assemble_tile_shape's; the work list is finished by
 // launch_assemble_deriv_list_shape
 hipError_t launch_assemble_tile_shape_deriv(const AssembleLaunch& L, unsigned long long* worklist,
