@@ -190,6 +190,13 @@ def load():
     lib.emme_assemble_derivative_batch.argtypes = [P, P, C.c_int, P, P, P]
     lib.emme_solve_roots_newton.argtypes = [P, P, C.c_int, C.c_double, C.c_int, P, P, P, P]
     lib.emme_ctx_get_matrix.argtypes = [P, C.c_int, P]
+    lib.emme_params_same_shape.argtypes = [PP, PP]
+    lib.emme_ctx_bind_param_sets.argtypes = [P, P, C.c_int]
+    lib.emme_ctx_param_sets.argtypes = [P]
+    lib.emme_assemble_sets_batch.argtypes = [P, P, P, C.c_int, P, P, P]
+    lib.emme_solve_roots_sets.argtypes = [P, P, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P]
+    lib.emme_run_json_lockstep.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
+    lib.emme_scan_plan.argtypes = [C.c_char_p, C.c_int, P, P, P, P, C.c_int, P, P, P]
     lib.emme_null_vector.argtypes = [P, C.c_int, P]
     lib.emme_run_json.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
     lib.emme_free.argtypes = [C.c_void_p]
@@ -380,6 +387,48 @@ def run_json(text: str, matrix_dir: str | None = None) -> dict:
         load().emme_free(out)
 
 
+def run_json_lockstep(text: str, matrix_dir: str | None = None) -> dict:
+    """run_json with the independent lines of the scan solved side by side (emme_run_json_lockstep):
+    same output.json."""
+    import json
+    out = C.c_void_p()
+    rc = load().emme_run_json_lockstep(text.encode(), matrix_dir.encode() if matrix_dir else None, C.byref(out))
+    _check(rc)
+    try:
+        return json.loads(C.string_at(out).decode())
+    finally:
+        load().emme_free(out)
+
+
+def scan_plan(text: str) -> dict:
+    """The round plan of run_json_lockstep for an input.json text (host only): per point (axis by axis, each in
+    scan_values order) its axis, index on the axis, round (-1 on a sequential axis) and pred (index of the point it
+    continues from, -1: initial_guess); per axis whether the sequential driver runs it; the number of rounds."""
+    lib = load()
+    na, nr = C.c_int(0), C.c_int(0)
+    n = lib.emme_scan_plan(text.encode(), 0, None, None, None, None, 0, None, C.byref(na), C.byref(nr))
+    if n < 0:
+        _check(n)
+    axis, index, rnd, pred = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(4))
+    seq = np.zeros(max(na.value, 1), dtype=np.int32)
+    n = lib.emme_scan_plan(text.encode(), n, axis.ctypes.data, index.ctypes.data, rnd.ctypes.data, pred.ctypes.data,
+                           na.value, seq.ctypes.data, C.byref(na), C.byref(nr))
+    if n < 0:
+        _check(n)
+    return {"axis": axis[:n].copy(), "index": index[:n].copy(), "round": rnd[:n].copy(), "pred": pred[:n].copy(),
+            "sequential": seq[:na.value].astype(bool), "n_rounds": nr.value}
+
+
+def params_same_shape(a: Params, b: Params) -> bool:
+    """Can b be bound to a context made for a (emme_params_same_shape: npoints, beta_e == 0 alike,
+    integration_start_points, iteration_method)?  last_error() names the first field that differs."""
+    return load().emme_params_same_shape(C.byref(a), C.byref(b)) == 0
+
+
+def last_error() -> str:
+    return load().emme_last_error().decode()
+
+
 def release_pooled_memory() -> None:
     """Give the node-cache buffers kept from destroyed contexts back to the driver."""
     load().emme_release_pooled_memory()
@@ -533,9 +582,12 @@ class Context:
                     3: "k_assemble_union (HBM node cache + phase table)",
                     4: "k_assemble_dense (tiled HBM node cache + weighted phase tables, FP64 matrix cores)",
                     5: "k_assemble_tile (table-free tile fill, FP64 matrix cores)"}
+    # fill mode 6 (emme_assemble_sets_batch / emme_solve_roots_sets): not a kernel family of the plain fills above
+    SETS_FILL_KERNEL = "k_assemble_sets (lanes=nodes, a parameter set per item)"
 
     def fill_kernel(self) -> str:
-        return self.FILL_KERNELS.get(self.lib.emme_ctx_fill_mode(self.h), "none yet")
+        mode = self.lib.emme_ctx_fill_mode(self.h)
+        return self.SETS_FILL_KERNEL if mode == 6 else self.FILL_KERNELS.get(mode, "none yet")
 
     def last_deferred(self) -> int:
         """Integrals the last fill handed to its work list (finished from scratch by a second launch)."""
@@ -565,6 +617,8 @@ class Context:
             return f"k_assemble_cached_em<{pts}, {folded}>" if em else f"k_assemble_cached<{pts}, {folded}>"
         if mode == 1:
             return f"k_assemble_wl<{pts}>"
+        if mode == 6:
+            return f"k_assemble_sets<{pts}>"
         return f"k_assemble<{pts}, false>"
 
     def node_cache_gib(self) -> float:
@@ -694,6 +748,54 @@ class Context:
         _check(self.lib.emme_solve_roots_newton(self.h, g.ctypes.data, n, tol, step_limit, roots.ctypes.data,
                                                 iters.ctypes.data, info.ctypes.data,
                                                 its.ctypes.data if want_iterates else None))
+        return (roots, iters, info, its) if want_iterates else (roots, iters, info)
+
+    # ---- parameter sets: many sets on one context ----
+    def bind_param_sets(self, sets) -> None:
+        """Bind parameter sets (a list of Params of this context's shape, params_same_shape) to the context; an empty
+        list unbinds.  Items of assemble_sets / solve_roots_sets name them by position."""
+        sets = list(sets)
+        arr = (Params * max(len(sets), 1))(*sets)
+        _check(self.lib.emme_ctx_bind_param_sets(self.h, C.cast(arr, C.c_void_p), len(sets)))
+
+    def param_sets(self) -> int:
+        return self.lib.emme_ctx_param_sets(self.h)
+
+    def assemble_sets(self, set, omegas, want_derivative=False, want_intervals=False):
+        """M(omega_b) of the bound parameter set set[b], one launch for the batch: returns M[, Mp][, intervals]
+        (Mp: the exact dM/domega of the same quadrature trees)."""
+        w = _c128(np.atleast_1d(omegas))
+        nb = w.shape[0]
+        st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+        if st.shape[0] != nb:
+            raise ValueError("set needs one entry per omega")
+        iv = np.zeros(nb, dtype=np.int64)
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if want_derivative else None
+        _check(self.lib.emme_assemble_sets_batch(self.h, st.ctypes.data, w.ctypes.data, nb, M.ctypes.data,
+                                                 Mp.ctypes.data if want_derivative else None, iv.ctypes.data))
+        out = (M, Mp) if want_derivative else (M,)
+        if want_intervals:
+            out = out + (iv,)
+        return out[0] if len(out) == 1 else out
+
+    def solve_roots_sets(self, set, guesses, exact=False, tol=None, step_limit=None, want_iterates=False):
+        """solve_roots (exact=False) or solve_roots_newton (exact=True) with chain b on the bound parameter set
+        set[b]; tol and step_limit (default: this context's own parameters) hold for every chain."""
+        g = _c128(np.atleast_1d(guesses))
+        n = g.shape[0]
+        st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+        if st.shape[0] != n:
+            raise ValueError("set needs one entry per guess")
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros(n, dtype=np.complex128)
+        iters = np.zeros(n, dtype=np.int32)
+        info = np.zeros(n, dtype=np.int32)
+        its = np.zeros((n, step_limit + 1), dtype=np.complex128) if want_iterates else None
+        _check(self.lib.emme_solve_roots_sets(self.h, st.ctypes.data, g.ctypes.data, n, int(bool(exact)), tol, step_limit,
+                                              roots.ctypes.data, iters.ctypes.data, info.ctypes.data,
+                                              its.ctypes.data if want_iterates else None))
         return (roots, iters, info, its) if want_iterates else (roots, iters, info)
 
     def null_vectors(self, M=None, nbatch=None):

@@ -1,0 +1,5 @@
+// assemble_sets_deriv.hip -- M(omega_b) and the exact dM/domega for batch items that each carry their own parameter
+// set: k_assemble_sets_deriv and launch_assemble_sets_deriv, the derivative reading of
+// assemble_sets_text.hpp.  Its own translation unit, as assemble_sets.hip.
+#define EMME_SETS_DERIV 1
+#include "assemble_sets_text.hpp"

@@ -48,7 +48,7 @@ void set_error(const std::string& msg);
 enum Kind { K_ASM = 0, K_LIN = 1, K_OTHER = 2, K_DEFER = 3, K_CACHE = 4, K_NULL = 5 };
 
 // kernel family of a plain fill, as emme_ctx_fill_mode reports it (include/emme_hip.h)
-enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4, FILL_TILE = 5 };
+enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4, FILL_TILE = 5, FILL_SETS = 6 };
 
 // HBM node cache of one contour class (omi = +1, -1)
 struct NodeCacheClass {
@@ -77,6 +77,11 @@ struct emme_ctx {
     int N = 0, dim = 0, nm = 1, npairs = 0;
     DeviceBuffer<double> d_tab;
     DeviceBuffer<ushort2> d_pairs;
+    // parameter sets bound to the context (emme_ctx_bind_param_sets): each has the shape of `p`
+    std::vector<emme_params_t> sets;   // host copy
+    DeviceBuffer<DevParams> d_sets;    // the kernels' scalars, one per set
+    DeviceBuffer<double> d_set_tabs;   // eta | g | b of every set, 3N doubles each
+    DeviceBuffer<int> d_set;           // the set of every batch item of the current call
     // batch scratch
     DeviceBuffer<double> d_omega, d_domega, d_tr;
     DeviceBuffer<int> d_active, d_iters, d_info, d_status;
@@ -186,6 +191,8 @@ struct FillRequest {
     const unsigned long long* cost = nullptr;  // per item (interval count of its previous fill): orders the omegas
     bool newton_loop = false;            // a fill of a root search (skip_lost, wide items, deferred count published)
     bool force_uncached = false;         // omega-lane kernel whatever the batch size and the cache
+    const int* d_set = nullptr;          // set: item b belongs to the bound parameter set d_set[b] --
+    const int* host_set = nullptr;       // always the lanes-are-nodes fill over sets; and its host image
     FillRequest(int n, const double* omega, double* M) : nbatch(n), d_omega(omega), d_M(M) {}
 };
 int fill(emme_ctx* c, const FillRequest& r);
@@ -201,6 +208,9 @@ bool is_device_ptr(const void* p);
 int same_side(const void* a, const void* b, const char* names, bool* dev);
 // bytes of nbatch complex n x n matrices
 inline size_t batch_bytes(int n, int nbatch) { return (size_t)n * n * 2 * sizeof(double) * nbatch; }
+// a call over parameter sets: EMME_EINVAL unless sets are bound and every set[b] names one; the indices into c->d_set
+int check_set_indices(const emme_ctx* c, const int* set, int n, const char* who);
+int upload_set_indices(emme_ctx* c, const int* set, int n);
 int ensure_batch(emme_ctx* c, int nb);            // batch scratch for nb items
 int ensure_mats(emme_ctx* c, int nb, int sets);  // matrix sets for nb items: bit0 M, bit1 Mold, bit2 Mp, bit3 work
 // around a fill: the batch's omegas into d_omega; interval counts and status flags zeroed; afterwards the counts

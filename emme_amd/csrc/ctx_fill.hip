@@ -377,6 +377,25 @@ int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     return EMME_OK;
 }
 
+// A request whose items carry their own parameter set (r.d_set): k_assemble_sets, or with r.d_Md
+// k_assemble_sets_deriv.  Never the node cache, the omega-lane kernel or the tile fills; no fused secant.
+int launch_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
+    if (c->sets.empty() || !c->d_sets || !c->d_set_tabs) {
+        set_error("fill over parameter sets: no sets are bound to the context");
+        return EMME_EINVAL;
+    }
+    if (r.d_Mold) {
+        set_error("fill over parameter sets: no fused secant");
+        return EMME_EINVAL;
+    }
+    c->last_fill_listed = 0;
+    L.items_per_group = items_per_group_for(shape_of(c), r.nbatch);
+    c->last_fill_mode = FILL_SETS;
+    ScopedSpan span(c, K_ASM);
+    HIP_TRY((r.d_Md ? launch_assemble_sets_deriv : launch_assemble_sets)(L, c->d_sets, c->d_set_tabs, r.d_set, c->stream));
+    return EMME_OK;
+}
+
 // the majority class through the cache, then the `minority` class through the omega-lane kernel; the call's fill
 // kernel, as reported, stays the majority's
 int fill_by_class(emme_ctx* c, const FillRequest& r, int minority) {
@@ -398,11 +417,16 @@ int fill(emme_ctx* c, const FillRequest& r) {
     // omegas whose level lists overflowed in their previous fill (root search only): first, a chunk each, through the
     // wide-list build of the dense fill
     // (a derivative request has no wide-list build)
-    const bool has_wide = r.newton_loop && !r.d_Md && c->tiled && c->nm == 1 && !c->fb.wide.empty();
+    const bool has_wide = r.newton_loop && !r.d_Md && !r.d_set && c->tiled && c->nm == 1 && !c->fb.wide.empty();
     const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->fb.wide.data() : nullptr, c->h_actidx);
     const int n_act = (int)c->h_actidx.size();
     if (n_act == 0) return EMME_OK;
     AssembleLaunch L = make_launch(c, r);
+    if (r.d_set) {
+        EMME_TRY(launch_sets(c, L, r));
+        c->acc.matrices += n_act;
+        return EMME_OK;
+    }
     bool use_cache = wants_cache(c, r);
     if (use_cache) {
         const bool has_cache[2] = {(bool)c->cache[0].recs, (bool)c->cache[1].recs};

@@ -17,8 +17,13 @@ struct RootSearch {
     int step_limit;
     bool want_iterates;
     int method = 0;
+    const int* set = nullptr;  // host, n ints: chain b searches on the bound parameter set set[b] (null: the context's own)
     std::vector<int> act, zeros;  // host image of d_active (every chain live at the start); n zeros
     int stride() const { return step_limit + 1; }
+    // the parameter sets of the chains (uploaded by search_begin), for the loops' FillRequests
+    void to(const emme_ctx* c, FillRequest& r) const {
+        if (set) r.d_set = c->d_set, r.host_set = set;
+    }
     // (d_iterates is sized by the last call that asked for iterates: a call that does not ask must not write it)
     double* d_iterates(const emme_ctx* c) const { return want_iterates ? c->d_iterates.get() : nullptr; }
 };
@@ -37,6 +42,7 @@ int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     s.act.assign(n, 1), s.zeros.assign(n, 0);
+    if (s.set) EMME_TRY(upload_set_indices(c, s.set, n));
     HIP_TRY(hipMemcpyAsync(c->d_active, s.act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_iters, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_info, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
@@ -110,6 +116,7 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     };
     FillRequest first(n, c->d_omega, c->d_Mold);
     first.host_omega = w0.data(), first.newton_loop = true;
+    search.to(c, first);
     EMME_TRY(fill(c, first));
     EMME_TRY(refresh_cost());  // synchronises; the first fill's interval counts order the second
     HIP_TRY(hipMemcpyAsync(c->d_omega, w1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
@@ -117,6 +124,7 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     // taken by k_secant_copy at the top of the step that uses it, in one coalesced pass)
     FillRequest next(n, c->d_omega, c->d_M);
     next.host_omega = w1.data(), next.cost = fb.cost.data(), next.newton_loop = true;
+    search.to(c, next);
     EMME_TRY(fill(c, next));
     next.host_omega = h_w.data(), next.d_active = c->d_active, next.host_active = act.data();  // (the steps' fills)
 
@@ -198,6 +206,7 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
     HIP_TRY(hipMemcpyAsync(c->d_omega, search.guesses, sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
     FillRequest both(n, c->d_omega, c->d_M);
     both.d_Md = c->d_Mp, both.d_active = c->d_active, both.host_active = act.data();
+    search.to(c, both);
     // Option deriv_cached: the fills may go through the node cache, which needs what the secant loop gives its fills --
     // the live omegas on the host (contour classes), every omega's interval count of its previous fill (cost order)
     // and the root-search flag (skip_lost).  They travel as there: k_newton_update writes the omegas, k_retire the
@@ -266,10 +275,11 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
 }
 
 int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_limit, double* roots, int* iters, int* info,
-               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&)) {
+               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&), const int* set = nullptr) {
     if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
     RootSearch s{guesses, n, tol, step_limit, iterates != nullptr};
     s.method = c->p.iteration_method;  // src/main.cpp:45-49
+    s.set = set;
     EMME_TRY(check_method(c, s.method));
     HIP_TRY(hipSetDevice(c->device));
     for (;;) {
@@ -350,6 +360,14 @@ int emme_solve_roots(emme_ctx_t* c, const double* guesses, int n, double tol, in
 int emme_solve_roots_newton(emme_ctx_t* c, const double* guesses, int n, double tol, int step_limit, double* roots,
                             int* iters, int* info, double* iterates) {
     return run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop);  // (no M_old)
+}
+
+int emme_solve_roots_sets(emme_ctx_t* c, const int* set, const double* guesses, int n, int exact, double tol,
+                          int step_limit, double* roots, int* iters, int* info, double* iterates) {
+    if (!c || !set || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
+    EMME_TRY(check_set_indices(c, set, n, "emme_solve_roots_sets"));
+    return exact ? run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop, set)
+                 : run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 2 | 4 | 8, secant_loop, set);
 }
 
 }  // extern "C"

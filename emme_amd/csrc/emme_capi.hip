@@ -132,6 +132,27 @@ void dev_params_from(const emme_params_t* p, DevParams& P, std::vector<double>& 
     P.diag_d = es ? 0.0 : (2.0 * p->tau) / p->beta_e;
 }
 
+int check_set_indices(const emme_ctx* c, const int* set, int n, const char* who) {
+    if (c->sets.empty()) {
+        set_error(std::string(who) + ": no parameter sets are bound to the context (emme_ctx_bind_param_sets)");
+        return EMME_EINVAL;
+    }
+    for (int b = 0; b < n; ++b)
+        if (set[b] < 0 || set[b] >= (int)c->sets.size()) {
+            set_error(std::string(who) + ": set[" + std::to_string(b) + "] = " + std::to_string(set[b]) + " is outside [0, " +
+                      std::to_string(c->sets.size()) + ")");
+            return EMME_EINVAL;
+        }
+    return EMME_OK;
+}
+
+int upload_set_indices(emme_ctx* c, const int* set, int n) {
+    HIP_TRY(c->d_set.grow(sizeof(int) * (size_t)n));
+    // (pageable host memory: the copy has left `set` when the call returns)
+    HIP_TRY(hipMemcpyAsync(c->d_set, set, sizeof(int) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    return EMME_OK;
+}
+
 int require_device() {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
@@ -469,6 +490,68 @@ int emme_assemble_derivative_batch(emme_ctx_t* c, const double* omega, int nbatc
     if (!dev_out) {
         HIP_TRY(hipMemcpyAsync(M, dM, batch_bytes(c->dim, nbatch), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipMemcpyAsync(Mp, dMp, batch_bytes(c->dim, nbatch), hipMemcpyDeviceToHost, c->stream));
+    }
+    return collect_fill_status(c, nbatch, intervals);
+}
+
+// ---- parameter sets ---------------------------------------------------------------------------
+int emme_ctx_bind_param_sets(emme_ctx_t* c, const emme_params_t* sets, int nsets) {
+    if (!c || nsets < 0 || (nsets > 0 && !sets)) {
+        set_error("emme_ctx_bind_param_sets: NULL context or sets, or nsets < 0");
+        return EMME_EINVAL;
+    }
+    for (int s = 0; s < nsets; ++s)
+        if (emme_params_same_shape(&c->p, &sets[s]) != EMME_OK) {
+            set_error("emme_ctx_bind_param_sets: set " + std::to_string(s) + ": " + emme_last_error());
+            return EMME_EINVAL;
+        }
+    if (nsets == 0) {
+        c->sets.clear();
+        return EMME_OK;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    const size_t tn = 3 * (size_t)c->N;
+    std::vector<DevParams> P(nsets);
+    std::vector<double> tabs(tn * nsets), tab;
+    for (int s = 0; s < nsets; ++s) {
+        dev_params_from(&sets[s], P[s], tab);
+        std::copy(tab.begin(), tab.end(), tabs.begin() + tn * s);
+    }
+    // (an earlier call's kernels may still read the old binding)
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    c->sets.clear();
+    HIP_TRY(c->d_sets.grow(sizeof(DevParams) * nsets));
+    HIP_TRY(c->d_set_tabs.grow(sizeof(double) * tabs.size()));
+    HIP_TRY(hipMemcpy(c->d_sets, P.data(), sizeof(DevParams) * nsets, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(c->d_set_tabs, tabs.data(), sizeof(double) * tabs.size(), hipMemcpyHostToDevice));
+    c->sets.assign(sets, sets + nsets);
+    return EMME_OK;
+}
+
+int emme_ctx_param_sets(const emme_ctx_t* c) { return c ? (int)c->sets.size() : EMME_EINVAL; }
+
+int emme_assemble_sets_batch(emme_ctx_t* c, const int* set, const double* omega, int nbatch, double* M, double* Mp,
+                             long long* intervals) {
+    if (!c || !set || !omega || !M || nbatch < 1) return EMME_EINVAL;
+    EMME_TRY(check_set_indices(c, set, nbatch, "emme_assemble_sets_batch"));
+    HIP_TRY(hipSetDevice(c->device));
+    bool dev_out = is_device_ptr(M);
+    if (Mp) EMME_TRY(same_side(M, Mp, "M and Mp", &dev_out));
+    EMME_TRY(ensure_batch(c, nbatch));
+    double *dM = M, *dMp = Mp;
+    if (!dev_out) {
+        EMME_TRY(ensure_mats(c, nbatch, Mp ? (1 | 4) : 1));
+        dM = c->d_M, dMp = Mp ? c->d_Mp.get() : nullptr;
+    }
+    EMME_TRY(upload_set_indices(c, set, nbatch));
+    EMME_TRY(upload_omega(c, omega, nbatch, hipMemcpyDefault));
+    EMME_TRY(reset_fill_counters(c, nbatch));
+    FillRequest r(nbatch, c->d_omega, dM);
+    r.d_Md = dMp, r.d_set = c->d_set, r.host_set = set;
+    EMME_TRY(fill(c, r));
+    if (!dev_out) {
+        HIP_TRY(hipMemcpyAsync(M, dM, batch_bytes(c->dim, nbatch), hipMemcpyDeviceToHost, c->stream));
+        if (Mp) HIP_TRY(hipMemcpyAsync(Mp, dMp, batch_bytes(c->dim, nbatch), hipMemcpyDeviceToHost, c->stream));
     }
     return collect_fill_status(c, nbatch, intervals);
 }

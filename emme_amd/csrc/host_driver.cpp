@@ -21,6 +21,7 @@
 
 #include "../../include/emme_hip.h"
 #include "host_json.hpp"
+#include "scan_plan.hpp"
 
 namespace emme {
 void set_error(const std::string& msg);
@@ -30,6 +31,7 @@ int params_from_value(const JsonValue& root, emme_params_t* out);
 namespace {
 
 using emme::JsonValue;
+using emme::ScanGen;  // get_scan_generator, src/main.cpp:139-172 (scan_plan.hpp)
 using cplx = std::complex<double>;
 
 // ---- null vector: the right singular vector of the smallest singular value, by inverse iteration -------
@@ -124,31 +126,66 @@ JsonValue filter_input(const JsonValue& all) {
     return in;
 }
 
-// get_scan_generator, src/main.cpp:139-172
-struct ScanGen {
-    double head, step, left_tail, right_tail, current, current_tail;
-    bool to_left = true, is_first = true;
-    ScanGen(double h, double s, double l, double r)
-        : head(h), step(s), left_tail(l), right_tail(r), current(h), current_tail(l) {}
-    bool within() const {
-        return std::abs(current - head) <= (std::abs(current_tail - head) + 0.01 * std::abs(step));
+// What a search's per-chain info code becomes in a scan record: the text of the exception that turns the point into
+// {"eigenvalue":"NaN","reason":...} (src/main.cpp:311-318); empty for info == 0.
+std::string search_failure_text(int info) {
+    if (info > 0) {
+        // include/solver.h:142-153.  The reference prints zsysv's index of the singular block of its LDL^T
+        // factorisation; the step here is a partial-pivot LU, whose index of the zero pivot is a different
+        // number for the same verdict: the reference's sentence without a number it would not print, and
+        // this library's index marked as such.
+        std::ostringstream oss;
+        oss << "Linear solve failed. The factorization has been completed, but the "
+            << "block diagonal matrix D is exactly singular"
+            << ", so the solution could not be computed. [emme_amd: partial-pivot LU, zero pivot in column " << info << "]";
+        return oss.str();
     }
-    // returns (continue, turning, value)
-    void next(bool& cont, bool& turning, double& value) {
-        if (!is_first) current += std::copysign(step, (current_tail - head));
-        is_first = false;
-        if (within()) {
-            cont = true, turning = false, value = current;
-            return;
-        }
-        to_left = !to_left;
-        current_tail = right_tail;
-        current = head + std::copysign(step, (current_tail - head));
-        cont = !to_left && within();
-        turning = true;
-        value = current;
+    if (info < 0) {
+        // Failures the reference does not have a code for.  It would carry a non-finite integral
+        // into M, where zsysv fails (the message above), or into omega and end with a NaN eigenvalue;
+        // either way the scan records {"eigenvalue":"NaN","reason":...} (src/main.cpp:311-318) and does NOT
+        // continue the next scan point from this omega.  Same here.
+        return info == EMME_ENUMERIC
+                   ? "Linear solve failed. The matrix holds a non-finite integral, or the quadrature depth cap was reached "
+                     "(EMME_ENUMERIC), so the solution could not be computed."
+                   : "Linear solve failed on the device (EMME_EDEVICE).";
     }
-};
+    return std::string();
+}
+
+// M(omega_final) as the reference writes it (src/main.cpp:61-63); an empty path writes nothing
+bool write_matrix_file(const std::string& path, const std::vector<cplx>& M) {
+    if (path.empty()) return false;
+    std::ofstream f(path, std::ios::binary);
+    f.write(reinterpret_cast<const char*>(M.data()), (std::streamsize)(sizeof(cplx) * M.size()));
+    return (bool)f;
+}
+
+// the record of one solved point: eigenvalue, eigenvector, iterations
+JsonValue point_record(const double root[2], const cplx* vec, int dim, int iters) {
+    JsonValue res = JsonValue::make_object();
+    JsonValue ev = JsonValue::make_array();
+    ev.items.push_back(JsonValue::make(root[0]));
+    ev.items.push_back(JsonValue::make(root[1]));
+    res["eigenvalue"] = ev;
+    JsonValue evec = JsonValue::make_array();
+    for (int i = 0; i < dim; ++i) {
+        JsonValue pr = JsonValue::make_array();
+        pr.items.push_back(JsonValue::make(vec[i].real()));
+        pr.items.push_back(JsonValue::make(vec[i].imag()));
+        evec.items.push_back(pr);
+    }
+    res["eigenvector"] = evec;
+    res["iterations"] = JsonValue::make(iters);
+    return res;
+}
+
+JsonValue nan_record(const std::string& reason) {
+    JsonValue err = JsonValue::make_object();
+    err["eigenvalue"] = JsonValue::make(std::string("NaN"));
+    err["reason"] = JsonValue::make(reason);
+    return err;
+}
 
 // solve_once_eigen on an input object whose scan keys have been replaced by scalars
 JsonValue solve_once(const JsonValue& input, cplx& omega, const std::string& matrix_path, bool& file_ok) {
@@ -166,58 +203,159 @@ JsonValue solve_once(const JsonValue& input, cplx& omega, const std::string& mat
     if (emme_solve_roots(ctx, g, 1, p.iteration_precision, p.iteration_step_limit, root, &iters, &info,
                          nullptr) != EMME_OK)
         throw std::runtime_error(emme_last_error());
-    if (info > 0) {
-        // include/solver.h:142-153.  The reference prints zsysv's index of the singular block of its LDL^T
-        // factorisation; the step here is a partial-pivot LU, whose index of the zero pivot is a different
-        // number for the same verdict: the reference's sentence without a number it would not print, and
-        // this library's index marked as such.
-        std::ostringstream oss;
-        oss << "Linear solve failed. The factorization has been completed, but the "
-            << "block diagonal matrix D is exactly singular"
-            << ", so the solution could not be computed. [emme_amd: partial-pivot LU, zero pivot in column " << info << "]";
-        throw std::runtime_error(oss.str());
-    }
-    if (info < 0) {
-        // Failures the reference does not have a code for.  It would carry a non-finite integral
-        // into M, where zsysv fails (the message above), or into omega and end with a NaN eigenvalue;
-        // either way the scan records {"eigenvalue":"NaN","reason":...} (src/main.cpp:311-318) and does NOT
-        // continue the next scan point from this omega.  Same here.
-        throw std::runtime_error(
-            info == EMME_ENUMERIC
-                ? "Linear solve failed. The matrix holds a non-finite integral, or the quadrature depth cap was reached "
-                  "(EMME_ENUMERIC), so the solution could not be computed."
-                : "Linear solve failed on the device (EMME_EDEVICE).");
-    }
+    if (info != 0) throw std::runtime_error(search_failure_text(info));
     const int dim = emme_ctx_dim(ctx);
     std::vector<cplx> M((size_t)dim * dim), vec(dim);
     if (emme_ctx_get_matrix(ctx, 0, reinterpret_cast<double*>(M.data())) != EMME_OK)
         throw std::runtime_error(emme_last_error());
-    file_ok = false;
-    if (!matrix_path.empty()) {
-        std::ofstream f(matrix_path, std::ios::binary);  // src/main.cpp:61-63
-        f.write(reinterpret_cast<const char*>(M.data()), (std::streamsize)(sizeof(cplx) * M.size()));
-        file_ok = (bool)f;
-    }
+    file_ok = write_matrix_file(matrix_path, M);
     // nullSpace (include/solver.h:58-112, src/main.cpp:73-76) on the device, from M(omega_final) as the search left it
     int vinfo = 0;
     if (emme_null_vectors_batch(ctx, dim, 1, nullptr, reinterpret_cast<double*>(vec.data()), &vinfo) != EMME_OK)
         throw std::runtime_error(emme_last_error());
-    JsonValue res = JsonValue::make_object();
-    JsonValue ev = JsonValue::make_array();
-    ev.items.push_back(JsonValue::make(root[0]));
-    ev.items.push_back(JsonValue::make(root[1]));
-    res["eigenvalue"] = ev;
-    JsonValue evec = JsonValue::make_array();
-    for (int i = 0; i < dim; ++i) {
-        JsonValue pr = JsonValue::make_array();
-        pr.items.push_back(JsonValue::make(vec[i].real()));
-        pr.items.push_back(JsonValue::make(vec[i].imag()));
-        evec.items.push_back(pr);
-    }
-    res["eigenvector"] = evec;
-    res["iterations"] = JsonValue::make(iters);
+    JsonValue res = point_record(root, vec.data(), dim, iters);
     omega = cplx(root[0], root[1]);  // continuation, src/main.cpp:78
     return res;
+}
+
+// ---- the lock-step scan driver -------------------------------------------------------------
+// One axis that cannot ride along (ScanAxis::sequential), point after point through solve_once -- a context per
+// point, as the sequential driver walks it (src/main.cpp:264-324; emme_run_json's axis loop, which stays as it is).
+JsonValue sequential_unit(const JsonValue& all, const emme::ScanAxis& ax, const cplx guess0, const std::string& dir) {
+    JsonValue input = filter_input(all);
+    ScanGen gen(ax.head, ax.step, ax.t0, ax.t1);
+    bool cont, turning;
+    double value;
+    gen.next(cont, turning, value);
+    JsonValue values = JsonValue::make_array(), arr = JsonValue::make_array();
+    cplx omega = guess0;
+    while (cont) {
+        input[ax.key] = ax.head_is_int ? JsonValue::make((int)value) : JsonValue::make(value);
+        values.items.push_back(JsonValue::make(value));
+        if (turning) {  // second direction restarts from the head's root (:282-291)
+            const JsonValue& first = arr.items.at(0).at("eigenvalue");
+            omega = first.is_string() ? guess0 : cplx(first.at((size_t)0).number(), first.at((size_t)1).number());
+        }
+        const std::string fname = dir.empty() ? "" : dir + "/" + ax.key + "Eq" + std::to_string(value) + ".bin";
+        try {
+            bool ok = false;
+            JsonValue one = solve_once(input, omega, fname, ok);
+            one["eigenMatrix"] = JsonValue::make(ok ? fname : "Can not open '" + fname + "' for write.");
+            one["scan_value"] = JsonValue::make(value);
+            arr.items.push_back(one);
+        } catch (const std::exception& e) {
+            arr.items.push_back(nan_record(e.what()));
+        }
+        gen.next(cont, turning, value);
+    }
+    JsonValue unit = JsonValue::make_object();
+    unit["scan_key"] = JsonValue::make(ax.key);
+    unit["scan_values"] = values;
+    unit["scan_result"] = arr;
+    return unit;
+}
+
+// The axes that ride along, round by round on ONE context: the points of a round become the parameter sets bound to
+// it, one emme_solve_roots_sets call finds their roots side by side, one emme_null_vectors_batch their vectors.
+// units[a] receives the unit of riding axis a.  Throws (before any record exists) if the context cannot be made: the
+// caller then falls back to the sequential driver, whose records carry the reason point by point.
+void lockstep_units(const JsonValue& all, const emme::ScanPlan& plan, const cplx guess0, const std::string& dir,
+                    std::vector<JsonValue>& units) {
+    const JsonValue base = filter_input(all);
+    emme_params_t p0;
+    if (emme::params_from_value(base, &p0) != EMME_OK) throw std::runtime_error(emme_last_error());
+    emme_ctx_t* ctx = nullptr;
+    if (emme_ctx_create(&p0, -1, &ctx) != EMME_OK) throw std::runtime_error(emme_last_error());
+    struct Guard {
+        emme_ctx_t* c;
+        ~Guard() { emme_ctx_destroy(c); }
+    } guard{ctx};
+    const int dim = emme_ctx_dim(ctx);
+    const size_t naxes = plan.axes.size();
+    std::vector<std::vector<JsonValue>> records(naxes);
+    std::vector<JsonValue> values(naxes, JsonValue::make_array());
+    // per line: the omega its next point continues from (solve_once's `omega`); per axis: the head's root, if any
+    std::vector<cplx> cont0(naxes, guess0), cont1(naxes, guess0), head_root(naxes, guess0);
+    for (const emme::ScanPoint& pt : plan.points)
+        if (pt.round >= 0) {
+            records[pt.axis].resize(records[pt.axis].size() + 1);
+            values[pt.axis].items.push_back(JsonValue::make(pt.value));
+        }
+    struct Item {
+        const emme::ScanPoint* pt;
+        std::string fname;
+    };
+    for (int t = 0; t < plan.nrounds; ++t) {
+        std::vector<Item> items;
+        std::vector<emme_params_t> sets;
+        std::vector<double> guesses;
+        for (const emme::ScanPoint& pt : plan.points) {
+            if (pt.round != t) continue;
+            const emme::ScanAxis& ax = plan.axes[pt.axis];
+            if (pt.line == 1 && pt.pred == 0) cont1[pt.axis] = head_root[pt.axis];  // src/main.cpp:282-291
+            JsonValue input = base;
+            input[ax.key] = ax.head_is_int ? JsonValue::make((int)pt.value) : JsonValue::make(pt.value);
+            emme_params_t p;
+            if (emme::params_from_value(input, &p) != EMME_OK) {
+                records[pt.axis][pt.index] = nan_record(emme_last_error());
+                continue;
+            }
+            const cplx g = pt.line == 1 ? cont1[pt.axis] : cont0[pt.axis];
+            items.push_back({&pt, dir.empty() ? "" : dir + "/" + ax.key + "Eq" + std::to_string(pt.value) + ".bin"});
+            sets.push_back(p);
+            guesses.push_back(g.real()), guesses.push_back(g.imag());
+        }
+        const int n = (int)items.size();
+        if (n == 0) continue;
+        std::vector<int> set(n), iters(n, 0), info(n, 0), vinfo(n, 0);
+        for (int b = 0; b < n; ++b) set[b] = b;
+        std::vector<double> roots(2 * (size_t)n);
+        std::vector<cplx> vecs((size_t)n * dim), M((size_t)dim * dim);
+        std::string failed;  // a failure of the whole call: every point of the round records it, as solve_once would
+        if (emme_ctx_bind_param_sets(ctx, sets.data(), n) != EMME_OK ||
+            emme_solve_roots_sets(ctx, set.data(), guesses.data(), n, 0, p0.iteration_precision, p0.iteration_step_limit,
+                                  roots.data(), iters.data(), info.data(), nullptr) != EMME_OK)
+            failed = emme_last_error();
+        bool any_ok = false;
+        for (int b = 0; b < n; ++b) any_ok |= info[b] == 0;
+        std::string vec_failed;
+        if (failed.empty() && any_ok &&
+            emme_null_vectors_batch(ctx, dim, n, nullptr, reinterpret_cast<double*>(vecs.data()), vinfo.data()) != EMME_OK)
+            vec_failed = emme_last_error();
+        for (int b = 0; b < n; ++b) {
+            const emme::ScanPoint& pt = *items[b].pt;
+            JsonValue& rec = records[pt.axis][pt.index];
+            if (!failed.empty() || info[b] != 0) {
+                rec = nan_record(failed.empty() ? search_failure_text(info[b]) : failed);
+                continue;
+            }
+            if (emme_ctx_get_matrix(ctx, b, reinterpret_cast<double*>(M.data())) != EMME_OK) {
+                rec = nan_record(emme_last_error());
+                continue;
+            }
+            const bool ok = write_matrix_file(items[b].fname, M);
+            if (!vec_failed.empty()) {
+                rec = nan_record(vec_failed);
+                continue;
+            }
+            rec = point_record(&roots[2 * (size_t)b], vecs.data() + (size_t)b * dim, dim, iters[b]);
+            rec["eigenMatrix"] = JsonValue::make(ok ? items[b].fname : "Can not open '" + items[b].fname + "' for write.");
+            rec["scan_value"] = JsonValue::make(pt.value);
+            const cplx w(roots[2 * (size_t)b], roots[2 * (size_t)b + 1]);  // continuation, src/main.cpp:78
+            (pt.line == 1 ? cont1 : cont0)[pt.axis] = w;
+            if (pt.index == 0) head_root[pt.axis] = w;
+        }
+    }
+    for (size_t a = 0; a < naxes; ++a) {
+        if (plan.axes[a].sequential) continue;
+        JsonValue unit = JsonValue::make_object();
+        unit["scan_key"] = JsonValue::make(plan.axes[a].key);
+        JsonValue arr = JsonValue::make_array();
+        arr.items = records[a];
+        unit["scan_values"] = values[a];
+        unit["scan_result"] = arr;
+        units[a] = unit;
+    }
 }
 
 }  // namespace
@@ -348,6 +486,43 @@ int emme_run_json(const char* input_text, const char* matrix_dir, char** output_
                 results[ax.key] = unit;
             }
         }
+        result["result"] = results;
+        const std::string text = result.dump(0);
+        *output_text = static_cast<char*>(std::malloc(text.size() + 1));
+        if (!*output_text) return EMME_ENOMEM;
+        std::memcpy(*output_text, text.c_str(), text.size() + 1);
+        return EMME_OK;
+    } catch (const std::exception& e) {
+        emme::set_error(e.what());
+        return EMME_EJSON;
+    }
+}
+
+int emme_run_json_lockstep(const char* input_text, const char* matrix_dir, char** output_text) {
+    if (!input_text || !output_text) return EMME_EINVAL;
+    *output_text = nullptr;
+    try {
+        const JsonValue all = emme::json_parse(input_text, "input.json");
+        const emme::ScanPlan plan = emme::make_scan_plan(all);
+        // nothing to put side by side (no axis, or none that rides along), an input the sequential driver refuses, or
+        // no context for the rounds: the sequential driver, whose output says why point by point
+        if (plan.nrounds == 0 || all.at("method").str() != "eigen") return emme_run_json(input_text, matrix_dir, output_text);
+        const JsonValue& guess = all.at("initial_guess");
+        const cplx guess0(guess.at((size_t)0).number(), guess.at((size_t)1).number());
+        std::vector<JsonValue> units(plan.axes.size());
+        const std::string dir = matrix_dir ? std::string(matrix_dir) : std::string();
+        try {
+            lockstep_units(all, plan, guess0, dir, units);
+        } catch (const std::exception&) {
+            return emme_run_json(input_text, matrix_dir, output_text);
+        }
+        JsonValue result = JsonValue::make_object();
+        result["input"] = all;
+        result["run_time"] = JsonValue::make(date_string());
+        JsonValue results = JsonValue::make_object();
+        for (size_t a = 0; a < plan.axes.size(); ++a)
+            results[plan.axes[a].key] =
+                plan.axes[a].sequential ? sequential_unit(all, plan.axes[a], guess0, dir) : units[a];
         result["result"] = results;
         const std::string text = result.dump(0);
         *output_text = static_cast<char*>(std::malloc(text.size() + 1));

@@ -143,6 +143,27 @@ int emme_params_derive(emme_params_t* p) {
     return EMME_OK;
 }
 
+int emme_params_same_shape(const emme_params_t* a, const emme_params_t* b) {
+    if (!a || !b) {
+        emme::set_error("emme_params_same_shape: NULL parameter set");
+        return EMME_EINVAL;
+    }
+    // what every parameter set bound to one context shares: the order of the matrix and the number of
+    // integrals per pair, the quadrature rule the kernels are compiled for, the step of the search
+    const char* differs = nullptr;
+    if (a->npoints != b->npoints)
+        differs = "npoints";
+    else if ((std::fpclassify(a->beta_e) == FP_ZERO) != (std::fpclassify(b->beta_e) == FP_ZERO))
+        differs = "beta_e (zero in one set only)";
+    else if (a->integration_start_points != b->integration_start_points)
+        differs = "integration_start_points";
+    else if (a->iteration_method != b->iteration_method)
+        differs = "iteration_method";
+    if (!differs) return EMME_OK;
+    emme::set_error(std::string("parameter sets differ in shape: ") + differs);
+    return EMME_EINVAL;
+}
+
 int emme_params_from_json(const char* json_text, emme_params_t* out) {
     if (!json_text || !out) return EMME_EINVAL;
     try {

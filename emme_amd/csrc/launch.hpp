@@ -169,6 +169,16 @@ hipError_t launch_assemble_tile_shape_deriv(const AssembleLaunch& L, unsigned lo
 hipError_t launch_assemble_deriv_list_shape(const AssembleLaunch& L, const unsigned long long* worklist,
                                             const unsigned int* count, hipStream_t stream);
 
+// ---- lanes-are-nodes fill over parameter sets: assemble_sets_text.hpp -> assemble_sets.hip (M),
+// assemble_sets_deriv.hip (M and the exact dM/domega: L.Md set, L.Mold null).  Batch item b reads the scalars
+// sets[set[b]] and the tables tabs + set[b] * 3N (all three device arrays; every set has the shape of L.P: N, nm).
+// L.tab and L.Mold / L.Mp are not used (no fused secant: hipErrorInvalidValue if L.Mold is set); the plain launcher
+// refuses L.Md with hipErrorNotSupported. ------
+hipError_t launch_assemble_sets(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
+                                hipStream_t stream);
+hipError_t launch_assemble_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
+                                      hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

@@ -190,7 +190,8 @@ int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
 /* Kernel family used by the last fill: 0 lanes-are-nodes, 1 omega-lane, 2 HBM node cache
  * (independent lanes), 3 HBM node cache + phase table, union walk, 4 HBM node cache (tiled) +
- * dense fill on the FP64 matrix cores, 5 table-free tile fill on the FP64 matrix cores. */
+ * dense fill on the FP64 matrix cores, 5 table-free tile fill on the FP64 matrix cores, 6 lanes-are-nodes over
+ * parameter sets (emme_assemble_sets_batch, emme_solve_roots_sets; with or without the derivative). */
 int emme_ctx_fill_mode(const emme_ctx_t* ctx);
 /* Integrals the last fill handed to the work list (the cached fills and the tile fill finish them in a second
  * launch, from scratch); 0 for fills that have no work list.  Synchronises the context's stream.  < 0: an EMME_* code. */
@@ -279,7 +280,33 @@ int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nba
  * with tile_uncached as well through the table-free tile fill (k_assemble_tile_deriv) where there is no cache. */
 int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
                             double* roots, int* iters, int* info, double* iterates);
-/* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton call (dim*dim complex). */
+/* ---- parameter sets: many sets on one context (additions within version 4: find them by symbol lookup;
+ * DESIGN.md §13) ----------------------------------------------------------------------------------------------
+ * Every other entry point works on the ONE parameter set the context was created with.  These bind further sets to
+ * the context and let every item of a batch name the set it belongs to: one launch then fills (and one search
+ * iterates) items of different sets side by side, through k_assemble_sets / k_assemble_sets_deriv -- the
+ * lanes-are-nodes fill, never the node cache, the omega-lane kernel or the tile fills.  All sets of a context share
+ * its SHAPE: npoints, whether beta_e == 0, integration_start_points and iteration_method; everything else may differ,
+ * conf and length included.  Entry points without `set` behave exactly as before, whether or not sets are bound. */
+/* host only, no device: EMME_OK if b has a's shape (npoints, beta_e == 0 alike, integration_start_points,
+ * iteration_method), else EMME_EINVAL with emme_last_error naming the first field that differs */
+int emme_params_same_shape(const emme_params_t* a, const emme_params_t* b);
+/* bind nsets parameter sets (derived members filled) to a context; each must have the shape of the context's own
+ * set; replaces an earlier binding; nsets = 0 unbinds.  Arguments are checked BEFORE the device is looked for. */
+int emme_ctx_bind_param_sets(emme_ctx_t* ctx, const emme_params_t* sets, int nsets);
+int emme_ctx_param_sets(const emme_ctx_t* ctx);          /* number bound, < 0: EMME_EINVAL */
+/* M(omega_b) of parameter set set[b]; Mp nullable: the exact dM/domega of the same trees.
+ * Pointer rules as emme_assemble_batch / emme_assemble_derivative_batch; set: host, nbatch ints in [0, nsets).
+ * EMME_EINVAL without a binding or for a set[b] out of range; EMME_ENUMERIC as emme_assemble_batch. */
+int emme_assemble_sets_batch(emme_ctx_t* ctx, const int* set, const double* omega, int nbatch,
+                             double* M, double* Mp, long long* intervals);
+/* emme_solve_roots (exact = 0) or emme_solve_roots_newton (exact = 1), chain b on parameter set set[b].
+ * Everything else as those two (tol and step_limit are the call's, for every chain); emme_ctx_get_matrix and
+ * emme_null_vectors_batch(M = NULL) work afterwards. */
+int emme_solve_roots_sets(emme_ctx_t* ctx, const int* set, const double* guesses, int n, int exact,
+                          double tol, int step_limit, double* roots, int* iters, int* info, double* iterates);
+/* Copy M(omega_final) of item b of the last emme_solve_roots / emme_solve_roots_newton / emme_solve_roots_sets call
+ * (dim*dim complex). */
 int emme_ctx_get_matrix(emme_ctx_t* ctx, int b, double* M_host);
 
 /* ---- point probes (additions within version 4: find them by symbol lookup; tests and tooling only) ---------------
@@ -379,6 +406,21 @@ int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double r
  * emme_free).  Per-point failures become {"eigenvalue":"NaN","reason":...} records. */
 int emme_run_json(const char* input_text, const char* matrix_dir, char** output_text);
 void emme_free(void* p);
+/* emme_run_json with the independent lines of the scan solved side by side; same output schema.  A line is (axis,
+ * direction): round 0 solves the head of every axis, round t the t-th point of every line, each from the last
+ * successful root of its own line -- one emme_solve_roots_sets call on one context per round.
+ * Records, their order, file names, NaN records and reasons are the sequential driver's.  An axis whose key changes
+ * the shape (npoints, beta_e through zero, integration_start_points, iteration_method) or is iteration_precision /
+ * iteration_step_limit is run by the sequential driver. */
+int emme_run_json_lockstep(const char* input_text, const char* matrix_dir, char** output_text);
+/* The round plan of emme_run_json_lockstep for an input.json text (host only, no device).  Points are listed axis by
+ * axis (input order), each axis in emme_scan_values order: axis[k], index[k] (position on its axis), round[k] (-1 on a
+ * sequential axis), pred[k] (index on the same axis of the point it continues from: the previous point of its line,
+ * the head for the first point of either direction; -1 for the head: initial_guess).  sequential[a] = 1 for an axis
+ * left to the sequential driver.  At most max_points / max_axes entries are written (arrays nullable); *n_rounds is
+ * 1 + the longest line of the axes that ride along.  Returns the number of points, or EMME_EINVAL / EMME_EJSON. */
+int emme_scan_plan(const char* input_text, int max_points, int* axis, int* index, int* round, int* pred,
+                   int max_axes, int* sequential, int* n_axes, int* n_rounds);
 /* Values one {head, step, tail:[tail0, tail1]} axis visits, in order (reference
  * src/main.cpp:139-172); turning_flags[k] = 1 where the sweep restarts from the head in the
  * other direction.  Returns the number of values (<= max_values). */
