@@ -18,6 +18,7 @@
 
 #include "assemble_common.hpp"
 #include "launch.hpp"
+#include "launch_grid.hpp"
 #include "node_cache.hpp"
 
 namespace emme {
@@ -146,8 +147,8 @@ __device__ __forceinline__ cd node_value(const AsmArgs& A, const ClassTables& ct
     return node_eval(d, oc.omega, tc);
 }
 
-// (k_assemble_deriv below is the non-LIST, uncached form of this kernel with M' alongside: a change to the
-// accept / split rule or to the scatter here belongs there too)
+// (assemble_nodes_text.hpp is the non-LIST, uncached form of this kernel, and k_assemble_coop below has its scatter:
+// a change to the accept / split rule, the walk or the scatter here belongs there too)
 template <int PTS, bool LIST>
 #ifndef EMME_ASM_MIN_WAVES
 #define EMME_ASM_MIN_WAVES 3
@@ -334,165 +335,16 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
     }
 }
 
-// M and the exact dM/domega of the same discretised integrals, from scratch: k_assemble<PTS, false>
-// without the node cache, each lane also evaluating F' at its node (integrand_d) and the group summing K' beside K
-// and G.  Only K and G decide accept / split, so the trees, the interval counts and M are those of the plain kernel
-// bit for bit; accepted intervals add scale K' to a second running sum.  (A separate kernel rather than a template
-// flag on k_assemble, whose generated code a shared template changed.)  Md: [nbatch][dim][dim]; no fused secant.
-template <int PTS>
-__global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_deriv(AsmArgs A, double2* Md) {
-    constexpr int GW = PTS == 15 ? 16 : 32;
-    constexpr int GROUPS_PER_BLOCK = 256 / GW;
-    constexpr int MAXD = EMME_MAX_DEPTH;
-    extern __shared__ double lds_tab[];  // eta | g | b  (3N doubles) | per-group (mid, r) stack
-
-    const DevParams& P = A.P;
-    const int b = blockIdx.y;
-    if (A.active && A.active[b] == 0) return;
-    const int N = P.N, dim = P.dim;
-
-    for (int k = threadIdx.x; k < 3 * N; k += blockDim.x) lds_tab[k] = A.tab[k];
-    __syncthreads();
-    const double* eta = lds_tab;
-    const double* gtab = lds_tab + N;
-    const double* btab = lds_tab + 2 * N;
-    double2* stk = reinterpret_cast<double2*>(lds_tab + 3 * N + (3 * N & 1)) + (threadIdx.x / GW) * MAXD;
-
-    double2* Mb = A.M + (size_t)b * dim * dim;
-    double2* Mdb = Md + (size_t)b * dim * dim;
-    OmegaConst oc;
-    oc.omega = mk(A.omega[b].x, A.omega[b].y);
-    oc.omi = -copysign(1.0, oc.omega.x);
-    // an entry of M and the same entry of M'
-    auto store = [&](int r, int c, cd v, cd vd) {
-        store_entry_twin(Mb, Mdb, (size_t)r * dim + c, v, vd);
-    };
-    const cd zero = mk(0.0, 0.0);
-
-    // diagonal (include/solver.h:442-443, 465-470): constant in omega, so 0 in M'
-    if (blockIdx.x == 0) {
-        for (int i = threadIdx.x; i < N; i += blockDim.x) {
-            store(i, i, mk(P.diag_a, 0.0), zero);
-            if (P.nm == 3) {
-                store(i, i + N, zero, zero);
-                store(i + N, i, zero, zero);
-                store(i + N, i + N, mk(P.diag_d * btab[i], 0.0), zero);
-            }
-        }
-    }
-
-    const int lane_in_group = threadIdx.x % GW;
-    const int group = blockIdx.x * GROUPS_PER_BLOCK + threadIdx.x / GW;
-    const int ngroups = gridDim.x * GROUPS_PER_BLOCK;
-    const GkLane gk = gk_lane<PTS>(lane_in_group);
-
-    const double qa = 0.0, qb = M_PI / 2.0;
-    const double inv_scale = 2. / (qb - qa);
-    const int nitems = A.npairs * P.nm;
-
-    int item = group;
-    bool live = item < nitems;
-    int i = 0, j = 0, m = 0;
-    PairConst pc{};
-    double dg = 0.0;
-    int depth = 0;
-    unsigned long long path = 0;
-    double l = qa, r = qb;
-    double abs_tol = 0.0;
-    cd sum = zero, sum_d = zero;
-    unsigned long long my_intervals = 0;
-    int item_intervals = 0;
-    int bad = 0;
-
-    auto load_item = [&]() {
-        const int p = item / P.nm;
-        m = item - p * P.nm;
-        const ushort2 ij = A.pairs[p];
-        i = ij.x, j = ij.y;
-        dg = gtab[i] - gtab[j];
-        pc = make_pair_const(P, eta[i], eta[j], btab[i], btab[j], dg);
-        depth = 0, path = 0, abs_tol = 0.0;
-        l = qa, r = qb;
-        item_intervals = 0;
-        sum = zero, sum_d = zero;
-    };
-    if (live) load_item();
-
-    while (live) {
-        const double mid = (r + l) / 2;
-        const double scale = (r - l) / 2;
-        const double x = __dadd_rn(__dmul_rn(scale, gk.x), mid);
-
-        cd fd;
-        const cd f = integrand_d(x, P, pc, oc, m, fd);
-        const double Kx = group_sum<GW>(gk.wk * f.x), Ky = group_sum<GW>(gk.wk * f.y);
-        const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
-        const double Kdx = group_sum<GW>(gk.wk * fd.x), Kdy = group_sum<GW>(gk.wk * fd.y);
-        ++my_intervals;
-        ++item_intervals;
-
-        // the plain kernel's rule, on K and G alone
-        const cd integral = mk(Kx * scale, Ky * scale);
-        bool split = gk_split(mk(Kx, Ky), mk(Gx, Gy), scale, inv_scale, depth, P, abs_tol);
-        if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {
-            split = false;
-            bad = 1;
-        }
-        if (split) {
-            stk[depth] = make_double2(mid, r);
-            r = mid;
-            ++depth;
-            path <<= 1;
-        } else {
-            sum = sum + integral;
-            sum_d = sum_d + mk(Kdx * scale, Kdy * scale);
-            ++path;
-            while (depth > 0 && !(path & 1)) {
-                path >>= 1;
-                --depth;
-            }
-            if (depth == 0) {
-                cd kap = mk(P.pref * sum.y, -(P.pref * sum.x));
-                if (kappa_bad(kap)) bad = 1;
-                kap = kap + kappa_e(m, P, pc.de, dg, oc.omega);
-                // kappa' = -i pref sum' + kappa_e', scattered like kappa
-                cd kd = mk(P.pref * sum_d.y, -(P.pref * sum_d.x));
-                if (kappa_bad(kd)) bad = 1;
-                kd = kd + kappa_e_d(m, P, pc.de, dg, oc.omega);
-                if (lane_in_group == 0) {
-                    if (m == 0) {
-                        const double w = -(pair_weight(i, j, N) * P.dx);
-                        const cd v = w * kap, vd = w * kd;
-                        store(i, j, v, vd);
-                        store(j, i, v, vd);
-                    } else if (m == 1) {
-                        const cd v = P.dx * kap, vd = P.dx * kd;
-                        store(i, j + N, v, vd);
-                        store(j, i + N, -v, -vd);
-                        store(i + N, j, -v, -vd);
-                        store(j + N, i, v, vd);
-                    } else {
-                        const cd v = P.dx * kap, vd = P.dx * kd;
-                        store(i + N, j + N, v, vd);
-                        store(j + N, i + N, v, vd);
-                    }
-                }
-                item += ngroups;
-                live = item < nitems;
-                if (live) load_item();
-            } else {
-                const double2 pr = stk[depth - 1];
-                l = pr.x;
-                r = pr.y;
-            }
-        }
-    }
-
-    if (lane_in_group == 0) {
-        if (A.intervals && my_intervals) atomicAdd(&A.intervals[b], my_intervals);
-        if (bad) A.status[b] = 1;
-    }
-}
+// k_assemble_deriv<PTS>(AsmArgs A, double2* Md): M and the exact dM/domega of the same discretised integrals, from
+// scratch -- k_assemble<PTS, false> without the node cache, with K' summed beside K and G.  Its text is
+// the one-set derivative reading of assemble_nodes_text.hpp, which the fills over parameter sets share.  (A separate
+// kernel rather than a template flag on k_assemble, whose generated code a shared template changed.)  Md:
+// [nbatch][dim][dim]; no fused secant.
+#define EMME_NODES_SETS 0
+#define EMME_NODES_DERIV 1
+#include "assemble_nodes_text.hpp"
+#undef EMME_NODES_SETS
+#undef EMME_NODES_DERIV
 
 // ---- cooperative form for the deferred list ---------------------------------------------------
 // The few integrals the cached kernel defers are the long ones (up to thousands of intervals,
@@ -717,18 +569,10 @@ hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream) {
         A.wtab[c] = nullptr;
         for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k) A.recs_ext[c][k] = nullptr;
     }
-    const int gw = L.gk_points == 15 ? 16 : 32;
-    const int groups_per_block = 256 / gw;
+    const int groups_per_block = 256 / (L.gk_points == 15 ? 16 : 32);
     const long nitems = (long)L.npairs * L.P.nm;
-    // about `items_per_group` integrals per group keeps the tail short without
-    // starving the chip when the batch is small
-    long want_groups = (nitems + L.items_per_group - 1) / L.items_per_group;
-    long gx = (want_groups + groups_per_block - 1) / groups_per_block;
-    if (gx < 1) gx = 1;
-    if (gx > 65535) gx = 65535;
-    dim3 grid((unsigned)gx, (unsigned)L.nbatch), block(256);
-    const size_t lds = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double) +
-                       (size_t)groups_per_block * EMME_MAX_DEPTH * sizeof(double2);
+    dim3 grid(lane_group_grid_x(nitems, L.items_per_group, groups_per_block), (unsigned)L.nbatch), block(256);
+    const size_t lds = tables_stack_lds_bytes(L.P.N, groups_per_block);
     if (L.Md) {
         if (L.Mold) return hipErrorInvalidValue;  // (the derivative fill has no fused secant)
         if (L.gk_points == 15)
@@ -776,8 +620,7 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
         for (int k = 0; k < NODE_CACHE_MAX_SUB - 1; ++k)
             A.recs_ext[c][k] = cache ? (const NodeRec*)cache->recs_ext[c][k] : nullptr;
     }
-    const int gw = L.gk_points == 15 ? 16 : 32;
-    const int groups_per_block = 256 / gw;
+    const int groups_per_block = 256 / (L.gk_points == 15 ? 16 : 32);
     dim3 grid(2048), block(256);
     const bool one_group = L.defer_one_group != 0;
     if (!one_group) {
@@ -787,7 +630,7 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
         // wave-level barriers).  The list length is on the device: both variants are launched
         // and the one whose range it is not in returns at once.
         const unsigned int wide_min = (unsigned int)L.coop_wide_min;  // (-1 = never: 0xffffffff)
-        const size_t tab_bytes = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double);
+        const size_t tab_bytes = tables_lds_bytes(L.P.N);
         A.count_lo = 0, A.count_hi = wide_min;
         if (L.gk_points == 15)
             hipLaunchKernelGGL((k_assemble_coop<15, 256>), grid, block, tab_bytes + 4 * 256 * sizeof(CoopEnt), stream, A);
@@ -802,8 +645,7 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
         }
         return hipGetLastError();
     }
-    const size_t lds = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double) +
-                       (size_t)groups_per_block * EMME_MAX_DEPTH * sizeof(double2);
+    const size_t lds = tables_stack_lds_bytes(L.P.N, groups_per_block);
     if (L.gk_points == 15)
         hipLaunchKernelGGL((k_assemble<15, true>), grid, block, lds, stream, A);
     else

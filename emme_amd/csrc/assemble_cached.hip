@@ -27,6 +27,7 @@
 
 #include "assemble_common.hpp"
 #include "launch.hpp"
+#include "launch_grid.hpp"
 #include "node_cache.hpp"
 
 namespace emme {
@@ -965,33 +966,24 @@ hipError_t launch_assemble_cached(const AssembleLaunch& L, const NodeCacheView& 
     A.intervals = L.intervals;
     A.status = L.status;
     A.skip_lost = L.skip_lost;
-    const int gw = L.gk_points == 15 ? 16 : 32;
-    const int groups_per_block = 256 / gw;
+    const int groups_per_block = 256 / (L.gk_points == 15 ? 16 : 32);
     const long nitems = (long)L.npairs * L.P.nm;
-    long want_groups = (nitems + L.items_per_group - 1) / L.items_per_group;
-    long gx = (want_groups + groups_per_block - 1) / groups_per_block;
-    if (gx < 1) gx = 1;
-    if (gx > 65535) gx = 65535;
-    dim3 grid((unsigned)gx, (unsigned)nchunks), block(256);
+    dim3 grid(lane_group_grid_x(nitems, L.items_per_group, groups_per_block), (unsigned)nchunks), block(256);
     const size_t lds = ((size_t)3 * L.P.N + (size_t)A.geom.ni()) * sizeof(double);
     // electrostatic GK15 on folded records: the union-walk kernel (EMME_UNION=0: independent lanes)
     const bool union_walk = L.union_walk != 0;
     if (L.gk_points == 15 && etab && union_walk && L.P.nm == 1) {
-        const long ug = (nitems + L.items_per_group - 1) / L.items_per_group;
-        long ugx = (ug + 15) / 16;
-        if (ugx < 1) ugx = 1;
-        if (ugx > 65535) ugx = 65535;
-        const size_t n0 = (size_t)3 * L.P.N;
+        const unsigned ugx = lane_group_grid_x(nitems, L.items_per_group, 16);
         // intervals served per round (EMME_UNION_SEL, default 2): see the kernel
         const int nsel = L.union_sel;
-        const size_t ulds0 = (n0 + (n0 & 1)) * sizeof(double);
+        const size_t ulds0 = tables_lds_bytes(L.P.N);
         const size_t slot_bytes = (size_t)16 * 16 * 3 * sizeof(double2);
         if (nsel <= 1)
-            hipLaunchKernelGGL((k_assemble_union<15, 1>), dim3((unsigned)ugx, (unsigned)nchunks), block, ulds0 + slot_bytes, stream, A);
+            hipLaunchKernelGGL((k_assemble_union<15, 1>), dim3(ugx, (unsigned)nchunks), block, ulds0 + slot_bytes, stream, A);
         else if (nsel == 2)
-            hipLaunchKernelGGL((k_assemble_union<15, 2>), dim3((unsigned)ugx, (unsigned)nchunks), block, ulds0 + 2 * slot_bytes, stream, A);
+            hipLaunchKernelGGL((k_assemble_union<15, 2>), dim3(ugx, (unsigned)nchunks), block, ulds0 + 2 * slot_bytes, stream, A);
         else
-            hipLaunchKernelGGL((k_assemble_union<15, 4>), dim3((unsigned)ugx, (unsigned)nchunks), block, ulds0 + 4 * slot_bytes, stream, A);
+            hipLaunchKernelGGL((k_assemble_union<15, 4>), dim3(ugx, (unsigned)nchunks), block, ulds0 + 4 * slot_bytes, stream, A);
     } else if (L.gk_points == 15 && etab)
         hipLaunchKernelGGL((k_assemble_cached<15, true>), grid, block, lds, stream, A);
     else if (L.gk_points == 15)
@@ -1035,14 +1027,9 @@ hipError_t launch_assemble_cached_em(const AssembleLaunch& L, const NodeCacheVie
     A.intervals = L.intervals;
     A.status = L.status;
     A.skip_lost = L.skip_lost;
-    const int gw = L.gk_points == 15 ? 16 : 32;
-    const int groups_per_block = 256 / gw;
+    const int groups_per_block = 256 / (L.gk_points == 15 ? 16 : 32);
     const long nitems = (long)L.npairs;  // an item is a pair
-    long want_groups = (nitems + L.items_per_group - 1) / L.items_per_group;
-    long gx = (want_groups + groups_per_block - 1) / groups_per_block;
-    if (gx < 1) gx = 1;
-    if (gx > 65535) gx = 65535;
-    dim3 grid((unsigned)gx, (unsigned)nchunks), block(256);
+    dim3 grid(lane_group_grid_x(nitems, L.items_per_group, groups_per_block), (unsigned)nchunks), block(256);
     const size_t lds = ((size_t)3 * L.P.N + (size_t)A.geom.ni()) * sizeof(double);
     if (L.gk_points == 15 && etab)
         hipLaunchKernelGGL((k_assemble_cached_em<15, true>), grid, block, lds, stream, A);

@@ -1,40 +1,58 @@
-// assemble_sets_text.hpp -- the ONE text of the lanes-are-nodes fill whose batch items each carry their own parameter
-// set, compiled once per translation unit: assemble_sets.hip sets EMME_SETS_DERIV to 0 and gets k_assemble_sets (M),
-// assemble_sets_deriv.hip sets it to 1 and gets k_assemble_sets_deriv (M and the exact dM/domega).  The
-// preprocessor selects the regions that differ, so each unit's compiler sees the token stream of a kernel written on
-// its own and each kernel keeps its own register allocation (as assemble_tile_text.hpp).
+// assemble_nodes_text.hpp -- the ONE text of the lanes-are-nodes fills that carry neither LIST mode nor the node cache:
+// a lane group of 16 (GK15) or 32 (GK31) lanes per (pair, moment) item, lane = node, group_sum, the flattened
+// accept / split state machine, blockIdx.y = batch item, the caps EMME_MAX_DEPTH / EMME_MAX_INTERVALS, the `active`
+// skip, the interval and status counters.  Two macros select the regions that differ:
 //
-// Every other fill takes ONE DevParams by value as a kernel argument and ONE eta | g | b table: a launch holds one
-// parameter set.  Here batch item b = blockIdx.y belongs to set s = set[b] of the sets bound to the context
-// (emme_ctx_bind_param_sets): its scalars are sets[s], its tables tabs + s * 3N.  The rest is k_assemble<PTS, false> /
-// k_assemble_deriv<PTS> of assemble.hip, statement by statement: a lane group of 16 (GK15) or 32 (GK31) lanes per
-// (pair, moment) item, lane = node, group_sum, the flattened accept / split state machine, the same leaves
-// (integrand, integrand_d, make_pair_const, gk_split, store_entry_secant / store_entry_twin, kappa_e, pair_weight,
-// kappa_bad) in the same order, the caps EMME_MAX_DEPTH / EMME_MAX_INTERVALS, the `active` skip, the interval and
-// status counters.  No node cache, no LIST mode, no fused secant (a root search takes M' with k_secant_copy_sym).
+//   EMME_NODES_DERIV  0: M alone;  1: M and the exact dM/domega of the same discretised integrals -- each
+//                     lane also evaluates F' at its node (integrand_d) and the group sums K' beside K and G.  Only K and
+//                     G decide accept / split, so the trees, the interval counts and M are the plain kernel's bit for bit.
+//   EMME_NODES_SETS   0: ONE parameter set per launch, DevParams by value in the kernel argument, one eta | g | b table;
+//                     1: batch item b belongs to set s = set[b] of the sets bound to the context
+//                     (emme_ctx_bind_param_sets): its scalars are sets[s], its tables tabs + s * 3N.
 //
-// s is uniform per workgroup and the set's scalars are read ONCE, before the kernel's first store, into a by-value
-// copy: the address is uniform and nothing can have clobbered it, so the compiler reads the struct with scalar loads
-// and keeps it in SGPRs, where k_assemble has its kernel argument.  (A reference into `sets` would be read again
-// after the stores to M, by vector loads, once per use.)
+//   SETS  DERIV   read by                    yields
+//    1     0      assemble_sets.hip          k_assemble_sets<PTS>, launch_assemble_sets
+//    1     1      assemble_sets_deriv.hip    k_assemble_sets_deriv<PTS>, launch_assemble_sets_deriv
+//    0     1      assemble.hip               k_assemble_deriv<PTS>(AsmArgs, Md), where that kernel stood
+//    0     0      nobody: k_assemble<PTS, LIST> of assemble.hip keeps its own text, because it also carries LIST mode
+//                 and the node-cache reads.  That text is this one's plain reading statement by statement -- a change
+//                 to the accept / split rule, the walk or the scatter in one belongs in the other.
 //
-// All sets of a launch share N, nm (whether beta_e == 0), the quadrature rule and the pair list (the
-// shape); everything else in DevParams and the tables may differ from item to item.
+// Each reading's compiler sees the token stream of a kernel written on its own, so each kernel keeps its own register
+// allocation (as assemble_tile_text.hpp).  No fused secant in any reading (a root search takes
+// M' with k_secant_copy_sym).
 //
-// No include guard: a text, not a header of declarations.  The including unit defines EMME_SETS_DERIV and nothing else.
-#ifndef EMME_SETS_DERIV
-#error "assemble_sets_text.hpp is included by assemble_sets.hip (0) and assemble_sets_deriv.hip (1) only"
+// The sets readings are whole translation units: includes, namespaces, argument struct and launcher are under
+// EMME_NODES_SETS here.  assemble.hip reads the kernel alone, inside its anonymous namespace, below AsmArgs and
+// EMME_ASM_MIN_WAVES.
+//
+// Sets: s is uniform per workgroup and the set's scalars are read ONCE, before the kernel's first store, into a
+// by-value copy: the address is uniform and nothing can have clobbered it, so the compiler reads the struct with scalar
+// loads and keeps it in SGPRs, where k_assemble has its kernel argument.  (A reference into `sets` would be read again
+// after the stores to M, by vector loads, once per use.)  All sets of a launch share N, nm (whether beta_e == 0), the
+// quadrature rule and the pair list (the shape); everything else in DevParams and the tables may differ
+// from item to item.
+//
+// No include guard: a text, not a header of declarations.
+#if !defined(EMME_NODES_DERIV) || !defined(EMME_NODES_SETS)
+#error "assemble_nodes_text.hpp is read by assemble_sets.hip, assemble_sets_deriv.hip and assemble.hip only, with EMME_NODES_SETS and EMME_NODES_DERIV set"
 #endif
+#if !EMME_NODES_SETS && !EMME_NODES_DERIV
+#error "assemble_nodes_text.hpp has no plain one-set reading: that kernel is k_assemble<PTS, LIST> of assemble.hip"
+#endif
+
+#if EMME_NODES_SETS
 #include <hip/hip_runtime.h>
 
 #include "assemble_common.hpp"
 #include "launch.hpp"
+#include "launch_grid.hpp"
 
 namespace emme {
 
 namespace {
 
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
 struct SetsDerivArgs {
 #else
 struct SetsArgs {
@@ -47,7 +65,7 @@ struct SetsArgs {
     const double2* omega;   // [nbatch]
     const int* active;      // [nbatch] or null: item skipped when 0
     double2* M;             // [nbatch][dim][dim]
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
     double2* Md;            // [nbatch][dim][dim]
 #endif
     unsigned long long* intervals;  // [nbatch], atomically accumulated (may be null)
@@ -57,8 +75,12 @@ struct SetsArgs {
 #ifndef EMME_ASM_MIN_WAVES
 #define EMME_ASM_MIN_WAVES 3
 #endif
+#endif  // EMME_NODES_SETS
+
 template <int PTS>
-#if EMME_SETS_DERIV
+#if !EMME_NODES_SETS
+__global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_deriv(AsmArgs A, double2* Md) {
+#elif EMME_NODES_DERIV
 __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets_deriv(SetsDerivArgs A) {
 #else
 __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsArgs A) {
@@ -68,6 +90,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
     constexpr int MAXD = EMME_MAX_DEPTH;  // bisection depth the LDS interval stack can hold
     extern __shared__ double lds_tab[];  // eta | g | b  (3N doubles) | per-group (mid, r) stack
 
+#if EMME_NODES_SETS
     const int b = blockIdx.y;
     if (A.active && A.active[b] == 0) return;
     const int s = A.set[b];       // uniform per workgroup
@@ -75,21 +98,35 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
     const int N = P.N, dim = P.dim;
 
     const double* tab = A.tabs + (size_t)s * 3 * N;
+#else
+    const DevParams& P = A.P;
+    const int b = blockIdx.y;
+    if (A.active && A.active[b] == 0) return;
+    const int N = P.N, dim = P.dim;
+
+    const double* tab = A.tab;
+#endif
     for (int k = threadIdx.x; k < 3 * N; k += blockDim.x) lds_tab[k] = tab[k];
     __syncthreads();
     const double* eta = lds_tab;
     const double* gtab = lds_tab + N;
     const double* btab = lds_tab + 2 * N;
-    // (mid, r) of every split ancestor of the current interval, one stack per lane group (assemble.hip)
+    // (mid, r) of every split ancestor of the current interval, one stack per lane group.  All lanes of a group store
+    // the same value to the same slot and later read it back, so plain per-thread program order is enough
     double2* stk = reinterpret_cast<double2*>(lds_tab + 3 * N + (3 * N & 1)) + (threadIdx.x / GW) * MAXD;
 
     double2* Mb = A.M + (size_t)b * dim * dim;
+#if !EMME_NODES_SETS  // (Mdb here, before omega is read, in this reading and below it in the other: DESIGN.md 12.2.2)
+    double2* Mdb = Md + (size_t)b * dim * dim;
+#endif
     OmegaConst oc;
     oc.omega = mk(A.omega[b].x, A.omega[b].y);
     oc.omi = -copysign(1.0, oc.omega.x);
     const cd zero = mk(0.0, 0.0);
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
+#if EMME_NODES_SETS
     double2* Mdb = A.Md + (size_t)b * dim * dim;
+#endif
     // an entry of M and the same entry of M'
     auto store = [&](int r, int c, cd v, cd vd) {
         store_entry_twin(Mb, Mdb, (size_t)r * dim + c, v, vd);
@@ -103,7 +140,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
     // diagonal (include/solver.h:442-443, 465-470): block 0 of each batch item; constant in omega, so 0 in M'
     if (blockIdx.x == 0) {
         for (int i = threadIdx.x; i < N; i += blockDim.x) {
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
             store(i, i, mk(P.diag_a, 0.0), zero);
             if (P.nm == 3) {
                 store(i, i + N, zero, zero);
@@ -141,8 +178,8 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
     double l = qa, r = qb;        // the current interval
     double abs_tol = 0.0;
     cd sum = zero;
-#if EMME_SETS_DERIV
-    cd sum_d = zero;
+#if EMME_NODES_DERIV
+    cd sum_d = zero;  // accepted intervals' scale * K'
 #endif
     unsigned long long my_intervals = 0;
     int item_intervals = 0;  // safety valve: no integral may run away (every wave must exit)
@@ -159,7 +196,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
         l = qa, r = qb;
         item_intervals = 0;
         sum = zero;
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
         sum_d = zero;
 #endif
     };
@@ -171,7 +208,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
         // abscissa scale * x + mid, rounded like the reference (no FMA contraction)
         const double x = __dadd_rn(__dmul_rn(scale, gk.x), mid);
 
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
         cd fd;
         const cd f = integrand_d(x, P, pc, oc, m, fd);
 #else
@@ -179,13 +216,13 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
 #endif
         const double Kx = group_sum<GW>(gk.wk * f.x), Ky = group_sum<GW>(gk.wk * f.y);
         const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
         const double Kdx = group_sum<GW>(gk.wk * fd.x), Kdy = group_sum<GW>(gk.wk * fd.y);
 #endif
         ++my_intervals;
         ++item_intervals;
 
-        // (the derivative kernel: the plain kernel's rule, on K and G alone)
+        // (the derivative kernels: the plain kernel's rule, on K and G alone)
         const cd integral = mk(Kx * scale, Ky * scale);
         bool split = gk_split(mk(Kx, Ky), mk(Gx, Gy), scale, inv_scale, depth, P, abs_tol);
         if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {  // flag and accept
@@ -201,7 +238,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
             path <<= 1;
         } else {
             sum = sum + integral;
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
             sum_d = sum_d + mk(Kdx * scale, Kdy * scale);
 #endif
             ++path;
@@ -214,7 +251,7 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
                 cd kap = mk(P.pref * sum.y, -(P.pref * sum.x));
                 if (kappa_bad(kap)) bad = 1;
                 kap = kap + kappa_e(m, P, pc.de, dg, oc.omega);
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
                 // kappa' = -i pref sum' + kappa_e', scattered like kappa
                 cd kd = mk(P.pref * sum_d.y, -(P.pref * sum_d.x));
                 if (kappa_bad(kd)) bad = 1;
@@ -277,12 +314,13 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble_sets(SetsA
     }
 }
 
+#if EMME_NODES_SETS
 }  // namespace
 
 // L describes the batch as for launch_assemble (L.P: the context's own set, read for the shape -- N, nm -- only; L.tab
 // is not read); sets / tabs / set are device arrays (see the argument struct).  The grid, the block and the LDS are
 // launch_assemble's.
-#if EMME_SETS_DERIV
+#if EMME_NODES_DERIV
 hipError_t launch_assemble_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
                                       hipStream_t stream) {
     if (!L.Md || L.Mold) return hipErrorInvalidValue;  // (no fused secant)
@@ -306,17 +344,11 @@ hipError_t launch_assemble_sets(const AssembleLaunch& L, const DevParams* sets, 
     A.M = (double2*)L.M;
     A.intervals = L.intervals;
     A.status = L.status;
-    const int gw = L.gk_points == 15 ? 16 : 32;
-    const int groups_per_block = 256 / gw;
+    const int groups_per_block = 256 / (L.gk_points == 15 ? 16 : 32);
     const long nitems = (long)L.npairs * L.P.nm;
-    long want_groups = (nitems + L.items_per_group - 1) / L.items_per_group;
-    long gx = (want_groups + groups_per_block - 1) / groups_per_block;
-    if (gx < 1) gx = 1;
-    if (gx > 65535) gx = 65535;
-    dim3 grid((unsigned)gx, (unsigned)L.nbatch), block(256);
-    const size_t lds = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double) +
-                       (size_t)groups_per_block * EMME_MAX_DEPTH * sizeof(double2);
-#if EMME_SETS_DERIV
+    dim3 grid(lane_group_grid_x(nitems, L.items_per_group, groups_per_block), (unsigned)L.nbatch), block(256);
+    const size_t lds = tables_stack_lds_bytes(L.P.N, groups_per_block);
+#if EMME_NODES_DERIV
     if (L.gk_points == 15)
         hipLaunchKernelGGL((k_assemble_sets_deriv<15>), grid, block, lds, stream, A);
     else
@@ -331,3 +363,4 @@ hipError_t launch_assemble_sets(const AssembleLaunch& L, const DevParams* sets, 
 }
 
 }  // namespace emme
+#endif  // EMME_NODES_SETS

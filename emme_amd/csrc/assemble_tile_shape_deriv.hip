@@ -4,141 +4,18 @@
 // unit, and the kernel that finishes the integrals they hand over.
 #define EMME_TILE_DERIV 1
 #include "assemble_tile_shape_text.hpp"
+#include "launch_grid.hpp"
 
 namespace emme {
 
 namespace {
 
 // ---- the integrals that kernel handed over --------------------------------------------------------------------------
-// k_assemble_deriv_list (assemble_dense_deriv.hip) for these shapes: a lane group of 16 (GK15) or 32 (GK31) lanes per
-// work-list entry (batch << 32 | pair nm + moment), from scratch (integrand_d per lane), M and M' of the integral.  The
-// scatter is k_assemble_deriv's, all three moment branches: a change there belongs here too.
-struct DerivListShapeArgs {
-    DevParams P;
-    const double* tab;
-    const ushort2* pairs;
-    const double2* omega;
-    double2* M;
-    double2* Md;
-    unsigned long long* intervals;
-    int* status;
-    const unsigned long long* worklist;
-    const unsigned int* worklist_count;
-    int skip_lost;
-};
-
-template <int PTS>
-__global__ __launch_bounds__(256, 2) void k_assemble_deriv_list_shape(DerivListShapeArgs A) {
-    constexpr int GW = PTS == 15 ? 16 : 32, GROUPS_PER_BLOCK = 256 / GW, MAXD = EMME_MAX_DEPTH;
-    extern __shared__ double lds_tab[];  // eta | g | b (3N doubles) | per-group (mid, r) stack
-
-    const DevParams& P = A.P;
-    const int N = P.N, dim = P.dim, nm = P.nm;
-    const int nitems = (int)*A.worklist_count;
-    if ((int)(blockIdx.x * GROUPS_PER_BLOCK) >= nitems) return;  // (block-uniform: no tables for an empty share)
-    for (int k = threadIdx.x; k < 3 * N; k += blockDim.x) lds_tab[k] = A.tab[k];
-    __syncthreads();
-    const double* eta = lds_tab;
-    const double* gtab = lds_tab + N;
-    const double* btab = lds_tab + 2 * N;
-    double2* stk = reinterpret_cast<double2*>(lds_tab + 3 * N + (3 * N & 1)) + (threadIdx.x / GW) * MAXD;
-
-    const int lane_in_group = threadIdx.x % GW;
-    const int group = blockIdx.x * GROUPS_PER_BLOCK + threadIdx.x / GW;
-    const int ngroups = gridDim.x * GROUPS_PER_BLOCK;
-    const GkLane gk = gk_lane<PTS>(lane_in_group);
-    const double qa = 0.0, qb = M_PI / 2.0;
-    const double inv_scale = 2. / (qb - qa);
-    const cd zero = mk(0.0, 0.0);
-
-    for (int item = group; item < nitems; item += ngroups) {
-        const unsigned long long e = A.worklist[item];
-        const int it = (int)(e & 0xffffffffull), b = (int)(e >> 32);
-        if (A.skip_lost && A.status[b] != 0) continue;  // (the matrix is lost already: uniform per group)
-        const int p = it / nm, m = it - p * nm;
-        OmegaConst oc;
-        oc.omega = mk(A.omega[b].x, A.omega[b].y);
-        oc.omi = -copysign(1.0, oc.omega.x);
-        const ushort2 ij = A.pairs[p];
-        const int i = ij.x, j = ij.y;
-        const double dg = gtab[i] - gtab[j];
-        const PairConst pc = make_pair_const(P, eta[i], eta[j], btab[i], btab[j], dg);
-        int depth = 0, item_intervals = 0, bad = 0;
-        unsigned long long path = 0;
-        double l = qa, r = qb, abs_tol = 0.0;
-        cd sum = zero, sum_d = zero;
-        for (;;) {
-            const double mid = (r + l) / 2;
-            const double scale = (r - l) / 2;
-            const double x = __dadd_rn(__dmul_rn(scale, gk.x), mid);
-            cd fd;
-            const cd f = integrand_d(x, P, pc, oc, m, fd);
-            const double Kx = group_sum<GW>(gk.wk * f.x), Ky = group_sum<GW>(gk.wk * f.y);
-            const double Gx = group_sum<GW>(gk.wg * f.x), Gy = group_sum<GW>(gk.wg * f.y);
-            const double Kdx = group_sum<GW>(gk.wk * fd.x), Kdy = group_sum<GW>(gk.wk * fd.y);
-            ++item_intervals;
-            // (gk_split of assemble_common.hpp, spelled out as in k_assemble_deriv_list)
-            const double dKx = Kx - Gx, dKy = Ky - Gy;
-            const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
-            double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
-            const cd integral = mk(Kx * scale, Ky * scale);
-            err *= scale;
-            const double rel_abs = P.rel_tol * (absK * scale);
-            if (abs_tol == 0.0) abs_tol = rel_abs;
-            bool split = depth < P.max_sub && err > abs_tol * inv_scale + P.prec_goal && err > rel_abs + P.prec_goal;
-            if (split && (depth >= MAXD || item_intervals >= EMME_MAX_INTERVALS)) {
-                split = false;
-                bad = 1;
-            }
-            if (split) {
-                stk[depth] = make_double2(mid, r);
-                r = mid;
-                ++depth;
-                path <<= 1;
-                continue;
-            }
-            sum = sum + integral;
-            sum_d = sum_d + mk(Kdx * scale, Kdy * scale);
-            ++path;
-            while (depth > 0 && !(path & 1)) {
-                path >>= 1;
-                --depth;
-            }
-            if (depth == 0) break;
-            const double2 pr = stk[depth - 1];
-            l = pr.x;
-            r = pr.y;
-        }
-        cd kap = mk(P.pref * sum.y, -(P.pref * sum.x));
-        cd kd = mk(P.pref * sum_d.y, -(P.pref * sum_d.x));
-        if (kappa_bad(kap) || kappa_bad(kd)) bad = 1;
-        kap = kap + kappa_e(m, P, pc.de, dg, oc.omega);
-        kd = kd + kappa_e_d(m, P, pc.de, dg, oc.omega);  // kappa' = -i pref sum' + kappa_e'
-        if (lane_in_group == 0) {
-            double2* Mb = A.M + (size_t)b * dim * dim;
-            double2* Mdb = A.Md + (size_t)b * dim * dim;
-            auto store = [&](int rw, int c, cd v, cd vd) { store_entry_twin(Mb, Mdb, (size_t)rw * dim + c, v, vd); };
-            if (m == 0) {
-                const double w = -(pair_weight(i, j, N) * P.dx);
-                const cd v = w * kap, vd = w * kd;
-                store(i, j, v, vd);
-                store(j, i, v, vd);
-            } else if (m == 1) {
-                const cd v = P.dx * kap, vd = P.dx * kd;
-                store(i, j + N, v, vd);
-                store(j, i + N, -v, -vd);
-                store(i + N, j, -v, -vd);
-                store(j + N, i, v, vd);
-            } else {
-                const cd v = P.dx * kap, vd = P.dx * kd;
-                store(i + N, j + N, v, vd);
-                store(j + N, i + N, v, vd);
-            }
-            if (A.intervals) atomicAdd(&A.intervals[b], (unsigned long long)item_intervals);
-            if (bad) A.status[b] = 1;
-        }
-    }
-}
+// DerivListShapeArgs and k_assemble_deriv_list_shape<PTS>, the shape reading of assemble_deriv_list_text.hpp: a lane
+// group of 16 (GK15) or 32 (GK31) lanes per work-list entry (batch << 32 | pair nm + moment), from scratch, M and M' of
+// the integral, every moment's scatter.
+#define EMME_DERIV_LIST_SHAPE 1
+#include "assemble_deriv_list_text.hpp"
 
 }  // namespace
 
@@ -157,9 +34,7 @@ hipError_t launch_assemble_deriv_list_shape(const AssembleLaunch& L, const unsig
     A.worklist = worklist;
     A.worklist_count = count;
     A.skip_lost = L.skip_lost;
-    const int groups_per_block = L.gk_points == 15 ? 16 : 8;
-    const size_t lds = ((size_t)3 * L.P.N + (3 * L.P.N & 1)) * sizeof(double) +
-                       (size_t)groups_per_block * EMME_MAX_DEPTH * sizeof(double2);
+    const size_t lds = tables_stack_lds_bytes(L.P.N, L.gk_points == 15 ? 16 : 8);
     // (the list length is on the device: a fixed grid strides over it, workgroups without a share return at once)
     if (L.gk_points == 15)
         hipLaunchKernelGGL(k_assemble_deriv_list_shape<15>, dim3(2048), dim3(256), lds, stream, A);

@@ -58,8 +58,8 @@ struct NodeCacheView {
 };
 // lanes-are-nodes kernel, without the node cache (L.Md set: k_assemble_deriv, M and dM/domega)
 hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream);
-// omega-lane form (assemble_wl.hip): the n_act batch items listed in act_idx (device) share
-// the omega-independent node data; L.active is ignored.  L.Md set: k_assemble_wl_deriv.
+// omega-lane form (assemble_wl.hip, both kernels from assemble_wl_text.hpp): the n_act batch items listed in act_idx
+// (device) share the omega-independent node data; L.active is ignored.  L.Md set: k_assemble_wl_deriv.
 hipError_t launch_assemble_wl(const AssembleLaunch& L, const int* act_idx, int n_act,
                               hipStream_t stream);
 
@@ -169,7 +169,8 @@ hipError_t launch_assemble_tile_shape_deriv(const AssembleLaunch& L, unsigned lo
 hipError_t launch_assemble_deriv_list_shape(const AssembleLaunch& L, const unsigned long long* worklist,
                                             const unsigned int* count, hipStream_t stream);
 
-// ---- lanes-are-nodes fill over parameter sets: assemble_sets_text.hpp -> assemble_sets.hip (M),
+// ---- lanes-are-nodes fill over parameter sets: the two sets readings of assemble_nodes_text.hpp (whose
+// one-set derivative reading is k_assemble_deriv of assemble.hip) -> assemble_sets.hip (M),
 // assemble_sets_deriv.hip (M and the exact dM/domega: L.Md set, L.Mold null).  Batch item b reads the scalars
 // sets[set[b]] and the tables tabs + set[b] * 3N (all three device arrays; every set has the shape of L.P: N, nm).
 // L.tab and L.Mold / L.Mp are not used (no fused secant: hipErrorInvalidValue if L.Mold is set); the plain launcher
