@@ -584,9 +584,13 @@ class Context:
                     5: "k_assemble_tile (table-free tile fill, FP64 matrix cores)"}
     # fill mode 6 (emme_assemble_sets_batch / emme_solve_roots_sets): not a kernel family of the plain fills above
     SETS_FILL_KERNEL = "k_assemble_sets (lanes=nodes, a parameter set per item)"
+    # fill mode 7: at least one (set, contour class) group of the call went through the tile fill over sets
+    TILE_SETS_FILL_KERNEL = "k_assemble_tile_sets (table-free tile fill, a parameter set per chunk)"
 
     def fill_kernel(self) -> str:
         mode = self.lib.emme_ctx_fill_mode(self.h)
+        if mode == 7:
+            return self.TILE_SETS_FILL_KERNEL
         return self.SETS_FILL_KERNEL if mode == 6 else self.FILL_KERNELS.get(mode, "none yet")
 
     def last_deferred(self) -> int:
@@ -619,6 +623,8 @@ class Context:
             return f"k_assemble_wl<{pts}>"
         if mode == 6:
             return f"k_assemble_sets<{pts}>"
+        if mode == 7:
+            return "k_assemble_tile_sets"
         return f"k_assemble<{pts}, false>"
 
     def node_cache_gib(self) -> float:

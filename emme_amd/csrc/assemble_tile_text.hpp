@@ -34,9 +34,24 @@
 // amplitude is not representable, goes whole to the work list; the host finishes the list from scratch
 // (launch_assemble_list without a cache view; launch_assemble_deriv_list for M and M').
 //
-// No include guard: a text, not a header of declarations.  The including unit defines EMME_TILE_DERIV and nothing else.
-#ifndef EMME_TILE_DERIV
-#error "assemble_tile_text.hpp is included by assemble_tile.hip (0) and assemble_tile_deriv.hip (1) only"
+// Parameter sets: EMME_TILE_SETS 1 is the reading for batches whose items carry their own parameter
+// set (emme_ctx_bind_param_sets).  A chunk holds omegas of ONE set as well as of one class (plan_tile_chunks with
+// host_set), so the set s of a workgroup is uniform: its scalars are read ONCE, before the kernel's first store, into a
+// by-value copy -- scalar loads into SGPRs, where the one-set reading has its kernel argument (assemble_nodes_text.hpp)
+// -- and its tables are tabs + s * 3N.  The work list has one segment and one counter per set, so that the list
+// kernels (assemble_sets_list_text.hpp) keep the set uniform per workgroup too.  No fused secant.  The walk, the
+// decisions, the caps, the counters and the epilogue are the one-set reading's.
+//
+//   SETS  DERIV   read by                         yields
+//    0     0      assemble_tile.hip               k_assemble_tile, launch_assemble_tile
+//    0     1      assemble_tile_deriv.hip         k_assemble_tile_deriv, launch_assemble_tile_deriv
+//    1     0      assemble_tile_sets.hip          k_assemble_tile_sets, launch_assemble_tile_sets
+//    1     1      assemble_tile_sets_deriv.hip    k_assemble_tile_sets_deriv, launch_assemble_tile_sets_deriv
+//
+// No include guard: a text, not a header of declarations.  The including unit defines EMME_TILE_DERIV and
+// EMME_TILE_SETS and nothing else.
+#if !defined(EMME_TILE_DERIV) || !defined(EMME_TILE_SETS)
+#error "assemble_tile_text.hpp is included by assemble_tile.hip, assemble_tile_deriv.hip, assemble_tile_sets.hip and assemble_tile_sets_deriv.hip only, with EMME_TILE_DERIV and EMME_TILE_SETS set"
 #endif
 #include <hip/hip_runtime.h>
 
@@ -48,17 +63,28 @@ namespace emme {
 
 namespace {
 
-#if EMME_TILE_DERIV
+#if EMME_TILE_SETS && EMME_TILE_DERIV
+struct TileSetsDerivArgs {
+#elif EMME_TILE_SETS
+struct TileSetsArgs {
+#elif EMME_TILE_DERIV
 struct TileDerivArgs {
 #else
 struct TileArgs {
 #endif
+#if EMME_TILE_SETS
+    const DevParams* sets;  // [nsets]: the scalars of every bound parameter set
+    const double* tabs;     // [nsets][3N]: eta | g | b of every set
+    const int* set;         // [nbatch]: the set of every batch item
+    const int* seg;         // [nsets]: where the work-list segment of every set begins
+#else
     DevParams P;
     const double* tab;  // eta | g | b
+#endif
     const ushort2* pairs;
     int npairs;
     unsigned long long* worklist;
-    unsigned int* worklist_count;
+    unsigned int* worklist_count;  // (sets: one counter per set)
     const int* act_idx;
     const int2* chunks;  // (first position, size <= 16) of every omega chunk; one contour class per chunk
     int nchunks;
@@ -66,7 +92,7 @@ struct TileArgs {
     double2* M;
 #if EMME_TILE_DERIV
     double2* Md;
-#else
+#elif !EMME_TILE_SETS
     const double2* Mold;
     double2* Mp;
     const double2* domega;
@@ -101,17 +127,35 @@ constexpr size_t TW_WG_LDS = TW * sizeof(TileWaveLds) + 16 * sizeof(unsigned lon
 static_assert(sizeof(TileWaveLds) == 23936, "LDS of a wave: DESIGN.md 12.3");
 static_assert(TW_WG_PER_CU * TW_WG_LDS <= 163840, "the intended workgroups per CU do not fit the CU's LDS");
 
+#if EMME_TILE_SETS
+__global__ __launch_bounds__(64 * TW, 2) void k_assemble_tile_sets_deriv(TileSetsDerivArgs A) {
+#else
 __global__ __launch_bounds__(64 * TW, 2) void k_assemble_tile_deriv(TileDerivArgs A) {
+#endif
 #else
 constexpr int TW = 4;
 #ifndef EMME_TILE_MIN_WAVES
 #define EMME_TILE_MIN_WAVES 2
 #endif
 
+#if EMME_TILE_SETS
+__global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile_sets(TileSetsArgs A) {
+#else
 __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(TileArgs A) {
 #endif
+#endif
     constexpr int KS = 8, GKS = 4;  // k-steps of K, k-steps that feed G too
+#if EMME_TILE_SETS
+    // the set of the workgroup's chunk (its first column's; below: blockIdx.x / ntg is the chunk), and that set's
+    // scalars by value before the first store: scalar loads (see the header)
+    const int set_chunk = blockIdx.x / (((A.npairs + TILE_PAIRS - 1) / TILE_PAIRS + TW - 1) / TW);
+    const int s = __builtin_amdgcn_readfirstlane(A.set[A.act_idx[A.chunks[set_chunk].x]]);
+    const DevParams P = A.sets[s];
+    const double* const tab = A.tabs + (size_t)s * 3 * P.N;
+    const int seg = A.seg[s];
+#else
     const DevParams& P = A.P;
+#endif
     const int N = P.N, dim = P.dim;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int col = lane & 15, rho = lane >> 4;
@@ -143,7 +187,12 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
     // the chunk's contour class is its first column's; a column of the other class (the planner never makes one)
     // is not filled and flags its matrix
     const int ccls = __builtin_amdgcn_readfirstlane(cls);
+#if EMME_TILE_SETS
+    // ... and so does a column of another set than the chunk's
+    const bool wrong_class = in_chunk && (cls != ccls || A.set[b] != s);
+#else
     const bool wrong_class = in_chunk && cls != ccls;
+#endif
     if (wrong_class) A.status[b] = 1;
     // A matrix that already holds a non-finite integral is lost: nobody works on it any more (assemble_dense.hip)
     const bool has_w = in_chunk && !wrong_class && !(A.skip_lost && A.status[b] != 0);
@@ -154,12 +203,14 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
         const size_t idx = (size_t)b * dim * dim + (size_t)r * dim + c;
 #if EMME_TILE_DERIV
         store_entry_twin(A.M, A.Md, idx, v, vx);
+#elif EMME_TILE_SETS
+        store_entry_secant(A.M, nullptr, nullptr, vx, idx, v);
 #else
         store_entry_secant(A.M, A.Mold, A.Mp, vx, idx, v);
 #endif
     };
     if (tile == 0 && has_w) {  // diagonal (include/solver.h:442-443): constant in omega, so 0 in M'
-#if EMME_TILE_DERIV
+#if EMME_TILE_DERIV || EMME_TILE_SETS
         const cd vx0 = mk(0.0, 0.0);
 #else
         const cd vx0 = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
@@ -174,7 +225,11 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
         const int pidx = tile * TILE_PAIRS + lane;
         const ushort2 ij = A.pairs[pidx < A.npairs ? pidx : 0];
         const int i = ij.x, j = ij.y;
+#if EMME_TILE_SETS
+        const PairConst pc = make_pair_const(P, tab[i], tab[j], tab[2 * N + i], tab[2 * N + j], tab[N + i] - tab[N + j]);
+#else
         const PairConst pc = make_pair_const(P, A.tab[i], A.tab[j], A.tab[2 * N + i], A.tab[2 * N + j], A.tab[N + i] - A.tab[N + j]);
+#endif
         pair_const_to_row(W.pc[lane], pc);
         W.wk[sn] = gk.wk;  // (lane 15 is the padding lane: weight 0 into slot 15)
     }
@@ -218,8 +273,14 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
 
     // (no record of the interval an element left at: there is no cache to grow around it)
     auto defer = [&](int r) {
+#if EMME_TILE_SETS
+        // (the segment of the chunk's set: it holds every integral of the set's items of this launch)
+        const unsigned int slot = atomicAdd(A.worklist_count + s, 1u);
+        A.worklist[(size_t)seg + slot] = ((unsigned long long)b << 32) | (unsigned int)(tile * TILE_PAIRS + rho + 4 * r);
+#else
         const unsigned int slot = atomicAdd(A.worklist_count, 1u);
         A.worklist[slot] = ((unsigned long long)b << 32) | (unsigned int)(tile * TILE_PAIRS + rho + 4 * r);
+#endif
         deferred[r] = true, alive[r] = false;
         mcur[r] = 0ull, mnext[r] = 0ull;
     };
@@ -422,7 +483,9 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
 
     // ---- results (include/solver.h:448-455: mat(i,j) = -kappa W_ij dx, mirrored; the same with sum' in M') -------
     unsigned long long my_intervals = 0;
-#if !EMME_TILE_DERIV
+#if EMME_TILE_SETS && !EMME_TILE_DERIV
+    const cd rdw = mk(0.0, 0.0);
+#elif !EMME_TILE_DERIV
     const cd rdw = A.Mold ? rcp(mk(A.domega[b].x, A.domega[b].y)) : mk(0.0, 0.0);
 #endif
 #pragma unroll
@@ -475,7 +538,25 @@ __global__ __launch_bounds__(64 * TW, EMME_TILE_MIN_WAVES) void k_assemble_tile(
 
 }  // namespace
 
-#if EMME_TILE_DERIV
+// (sets: L.P is the context's own set, read for the shape only -- L.tab, L.Mold / L.Mp are not used; sets / tabs / set
+// and seg are device arrays, see the argument struct; worklist_count has one counter per set)
+#if EMME_TILE_SETS && EMME_TILE_DERIV
+hipError_t launch_assemble_tile_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs,
+                                           const int* set, const int* seg, unsigned long long* worklist,
+                                           unsigned int* worklist_count, const int* act_idx, const void* chunks,
+                                           int nchunks, unsigned long long* stats, hipStream_t stream) {
+    if (L.gk_points != 15 || L.P.dim != L.P.N || !L.Md || L.Mold || !sets || !tabs || !set || !seg) return hipErrorInvalidValue;
+    TileSetsDerivArgs A;
+    A.Md = (double2*)L.Md;
+#elif EMME_TILE_SETS
+hipError_t launch_assemble_tile_sets(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
+                                     const int* seg, unsigned long long* worklist, unsigned int* worklist_count,
+                                     const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
+                                     hipStream_t stream) {
+    if (L.gk_points != 15 || L.P.dim != L.P.N || L.Md) return hipErrorNotSupported;
+    if (L.Mold || !sets || !tabs || !set || !seg) return hipErrorInvalidValue;  // (no fused secant)
+    TileSetsArgs A;
+#elif EMME_TILE_DERIV
 hipError_t launch_assemble_tile_deriv(const AssembleLaunch& L, unsigned long long* worklist, unsigned int* worklist_count,
                                       const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
                                       hipStream_t stream) {
@@ -494,8 +575,15 @@ hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* wor
     A.domega = (const double2*)L.domega;
 #endif
     if (nchunks < 1) return hipSuccess;
+#if EMME_TILE_SETS
+    A.sets = sets;
+    A.tabs = tabs;
+    A.set = set;
+    A.seg = seg;
+#else
     A.P = L.P;
     A.tab = L.tab;
+#endif
     A.pairs = (const ushort2*)L.pairs;
     A.npairs = L.npairs;
     A.worklist = worklist;
@@ -511,7 +599,11 @@ hipError_t launch_assemble_tile(const AssembleLaunch& L, unsigned long long* wor
     A.skip_lost = L.skip_lost;
     const int ntiles = (L.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
     const int ntg = (ntiles + TW - 1) / TW;
-#if EMME_TILE_DERIV
+#if EMME_TILE_SETS && EMME_TILE_DERIV
+    hipLaunchKernelGGL(k_assemble_tile_sets_deriv, dim3((unsigned)((long)ntg * nchunks)), dim3(64 * TW), 0, stream, A);
+#elif EMME_TILE_SETS
+    hipLaunchKernelGGL(k_assemble_tile_sets, dim3((unsigned)((long)ntg * nchunks)), dim3(64 * TW), 0, stream, A);
+#elif EMME_TILE_DERIV
     hipLaunchKernelGGL(k_assemble_tile_deriv, dim3((unsigned)((long)ntg * nchunks)), dim3(64 * TW), 0, stream, A);
 #else
     hipLaunchKernelGGL(k_assemble_tile, dim3((unsigned)((long)ntg * nchunks)), dim3(64 * TW), 0, stream, A);

@@ -48,7 +48,7 @@ void set_error(const std::string& msg);
 enum Kind { K_ASM = 0, K_LIN = 1, K_OTHER = 2, K_DEFER = 3, K_CACHE = 4, K_NULL = 5 };
 
 // kernel family of a plain fill, as emme_ctx_fill_mode reports it (include/emme_hip.h)
-enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4, FILL_TILE = 5, FILL_SETS = 6 };
+enum FillMode { FILL_NODES = 0, FILL_OMEGA_LANE = 1, FILL_CACHED_LANES = 2, FILL_CACHED_UNION = 3, FILL_DENSE = 4, FILL_TILE = 5, FILL_SETS = 6, FILL_TILE_SETS = 7 };
 
 // HBM node cache of one contour class (omi = +1, -1)
 struct NodeCacheClass {
@@ -82,6 +82,8 @@ struct emme_ctx {
     DeviceBuffer<DevParams> d_sets;    // the kernels' scalars, one per set
     DeviceBuffer<double> d_set_tabs;   // eta | g | b of every set, 3N doubles each
     DeviceBuffer<int> d_set;           // the set of every batch item of the current call
+    DeviceBuffer<int> d_set_lists;     // tile fill over sets: chunk table | position map | work-list
+                                       // segment offset of every set | the items left to k_assemble_sets
     // batch scratch
     DeviceBuffer<double> d_omega, d_domega, d_tr;
     DeviceBuffer<int> d_active, d_iters, d_info, d_status;
@@ -93,7 +95,9 @@ struct emme_ctx {
     std::vector<int> h_actidx; // its host image
     int last_fill_mode = -1;   // FillMode of the last plain fill (-1: none yet)
     int last_fill_listed = 0;  // work list the last fill reset and used (emme_ctx_last_deferred): 0 none, 1 the cached
-                               // fills' (d_worklist), 2 the tile fill's (d_tile_worklist)
+                               // fills' (d_worklist), 2 the tile fill's (d_tile_worklist), 3 the tile fill's over
+                               // parameter sets (d_tile_worklist in segments, a counter per bound set in d_tile_count)
+    int last_fill_counters = 1;  // ... and how many counters that work list has (3: the sets bound at that fill)
     int tile_shapes = EMME_TILE_SHAPES_ES15;  // shapes the option tile_uncached serves (emme_ctx_set_tile_shapes;
                                // EMME_TILE_SHAPES read at creation)
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
@@ -191,8 +195,8 @@ struct FillRequest {
     const unsigned long long* cost = nullptr;  // per item (interval count of its previous fill): orders the omegas
     bool newton_loop = false;            // a fill of a root search (skip_lost, wide items, deferred count published)
     bool force_uncached = false;         // omega-lane kernel whatever the batch size and the cache
-    const int* d_set = nullptr;          // set: item b belongs to the bound parameter set d_set[b] --
-    const int* host_set = nullptr;       // always the lanes-are-nodes fill over sets; and its host image
+    const int* d_set = nullptr;          // set: item b belongs to the bound parameter set d_set[b]: the
+    const int* host_set = nullptr;       // fills over sets (launch_sets); and its host image
     FillRequest(int n, const double* omega, double* M) : nbatch(n), d_omega(omega), d_M(M) {}
 };
 int fill(emme_ctx* c, const FillRequest& r);

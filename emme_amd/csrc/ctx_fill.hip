@@ -377,8 +377,74 @@ int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     return EMME_OK;
 }
 
-// A request whose items carry their own parameter set (r.d_set): k_assemble_sets, or with r.d_Md
-// k_assemble_sets_deriv.  Never the node cache, the omega-lane kernel or the tile fills; no fused secant.
+// A request over parameter sets that the table-free tile fill may serve: tile_fill_applies' rule,
+// with the accuracy precondition asked of EVERY bound set (any of them may be an item's), for electrostatic GK15 (the
+// sets readings exist for assemble_tile_text.hpp only).
+bool tile_sets_applies(const emme_ctx* c, const FillRequest& r) {
+    if (r.d_Md && c->opt.deriv_cached == 0) return false;
+    if (c->opt.tile_uncached == 0 || !tile_shape_is_es15(c) || !r.host_omega || !r.host_set) return false;
+    for (const emme_params_t& p : c->sets)
+        if (!(p.integration_accuracy >= 1e-9)) return false;
+    return true;
+}
+
+// The items of c->h_actidx (every group of them: one parameter set, one contour class, wl_min items or more) through
+// the tile fill over sets: chunk plan, lists to the device -- the omega order; behind the chunk table and the position
+// map, where the work-list segment of every set begins and, `rest` given, the items left to k_assemble_sets -- then
+// k_assemble_tile_sets or its _deriv form, then the segments from scratch by the list kernel of the same pick.
+// *d_rest <- the device image of `rest`.
+int launch_tile_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, const std::vector<int>* rest, const int** d_rest) {
+    const bool deriv = r.d_Md != nullptr;
+    const int nsets = (int)c->sets.size(), n = (int)c->h_actidx.size();
+    // a segment holds every integral of its set's items of this launch
+    std::vector<int> seg(nsets, 0), items(nsets, 0);
+    for (int b : c->h_actidx) ++items[r.host_set[b]];
+    size_t need = 0;
+    for (int s = 0; s < nsets; ++s) {
+        if (need > (size_t)std::numeric_limits<int>::max()) {
+            set_error("fill over parameter sets: the work list of the tile fill is too long");
+            return EMME_EINVAL;
+        }
+        seg[s] = (int)need, need += (size_t)c->npairs * items[s];
+    }
+    HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
+    HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int) * nsets));
+    const ChunkPlan plan = plan_tile_chunks(shape_of(c), c->h_actidx, r.host_omega, r.cost, c->h_chunks, r.host_set);
+    L.skip_lost = r.newton_loop && c->opt.skip_lost != 0;
+    const size_t n2 = c->h_chunks.size(), n_rest = rest ? rest->size() : 0, total = (size_t)n + n2 + nsets + n_rest;
+    HIP_TRY(c->d_set_lists.grow(sizeof(int) * (total - n)));
+    HIP_TRY(c->lists.reserve(total));
+    int* slot = nullptr;
+    HIP_TRY(c->lists.take(total, &slot));
+    std::copy(c->h_actidx.begin(), c->h_actidx.end(), slot);
+    std::copy(c->h_chunks.begin(), c->h_chunks.end(), slot + n);
+    std::copy(seg.begin(), seg.end(), slot + n + n2);
+    if (rest) std::copy(rest->begin(), rest->end(), slot + n + n2 + nsets);
+    HIP_TRY(launch_stage_ints(slot, c->d_actidx, n, c->d_set_lists, (int)(total - n), c->stream));
+    HIP_TRY(c->lists.read_on(c->stream));
+    const int* d_seg = c->d_set_lists + n2;
+    *d_rest = rest ? d_seg + nsets : nullptr;
+    HIP_TRY(hipMemsetAsync(c->d_tile_count, 0, sizeof(unsigned int) * nsets, c->stream));
+    c->last_fill_listed = 3, c->last_fill_counters = nsets;
+    {
+        ScopedSpan s(c, K_ASM);
+        HIP_TRY((deriv ? launch_assemble_tile_sets_deriv : launch_assemble_tile_sets)(
+            L, c->d_sets, c->d_set_tabs, r.d_set, d_seg, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_set_lists,
+            plan.nchunks, c->d_rounds, c->stream));
+    }
+    ScopedSpan s(c, K_DEFER);
+    HIP_TRY((deriv ? launch_assemble_sets_deriv_list : launch_assemble_sets_list)(L, c->d_sets, c->d_set_tabs, nsets,
+                                                                                  c->d_tile_worklist, d_seg, c->d_tile_count,
+                                                                                  c->stream));
+    return EMME_OK;
+}
+
+// A request whose items carry their own parameter set (r.d_set).  Never the node cache or the omega-lane
+// kernel; no fused secant.  Where tile_sets_applies, every (set, contour class) group of wl_min items or more -- the
+// project's threshold for "sharing node data between omegas pays" -- goes through the tile fill over sets (DESIGN.md
+// 13.7); the smaller groups, and every request that fails a precondition, through k_assemble_sets, or with r.d_Md
+// k_assemble_sets_deriv: in a second pass of the same call where both kinds of group exist.  The reported mode is
+// FILL_TILE_SETS when at least one group took the tile fill.
 int launch_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
     if (c->sets.empty() || !c->d_sets || !c->d_set_tabs) {
         set_error("fill over parameter sets: no sets are bound to the context");
@@ -389,8 +455,30 @@ int launch_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
         return EMME_EINVAL;
     }
     c->last_fill_listed = 0;
-    L.items_per_group = items_per_group_for(shape_of(c), r.nbatch);
     c->last_fill_mode = FILL_SETS;
+    bool all_tiled = false;
+    if (tile_sets_applies(c, r)) {
+        std::vector<int> group_items(2 * c->sets.size(), 0);
+        auto group_of = [&](int b) { return 2 * r.host_set[b] + contour_class(r.host_omega[2 * b]); };
+        for (int b : c->h_actidx) ++group_items[group_of(b)];
+        std::vector<int> tiled, rest(r.nbatch, 0);
+        for (int b : c->h_actidx) {
+            if (group_items[group_of(b)] >= c->opt.wl_min)
+                tiled.push_back(b);
+            else
+                rest[b] = 1;
+        }
+        if (!tiled.empty()) {
+            all_tiled = tiled.size() == c->h_actidx.size();
+            c->h_actidx = tiled;
+            const int* d_rest = nullptr;
+            EMME_TRY(launch_tile_sets(c, L, r, all_tiled ? nullptr : &rest, &d_rest));
+            c->last_fill_mode = FILL_TILE_SETS;
+            L.active = d_rest;
+        }
+    }
+    if (all_tiled) return EMME_OK;
+    L.items_per_group = items_per_group_for(shape_of(c), r.nbatch);
     ScopedSpan span(c, K_ASM);
     HIP_TRY((r.d_Md ? launch_assemble_sets_deriv : launch_assemble_sets)(L, c->d_sets, c->d_set_tabs, r.d_set, c->stream));
     return EMME_OK;

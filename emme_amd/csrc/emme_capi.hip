@@ -380,13 +380,16 @@ int emme_ctx_fill_mode(const emme_ctx_t* c) { return c ? c->last_fill_mode : EMM
 
 long long emme_ctx_last_deferred(emme_ctx_t* c) {
     if (!c) return EMME_EINVAL;
-    const unsigned int* src = c->last_fill_listed == 2 ? c->d_tile_count.get() : c->d_worklist_count.get();
+    const unsigned int* src = c->last_fill_listed >= 2 ? c->d_tile_count.get() : c->d_worklist_count.get();
     if (!c->last_fill_listed || !src) return 0;
     HIP_TRY(hipSetDevice(c->device));
-    unsigned int cnt = 0;
-    HIP_TRY(hipMemcpyAsync(&cnt, src, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    // (a tile fill over parameter sets has a counter per bound set: their sum)
+    std::vector<unsigned int> cnts(c->last_fill_listed == 3 ? (size_t)c->last_fill_counters : 1, 0u);
+    HIP_TRY(hipMemcpyAsync(cnts.data(), src, sizeof(unsigned int) * cnts.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
-    return (long long)cnt;
+    long long cnt = 0;
+    for (unsigned int v : cnts) cnt += v;
+    return cnt;
 }
 
 double emme_ctx_node_cache_gib(const emme_ctx_t* c) {
@@ -415,7 +418,7 @@ int emme_ctx_profile_read(emme_ctx_t* c, emme_profile_t* out, int reset) {
                     (double)r[4], (double)r[5], (double)r[6], (double)r[7], (double)r[8], (double)r[9],
                     (double)r[4] / (double)(r[0] + r[1] + 1), (double)r[5] / (double)(r[0] + 1),
                     (double)r[6] / (double)(r[1] + 1), (double)r[7] / (double)(r[0] + r[1] + 1));
-        if (c->tiled || c->last_fill_mode == FILL_TILE) {
+        if (c->tiled || c->last_fill_mode == FILL_TILE || c->last_fill_mode == FILL_TILE_SETS) {
             c->acc.union_rounds = (long long)(r[0] + r[1]);
             c->acc.dense_rounds = (long long)r[0], c->acc.sparse_rounds = (long long)r[1];
             c->acc.sparse_columns = (long long)r[2], c->acc.tile_tasks = (long long)r[3];
@@ -548,6 +551,8 @@ int emme_assemble_sets_batch(emme_ctx_t* c, const int* set, const double* omega,
     EMME_TRY(reset_fill_counters(c, nbatch));
     FillRequest r(nbatch, c->d_omega, dM);
     r.d_Md = dMp, r.d_set = c->d_set, r.host_set = set;
+    // (the tile fill over sets needs the omegas' host values for its chunks: DESIGN.md 13.7; host_active null = all)
+    if (!is_device_ptr(omega)) r.host_omega = omega;
     EMME_TRY(fill(c, r));
     if (!dev_out) {
         HIP_TRY(hipMemcpyAsync(M, dM, batch_bytes(c->dim, nbatch), hipMemcpyDeviceToHost, c->stream));

@@ -110,15 +110,18 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
 }
 
 ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const double* host_omega,
-                           const unsigned long long* cost, std::vector<int>& ch) {
+                           const unsigned long long* cost, std::vector<int>& ch, const int* host_set) {
     ChunkPlan plan;
     ch.clear();
     if (order.empty()) return plan;
-    // class by class; inside a class the order plan_order made (most expensive first where costs are given)
-    std::stable_partition(order.begin(), order.end(), [&](int b) { return contour_class(host_omega[2 * b]) == 0; });
+    // group by group -- (parameter set, contour class), or the class alone without host_set; inside a group the order
+    // plan_order made (most expensive first where costs are given)
+    auto group_of = [&](int b) { return 2L * (host_set ? host_set[b] : 0) + contour_class(host_omega[2 * b]); };
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return group_of(a) < group_of(b); });
     const size_t n = order.size();
-    size_t n0 = 0;
-    while (n0 < n && contour_class(host_omega[2 * order[n0]]) == 0) ++n0;
+    std::vector<size_t> ends;  // one past the last position of every group
+    for (size_t q = 1; q <= n; ++q)
+        if (q == n || group_of(order[q]) != group_of(order[q - 1])) ends.push_back(q);
     std::vector<unsigned long long> cs;
     for (int b : order) cs.push_back(cost ? cost[b] : 1ull);
     std::vector<unsigned long long> sorted = cs;
@@ -130,7 +133,12 @@ ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const do
     const int tile_cap = 16 / s.nm;
     int cap_all = tile_cap;
     const long ntiles = (s.npairs + 15) / 16;
-    auto chunks_at = [&](int cap) { return (long)((n0 + cap - 1) / cap + (n - n0 + cap - 1) / cap); };
+    auto chunks_at = [&](int cap) {
+        long k = 0;
+        size_t first = 0;
+        for (size_t end : ends) k += (long)((end - first + cap - 1) / cap), first = end;
+        return k;
+    };
     while (cap_all > 2 && chunks_at(cap_all) * ntiles < (long)s.dense_min_tasks) cap_all >>= 1;
     // an omega that costs dense_cost_ratio times the typical one gets a narrow chunk: its trees overlap nobody's
     struct Chunk {
@@ -138,8 +146,10 @@ ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const do
         unsigned long long cost;
     };
     std::vector<Chunk> cut;
+    size_t g = 0;
     for (size_t q = 0; q < n;) {
-        const size_t end = q < n0 ? n0 : n;  // a chunk ends where its class does
+        while (ends[g] <= q) ++g;
+        const size_t end = ends[g];  // a chunk ends where its group does
         int cap = cap_all;
         while (cap > 2 && (double)cs[q] * cap > typical * (tile_cap * s.dense_cost_ratio)) cap >>= 1;
         const int m = (int)std::min<size_t>((size_t)cap, end - q);

@@ -55,7 +55,9 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
 // <= 16 omegas that never mix contour classes (contour_class(host_omega[2 b])): the dense_min_tasks halving on the
 // launch's chunk count, the dense_cost_ratio cut where costs are given.  chunks <- the dense fill's table, (first
 // position, size) per chunk with the most expensive chunk first, and behind it position -> (chunk << 8 | column).
+// host_set given (a fill over parameter sets, DESIGN.md 13.7: item b belongs to set host_set[b]): the groups are the
+// (set, contour class) pairs, in ascending order of the set, and a chunk mixes neither sets nor classes.
 ChunkPlan plan_tile_chunks(const FillShape& s, std::vector<int>& order, const double* host_omega,
-                           const unsigned long long* cost, std::vector<int>& chunks);
+                           const unsigned long long* cost, std::vector<int>& chunks, const int* host_set = nullptr);
 
 }  // namespace emme

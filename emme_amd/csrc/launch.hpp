@@ -180,6 +180,28 @@ hipError_t launch_assemble_sets(const AssembleLaunch& L, const DevParams* sets, 
 hipError_t launch_assemble_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
                                       hipStream_t stream);
 
+// ---- table-free tile fill over parameter sets (electrostatic GK15): the two sets readings of
+// assemble_tile_text.hpp -> assemble_tile_sets.hip (M), assemble_tile_sets_deriv.hip (M and the exact dM/domega: L.Md
+// set).  act_idx / chunks as for launch_assemble_tile, every chunk of ONE set and one contour class (plan_tile_chunks
+// with host_set); sets / tabs / set as for launch_assemble_sets.  The work list has a segment per set: seg[s] (device)
+// is where the segment of set s begins, worklist_count[s] its counter.  L.tab is not used; no fused secant
+// (hipErrorInvalidValue if L.Mold is set).  The segments are finished by the two readings of
+// assemble_sets_list_text.hpp -> assemble_sets_list.hip, assemble_sets_list_deriv.hip: blockIdx.y = set. ------
+hipError_t launch_assemble_tile_sets(const AssembleLaunch& L, const DevParams* sets, const double* tabs, const int* set,
+                                     const int* seg, unsigned long long* worklist, unsigned int* worklist_count,
+                                     const int* act_idx, const void* chunks, int nchunks, unsigned long long* stats,
+                                     hipStream_t stream);
+hipError_t launch_assemble_tile_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs,
+                                           const int* set, const int* seg, unsigned long long* worklist,
+                                           unsigned int* worklist_count, const int* act_idx, const void* chunks,
+                                           int nchunks, unsigned long long* stats, hipStream_t stream);
+hipError_t launch_assemble_sets_list(const AssembleLaunch& L, const DevParams* sets, const double* tabs, int nsets,
+                                     const unsigned long long* worklist, const int* seg, const unsigned int* counts,
+                                     hipStream_t stream);
+hipError_t launch_assemble_sets_deriv_list(const AssembleLaunch& L, const DevParams* sets, const double* tabs, int nsets,
+                                           const unsigned long long* worklist, const int* seg, const unsigned int* counts,
+                                           hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

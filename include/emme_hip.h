@@ -191,7 +191,9 @@ int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
 /* Kernel family used by the last fill: 0 lanes-are-nodes, 1 omega-lane, 2 HBM node cache
  * (independent lanes), 3 HBM node cache + phase table, union walk, 4 HBM node cache (tiled) +
  * dense fill on the FP64 matrix cores, 5 table-free tile fill on the FP64 matrix cores, 6 lanes-are-nodes over
- * parameter sets (emme_assemble_sets_batch, emme_solve_roots_sets; with or without the derivative). */
+ * parameter sets (emme_assemble_sets_batch, emme_solve_roots_sets; with or without the derivative), 7 table-free
+ * tile fill over parameter sets, a set per omega chunk (the same two entry points, with or without the derivative:
+ * at least one (set, contour class) group of the call took it; see the routing rule there). */
 int emme_ctx_fill_mode(const emme_ctx_t* ctx);
 /* Integrals the last fill handed to the work list (the cached fills and the tile fill finish them in a second
  * launch, from scratch); 0 for fills that have no work list.  Synchronises the context's stream.  < 0: an EMME_* code. */
@@ -285,9 +287,16 @@ int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, doubl
  * Every other entry point works on the ONE parameter set the context was created with.  These bind further sets to
  * the context and let every item of a batch name the set it belongs to: one launch then fills (and one search
  * iterates) items of different sets side by side, through k_assemble_sets / k_assemble_sets_deriv -- the
- * lanes-are-nodes fill, never the node cache, the omega-lane kernel or the tile fills.  All sets of a context share
+ * lanes-are-nodes fill, never the node cache or the omega-lane kernel.  All sets of a context share
  * its SHAPE: npoints, whether beta_e == 0, integration_start_points and iteration_method; everything else may differ,
- * conf and length included.  Entry points without `set` behave exactly as before, whether or not sets are bound. */
+ * conf and length included.  Entry points without `set` behave exactly as before, whether or not sets are bound.
+ * Routing: with the option tile_uncached on an electrostatic GK15 context whose bound sets ALL have
+ * integration_accuracy >= 1e-9, and omegas the host knows (a host `omega` pointer; a root search), the items are
+ * grouped by (set, contour class) and every group of at least wl_min items goes through k_assemble_tile_sets
+ * (k_assemble_tile_sets_deriv for a derivative request, which asks for deriv_cached as well) -- the table-free tile
+ * fill with ONE set per omega chunk, fill mode 7.  Smaller groups of the same call, and every call that fails one of
+ * the conditions, keep k_assemble_sets bit for bit (mode 6 when no group took the tile fill).  With default options
+ * nothing changes. */
 /* host only, no device: EMME_OK if b has a's shape (npoints, beta_e == 0 alike, integration_start_points,
  * iteration_method), else EMME_EINVAL with emme_last_error naming the first field that differs */
 int emme_params_same_shape(const emme_params_t* a, const emme_params_t* b);
