@@ -1,6 +1,6 @@
 // assemble_common.hpp -- the leaf pieces that the fill kernels share (assemble.hip, assemble_wl.hip,
 // assemble_cached.hip, assemble_dense.hip, assemble_dense_deriv.hip, the table-free tile fills assemble_tile*.hip
-// through assemble_tile_text.hpp and assemble_tile_shape_text.hpp; probe.hip for the tables): the Gauss-Kronrod
+// through assemble_tile_text.hpp; probe.hip for the tables): the Gauss-Kronrod
 // tables, the caps, the accept / split rule of the adaptive quadrature, kappa_e, the pair weights, the three ways an
 // entry of M is stored, the small helpers of the dense fills and the leaves of the tile fills.  The kernel BODIES stay
 // separate texts: what is here are forceinline leaves that perform the same operations in the same
@@ -270,7 +270,7 @@ __device__ __forceinline__ void interval_bounds_d(int depth, unsigned long long 
     }
 }
 
-// ---- leaves of the table-free tile fills (assemble_tile_text.hpp, assemble_tile_shape_text.hpp) ----------------------
+// ---- leaves of the table-free tile fills (assemble_tile_text.hpp) ------------------------------------------------------
 // what the lanes of a wave wrote to LDS is visible to every lane of the wave afterwards
 __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");

@@ -1,9 +1,11 @@
 // assemble_tile_shape_deriv.hip -- M(omega) and the exact dM/domega from one table-free tile fill for electromagnetic
 // contexts and the 31-point rule: k_assemble_tile_shape_deriv<PTS, NM> and
-// launch_assemble_tile_shape_deriv, the derivative reading of assemble_tile_shape_text.hpp, in their own translation
-// unit (DESIGN.md 12.2), and the kernel that finishes the integrals they hand over.
+// launch_assemble_tile_shape_deriv, the derivative shape reading of assemble_tile_text.hpp, in their own translation
+// unit (DESIGN.md 12.2.1), and the kernel that finishes the integrals they hand over.
+#define EMME_TILE_SHAPE 1
+#define EMME_TILE_SETS 0
 #define EMME_TILE_DERIV 1
-#include "assemble_tile_shape_text.hpp"
+#include "assemble_tile_text.hpp"
 #include "launch_grid.hpp"
 
 namespace emme {

@@ -128,10 +128,10 @@ hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheV
 hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
                                       const unsigned int* count, hipStream_t stream);
 
-// ---- table-free tile fill (no node cache).  Two texts, one per shape family, each compiled as a plain and a
-// derivative translation unit: assemble_tile_text.hpp -> assemble_tile.hip, assemble_tile_deriv.hip
-// (electrostatic GK15); assemble_tile_shape_text.hpp -> assemble_tile_shape.hip, assemble_tile_shape_deriv.hip
-// (electromagnetic, GK31).  A plain launcher refuses L.Md with hipErrorNotSupported, a derivative launcher a missing
+// ---- table-free tile fill (no node cache).  One text, assemble_tile_text.hpp, read by one thin translation unit per
+// kernel: EMME_TILE_SHAPE 0 -> assemble_tile.hip, assemble_tile_deriv.hip (electrostatic GK15),
+// EMME_TILE_SHAPE 1 -> assemble_tile_shape.hip, assemble_tile_shape_deriv.hip (electromagnetic, GK31); the parameter-set
+// readings are further down.  A plain launcher refuses L.Md with hipErrorNotSupported, a derivative launcher a missing
 // L.Md or a set L.Mold with hipErrorInvalidValue; both answer so to a shape of the other family. ------
 // -- assemble_tile.hip: electrostatic GK15, plain fills --
 // act_idx: the launch's omegas; chunks: int2 (first position, size <= 16) per chunk, ONE contour class per chunk

@@ -21,8 +21,25 @@ def _code_lines(path):
     return [line.split("//")[0] for line in path.read_text().splitlines()]
 
 
+# the six thin units of the table-free tile fill: each is one reading of assemble_tile_text.hpp
+TILE_UNITS = ["assemble_tile.hip", "assemble_tile_deriv.hip", "assemble_tile_sets.hip", "assemble_tile_sets_deriv.hip",
+              "assemble_tile_shape.hip", "assemble_tile_shape_deriv.hip"]
+TILE_SELECTORS = {"EMME_TILE_SHAPE", "EMME_TILE_SETS", "EMME_TILE_DERIV"}
+
+
 def test_there_are_texts():
-    assert len(TEXTS) >= 5, TEXTS
+    assert TEXTS == ["assemble_deriv_list_text.hpp", "assemble_nodes_text.hpp", "assemble_sets_list_text.hpp",
+                     "assemble_tile_text.hpp", "assemble_wl_text.hpp"], TEXTS
+
+
+def test_every_tile_unit_defines_the_three_selectors():
+    """Exactly the text's three selectors, each once and to 0 or 1, before the unit reads the text."""
+    for u in TILE_UNITS:
+        lines = _code_lines(CSRC / u)
+        inc = next(k for k, line in enumerate(lines) if re.match(r'\s*#\s*include\s+"assemble_tile_text\.hpp"', line))
+        defs = [m.group(1) for line in lines[:inc] for m in [re.match(r"\s*#\s*define\s+(\w+)\s+[01]\s*$", line)] if m]
+        assert sorted(defs) == sorted(TILE_SELECTORS), (u, defs)
+        assert not any(re.match(r"\s*#\s*define\s+EMME_TILE_", line) for line in lines[inc:]), u
 
 
 def test_every_text_is_a_makefile_header():
