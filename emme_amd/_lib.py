@@ -548,7 +548,8 @@ class Context:
 
     def set_tile_shapes(self, shapes: int) -> None:
         """Which shapes the option tile_uncached serves: TILE_SHAPES_ES15 (default: electrostatic GK15 only) or
-        TILE_SHAPES_ALL (electromagnetic and GK31 contexts as well, k_assemble_tile_shape).  From the next call on."""
+        TILE_SHAPES_ALL (electromagnetic and GK31 contexts as well: k_assemble_tile_shape, and for calls over bound
+        parameter sets k_assemble_tile_shape_sets, fill mode 7).  From the next call on."""
         _check(self.lib.emme_ctx_set_tile_shapes(self.h, int(shapes)))
 
     def tile_shapes(self) -> int:
@@ -624,6 +625,8 @@ class Context:
         if mode == 6:
             return f"k_assemble_sets<{pts}>"
         if mode == 7:
+            if em or pts != 15:
+                return "k_assemble_tile_shape_sets<%d, %d>" % (pts, 3 if em else 1)
             return "k_assemble_tile_sets"
         return f"k_assemble<{pts}, false>"
 

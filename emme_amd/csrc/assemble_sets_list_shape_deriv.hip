@@ -1,0 +1,7 @@
+// assemble_sets_list_shape_deriv.hip -- M and M' of the integrals the derivative tile fill over parameter sets handed
+// over on electromagnetic and GK31 contexts, from scratch: k_assemble_sets_deriv_list_shape<PTS> and
+// launch_assemble_sets_deriv_list_shape, the derivative shape reading of assemble_sets_list_text.hpp.  Its own
+// translation unit, as assemble_sets_list_deriv.hip.
+#define EMME_SETS_LIST_SHAPE 1
+#define EMME_SETS_LIST_DERIV 1
+#include "assemble_sets_list_text.hpp"

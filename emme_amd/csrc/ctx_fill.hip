@@ -378,11 +378,12 @@ int fill_uncached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r) {
 }
 
 // A request over parameter sets that the table-free tile fill may serve: tile_fill_applies' rule,
-// with the accuracy precondition asked of EVERY bound set (any of them may be an item's), for electrostatic GK15 (the
-// sets readings exist for assemble_tile_text.hpp only).
+// with the accuracy precondition asked of EVERY bound set (any of them may be an item's): electrostatic GK15, and once
+// the context's tile shapes are EMME_TILE_SHAPES_ALL electromagnetic and GK31 contexts too.
 bool tile_sets_applies(const emme_ctx* c, const FillRequest& r) {
     if (r.d_Md && c->opt.deriv_cached == 0) return false;
-    if (c->opt.tile_uncached == 0 || !tile_shape_is_es15(c) || !r.host_omega || !r.host_set) return false;
+    if (c->opt.tile_uncached == 0 || !r.host_omega || !r.host_set) return false;
+    if (!(tile_shape_is_es15(c) || c->tile_shapes == EMME_TILE_SHAPES_ALL)) return false;
     for (const emme_params_t& p : c->sets)
         if (!(p.integration_accuracy >= 1e-9)) return false;
     return true;
@@ -391,21 +392,23 @@ bool tile_sets_applies(const emme_ctx* c, const FillRequest& r) {
 // The items of c->h_actidx (every group of them: one parameter set, one contour class, wl_min items or more) through
 // the tile fill over sets: chunk plan, lists to the device -- the omega order; behind the chunk table and the position
 // map, where the work-list segment of every set begins and, `rest` given, the items left to k_assemble_sets -- then
-// k_assemble_tile_sets or its _deriv form, then the segments from scratch by the list kernel of the same pick.
+// the kernel picked by (derivative request?, shape) -- k_assemble_tile_sets, k_assemble_tile_shape_sets<PTS, NM> or their
+// _deriv forms -- then the segments from scratch by the list kernel of the same pick.
 // *d_rest <- the device image of `rest`.
 int launch_tile_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, const std::vector<int>* rest, const int** d_rest) {
-    const bool deriv = r.d_Md != nullptr;
+    const bool deriv = r.d_Md != nullptr, es15 = tile_shape_is_es15(c);
     const int nsets = (int)c->sets.size(), n = (int)c->h_actidx.size();
-    // a segment holds every integral of its set's items of this launch
+    // a segment holds every integral of its set's items of this launch: npairs * nm per item
     std::vector<int> seg(nsets, 0), items(nsets, 0);
     for (int b : c->h_actidx) ++items[r.host_set[b]];
     size_t need = 0;
     for (int s = 0; s < nsets; ++s) {
+        // (a segment's begin and every position inside it are ints on the device)
+        seg[s] = (int)need, need += (size_t)c->npairs * c->nm * items[s];
         if (need > (size_t)std::numeric_limits<int>::max()) {
             set_error("fill over parameter sets: the work list of the tile fill is too long");
             return EMME_EINVAL;
         }
-        seg[s] = (int)need, need += (size_t)c->npairs * items[s];
     }
     HIP_TRY(c->d_tile_worklist.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_tile_count.grow(sizeof(unsigned int) * nsets));
@@ -428,14 +431,16 @@ int launch_tile_sets(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, const
     c->last_fill_listed = 3, c->last_fill_counters = nsets;
     {
         ScopedSpan s(c, K_ASM);
-        HIP_TRY((deriv ? launch_assemble_tile_sets_deriv : launch_assemble_tile_sets)(
+        const auto kernel = deriv ? (es15 ? launch_assemble_tile_sets_deriv : launch_assemble_tile_shape_sets_deriv)
+                                  : (es15 ? launch_assemble_tile_sets : launch_assemble_tile_shape_sets);
+        HIP_TRY(kernel(
             L, c->d_sets, c->d_set_tabs, r.d_set, d_seg, c->d_tile_worklist, c->d_tile_count, c->d_actidx, c->d_set_lists,
             plan.nchunks, c->d_rounds, c->stream));
     }
     ScopedSpan s(c, K_DEFER);
-    HIP_TRY((deriv ? launch_assemble_sets_deriv_list : launch_assemble_sets_list)(L, c->d_sets, c->d_set_tabs, nsets,
-                                                                                  c->d_tile_worklist, d_seg, c->d_tile_count,
-                                                                                  c->stream));
+    const auto list = deriv ? (es15 ? launch_assemble_sets_deriv_list : launch_assemble_sets_deriv_list_shape)
+                            : (es15 ? launch_assemble_sets_list : launch_assemble_sets_list_shape);
+    HIP_TRY(list(L, c->d_sets, c->d_set_tabs, nsets, c->d_tile_worklist, d_seg, c->d_tile_count, c->stream));
     return EMME_OK;
 }
 

@@ -202,6 +202,32 @@ hipError_t launch_assemble_sets_deriv_list(const AssembleLaunch& L, const DevPar
                                            const unsigned long long* worklist, const int* seg, const unsigned int* counts,
                                            hipStream_t stream);
 
+// ---- the same for electromagnetic and GK31 contexts: the two shape sets readings of
+// assemble_tile_text.hpp -> assemble_tile_shape_sets.hip (M), assemble_tile_shape_sets_deriv.hip (M and the exact
+// dM/domega: L.Md set); k_assemble_tile_shape_sets<PTS, NM> and its _deriv form for (15, 3), (31, 1), (31, 3).  The
+// argument lists and error answers are those of the two launchers above, the shapes those of launch_assemble_tile_shape
+// (hipErrorNotSupported / hipErrorInvalidValue for electrostatic GK15).  Chunks hold <= 16 / nm omegas of ONE set and one
+// class; a work-list entry is (b << 32) | (pair nm + moment), so the segment of a set must hold npairs * nm entries per
+// item of the set.  The segments are finished by the two shape readings of assemble_sets_list_text.hpp
+// (EMME_SETS_LIST_SHAPE 1) -> assemble_sets_list_shape.hip, assemble_sets_list_shape_deriv.hip:
+// k_assemble_sets_list_shape<PTS> / k_assemble_sets_deriv_list_shape<PTS>, blockIdx.y = set, a lane group of 16 (GK15)
+// or 32 (GK31) per entry, every moment's scatter.  Their launchers refuse electrostatic GK15 as the two above refuse
+// every other shape. ------
+hipError_t launch_assemble_tile_shape_sets(const AssembleLaunch& L, const DevParams* sets, const double* tabs,
+                                           const int* set, const int* seg, unsigned long long* worklist,
+                                           unsigned int* worklist_count, const int* act_idx, const void* chunks,
+                                           int nchunks, unsigned long long* stats, hipStream_t stream);
+hipError_t launch_assemble_tile_shape_sets_deriv(const AssembleLaunch& L, const DevParams* sets, const double* tabs,
+                                                 const int* set, const int* seg, unsigned long long* worklist,
+                                                 unsigned int* worklist_count, const int* act_idx, const void* chunks,
+                                                 int nchunks, unsigned long long* stats, hipStream_t stream);
+hipError_t launch_assemble_sets_list_shape(const AssembleLaunch& L, const DevParams* sets, const double* tabs, int nsets,
+                                           const unsigned long long* worklist, const int* seg,
+                                           const unsigned int* counts, hipStream_t stream);
+hipError_t launch_assemble_sets_deriv_list_shape(const AssembleLaunch& L, const DevParams* sets, const double* tabs,
+                                                 int nsets, const unsigned long long* worklist, const int* seg,
+                                                 const unsigned int* counts, hipStream_t stream);
+
 // tr(A_b^-1 B_b) by partial-pivot LU of the augmented system [A | B]; A, B destroyed.
 hipError_t launch_trace_solve(int n, int nbatch, double* A, double* B, const int* active,
                               double* tr /*2*nbatch*/, int* info, hipStream_t stream);

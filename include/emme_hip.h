@@ -180,7 +180,10 @@ void emme_release_pooled_memory(void);
  * k_assemble_tile_shape_deriv<PTS, NM>, also on contexts that have a node cache, which no derivative
  * request of these shapes reads; with deriv_cached = 0 they stay on the omega-lane derivative kernel.  No effect while
  * tile_uncached = 0.  Not a layout setting: it may change on a live context and takes effect from the next call.
- * emme_ctx_fill_mode reports 5 for either kernel. */
+ * emme_ctx_fill_mode reports 5 for either kernel.  Calls over bound parameter sets are served too:
+ * with EMME_TILE_SHAPES_ALL the routing rule of emme_assemble_sets_batch / emme_solve_roots_sets holds on
+ * electromagnetic and GK31 contexts as well, through k_assemble_tile_shape_sets<PTS, NM> and its _deriv form, fill
+ * mode 7; with EMME_TILE_SHAPES_ES15 such calls stay on k_assemble_sets. */
 #define EMME_TILE_SHAPES_ES15 0 /* default: tile_uncached serves electrostatic GK15 only */
 #define EMME_TILE_SHAPES_ALL  1 /* tile_uncached serves electromagnetic and GK31 contexts as well */
 int emme_ctx_set_tile_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range */
@@ -193,7 +196,8 @@ int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
  * dense fill on the FP64 matrix cores, 5 table-free tile fill on the FP64 matrix cores, 6 lanes-are-nodes over
  * parameter sets (emme_assemble_sets_batch, emme_solve_roots_sets; with or without the derivative), 7 table-free
  * tile fill over parameter sets, a set per omega chunk (the same two entry points, with or without the derivative:
- * at least one (set, contour class) group of the call took it; see the routing rule there). */
+ * at least one (set, contour class) group of the call took it; see the routing rule there; k_assemble_tile_sets on
+ * electrostatic GK15, k_assemble_tile_shape_sets<PTS, NM> on electromagnetic and GK31 contexts). */
 int emme_ctx_fill_mode(const emme_ctx_t* ctx);
 /* Integrals the last fill handed to the work list (the cached fills and the tile fill finish them in a second
  * launch, from scratch); 0 for fills that have no work list.  Synchronises the context's stream.  < 0: an EMME_* code. */
@@ -296,7 +300,10 @@ int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, doubl
  * (k_assemble_tile_sets_deriv for a derivative request, which asks for deriv_cached as well) -- the table-free tile
  * fill with ONE set per omega chunk, fill mode 7.  Smaller groups of the same call, and every call that fails one of
  * the conditions, keep k_assemble_sets bit for bit (mode 6 when no group took the tile fill).  With default options
- * nothing changes. */
+ * nothing changes.  Electromagnetic and GK31 contexts follow the same rule once their tile shapes are
+ * EMME_TILE_SHAPES_ALL (emme_ctx_set_tile_shapes): k_assemble_tile_shape_sets<PTS, NM> /
+ * k_assemble_tile_shape_sets_deriv<PTS, NM>, a chunk of an electromagnetic context holding 5 omegas x 3 moments of one
+ * set; with the shapes at their default they stay on k_assemble_sets whatever tile_uncached says. */
 /* host only, no device: EMME_OK if b has a's shape (npoints, beta_e == 0 alike, integration_start_points,
  * iteration_method), else EMME_EINVAL with emme_last_error naming the first field that differs */
 int emme_params_same_shape(const emme_params_t* a, const emme_params_t* b);
