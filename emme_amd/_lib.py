@@ -218,6 +218,9 @@ def load():
     lib.emme_find_roots_in_contour.argtypes = [P, C.POINTER(Contour), C.c_double, C.c_int, C.c_int, P, P, P, P, P, P]
     lib.emme_contour_moments_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P, P, P]
     lib.emme_contour_eigs.argtypes = [C.c_int, C.c_int, P, P, C.c_double, C.c_int, P, P, P]
+    lib.emme_contour_moments_groups.argtypes = [P, C.c_int, C.c_int, P, P, C.c_int, P, P, C.c_int, P, P, P, P, P]
+    lib.emme_find_roots_in_contours_sets.argtypes = [P, C.c_int, P, P, C.c_int, C.c_double, C.c_int, C.c_int,
+                                                     P, P, P, P, P, P, P]
     _LIB = lib
     return lib
 
@@ -871,6 +874,65 @@ class Context:
         _check(self.lib.emme_contour_moments_batch(self.h, n, nq, ptr, z.ctypes.data, w.ctypes.data, L, Vp,
                                                    A0.ctypes.data, A1.ctypes.data, ld.ctypes.data, info.ctypes.data))
         return A0, A1, ld, info
+
+    def contour_moments_groups(self, M, group, ngroups, z, w, L, V=None):
+        """contour_moments with the matrices dealt into ngroups groups (group[j] in [0, ngroups), any order): returns
+        (A0, A1, logdet, info) with A0, A1 of shape [ngroups, n, L], group g summed over its matrices in ascending j
+        (info != 0 left out, an empty group zero)."""
+        M = np.ascontiguousarray(_c128(M))
+        nq, n = M.shape[0], M.shape[1]
+        g = np.ascontiguousarray(np.atleast_1d(group), dtype=np.int32)
+        z = _c128(np.atleast_1d(z))
+        w = _c128(np.atleast_1d(w))
+        if g.shape[0] != nq or z.shape[0] != nq or w.shape[0] != nq:
+            raise ValueError("group, z and w need one entry per matrix")
+        Vp = None
+        if V is not None:
+            V = np.ascontiguousarray(_c128(V))
+            if V.shape != (n, L):
+                raise ValueError("V must be n x L")
+            Vp = V.ctypes.data
+        A0 = np.zeros((max(ngroups, 0), n, L), dtype=np.complex128)
+        A1 = np.zeros((max(ngroups, 0), n, L), dtype=np.complex128)
+        ld = np.zeros(nq, dtype=np.complex128)
+        info = np.zeros(nq, dtype=np.int32)
+        _check(self.lib.emme_contour_moments_groups(self.h, n, nq, M.ctypes.data, g.ctypes.data, ngroups, z.ctypes.data,
+                                                    w.ctypes.data, L, Vp, A0.ctypes.data, A1.ctypes.data, ld.ctypes.data,
+                                                    info.ctypes.data))
+        return A0, A1, ld, info
+
+    def find_roots_in_contours_sets(self, set, centers, semi_axes, exact=False, tol=None, step_limit=None, max_roots=64,
+                                    contours=None):
+        """find_roots_in_contour for many (parameter set, contour) items in one lock-step call: item k searches the
+        ellipse centers[k], semi_axes[k] = (a, b) on the bound set set[k]; contours: per-item keyword dicts (points,
+        max_points, probes, rank_tol) or None.  exact: polish by the Newton search on the exact derivative.  Returns a
+        list of dicts shaped like find_roots_in_contour's, plus status (0, or the error that took the item out)."""
+        st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+        n = st.shape[0]
+        centers = np.atleast_1d(centers)
+        semi_axes = np.asarray(semi_axes, dtype=np.float64).reshape(-1, 2)
+        contours = [{}] * n if contours is None else list(contours)
+        if len(centers) != n or len(semi_axes) != n or len(contours) != n:
+            raise ValueError("centers, semi_axes and contours need one entry per item")
+        cts = (Contour * max(n, 1))(*[contour_default(center=complex(centers[k]), semi_axes=tuple(semi_axes[k]),
+                                                      **(contours[k] or {})) for k in range(n)])
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros((max(n, 1), max_roots), dtype=np.complex128)
+        iters = np.zeros((max(n, 1), max_roots), dtype=np.int32)
+        info = np.zeros((max(n, 1), max_roots), dtype=np.int32)
+        nr, w, pu, status = (np.zeros(max(n, 1), dtype=np.int32) for _ in range(4))
+        _check(self.lib.emme_find_roots_in_contours_sets(self.h, n, st.ctypes.data, C.cast(cts, C.c_void_p), int(bool(exact)),
+                                                         tol, step_limit, max_roots, roots.ctypes.data, iters.ctypes.data,
+                                                         info.ctypes.data, nr.ctypes.data, w.ctypes.data, pu.ctypes.data,
+                                                         status.ctypes.data))
+        out = []
+        for k in range(n):
+            m = min(int(nr[k]), max_roots)
+            out.append({"roots": roots[k, :m].copy(), "iters": iters[k, :m].copy(), "info": info[k, :m].copy(),
+                        "n_roots": int(nr[k]), "winding": int(w[k]), "points_used": int(pu[k]),
+                        "complete": bool(w[k] >= 0 and nr[k] == w[k]), "status": int(status[k])})
+        return out
 
     def final_matrix(self, b=0):
         M = np.zeros((self.dim, self.dim), dtype=np.complex128)

@@ -171,6 +171,149 @@ int contour_winding(const double* args, int N, double max_step, bool* resolved, 
     return std::isfinite(W) ? (int)std::nearbyint(W) : -1;
 }
 
+const char* contour_arg_error(const emme_contour_t* ct) {
+    auto pow2 = [](int x) { return x > 0 && (x & (x - 1)) == 0; };
+    if (ct->size != (int)sizeof(emme_contour_t)) return "emme_contour_t of the wrong size (fill it with emme_contour_default)";
+    const double cx = ct->center[0], cy = ct->center[1], ea = ct->semi_axes[0], eb = ct->semi_axes[1];
+    if (!(ea > 0.0 && eb > 0.0) || !std::isfinite(ea) || !std::isfinite(eb) || !std::isfinite(cx) || !std::isfinite(cy))
+        return "the semi-axes must be positive and finite";
+    if (!(std::fabs(cx) > ea))
+        return "the ellipse reaches Re omega = 0 (|Re c| <= a); M(omega) is analytic in one half-plane only";
+    if (!pow2(ct->points) || ct->points < 4 || !pow2(ct->max_points) || ct->max_points < ct->points)
+        return "points and max_points must be powers of two, 4 <= points <= max_points";
+    if (ct->probes < 1 || ct->probes > 64 || !(ct->rank_tol > 0.0 && ct->rank_tol < 1.0))
+        return "probes must lie in 1 .. 64 and rank_tol in (0, 1)";
+    return nullptr;
+}
+
+namespace {
+double norm_radius(const emme_contour_t& ct, double re, double im) {
+    return std::hypot((re - ct.center[0]) / ct.semi_axes[0], (im - ct.center[1]) / ct.semi_axes[1]);
+}
+}  // namespace
+
+void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::vector<double>& guesses) {
+    const double rho = std::max(ct.semi_axes[0], ct.semi_axes[1]);
+    for (int q = 0; q < k; ++q) {
+        const double re = ct.center[0] + rho * mu[2 * q], im = ct.center[1] + rho * mu[2 * q + 1];
+        if (std::isfinite(re) && std::isfinite(im) && norm_radius(ct, re, im) < 1.5) guesses.push_back(re), guesses.push_back(im);
+    }
+}
+
+std::vector<ContourRoot> contour_keep_roots(const emme_contour_t& ct, double tol, int step_limit, int ng, const double* r,
+                                            const int* its, const int* inf, const double* path) {
+    // a chain that used every step converged only if its last step was below tol (src/main.cpp:53-56)
+    auto converged = [&](int q) {
+        if (its[q] <= step_limit) return true;
+        if (step_limit < 1) return false;
+        const double* w = &path[2 * ((size_t)q * (step_limit + 1) + step_limit)];
+        return std::hypot(w[0] - w[-2], w[1] - w[-1]) < tol * std::hypot(w[0], w[1]);
+    };
+    std::vector<ContourRoot> found;
+    for (int q = 0; q < ng; ++q) {
+        if (inf[q] != 0 || !converged(q) || !(norm_radius(ct, r[2 * q], r[2 * q + 1]) < 1.0)) continue;
+        bool dup = false;
+        for (const ContourRoot& f : found)
+            dup |= std::hypot(f.re - r[2 * q], f.im - r[2 * q + 1]) <= 10.0 * tol * std::hypot(r[2 * q], r[2 * q + 1]);
+        if (!dup) found.push_back({r[2 * q], r[2 * q + 1], its[q], inf[q]});
+    }
+    std::stable_sort(found.begin(), found.end(), [](const ContourRoot& x, const ContourRoot& y) { return x.im > y.im; });
+    return found;
+}
+
+// ---- the round plan of a region search over (set, contour) items -------------------------------
+ContourRounds::ContourRounds(int nitems, const int* set, const emme_contour_t* contours) : items(nitems) {
+    for (int k = 0; k < nitems; ++k) items[k].set = set[k], items[k].ct = contours[k], items[k].L = contours[k].probes;
+}
+
+bool ContourRounds::plan_nodes() {
+    r_first = nodes();
+    r_item.clear(), r_set.clear(), r_omega.clear();
+    for (int k = 0; k < (int)items.size(); ++k) {
+        Item& it = items[k];
+        if (it.dropped || !it.adding) continue;
+        const int cap = it.ct.max_points;
+        const int add = it.N == 0 ? it.ct.points : it.N;
+        for (int j = 0; j < add; ++j) {
+            // the start nodes t_j = 2 pi j / N; later the midpoints of the N nodes held
+            const int m = it.N == 0 ? j * (cap / add) : (2 * j + 1) * (cap / (2 * it.N));
+            const double t = 2.0 * M_PI * m / cap;
+            it.nodes.push_back(nodes()), it.node_m.push_back(m);
+            node_item.push_back(k);
+            r_item.push_back(k), r_set.push_back(it.set);
+            r_omega.push_back(it.ct.center[0] + it.ct.semi_axes[0] * std::cos(t));
+            r_omega.push_back(it.ct.center[1] + it.ct.semi_axes[1] * std::sin(t));
+        }
+        it.N += add;
+    }
+    return !r_item.empty();
+}
+
+void ContourRounds::drop(int item, int status) {
+    Item& it = items[item];
+    if (it.dropped) return;
+    it.dropped = true, it.adding = it.doubling = false;
+    it.status = status, it.W = -1, it.k = 0;
+}
+
+void ContourRounds::take_logdets(const double* logdet) {
+    std::vector<int> ord;
+    std::vector<double> args;
+    for (Item& it : items) {
+        if (it.dropped || !it.adding) continue;
+        // argument principle on the item's nodes in contour order
+        ord.resize(it.nodes.size());
+        std::iota(ord.begin(), ord.end(), 0);
+        std::sort(ord.begin(), ord.end(), [&](int x, int y) { return it.node_m[x] < it.node_m[y]; });
+        args.resize(ord.size());
+        for (size_t q = 0; q < ord.size(); ++q) args[q] = logdet[2 * (size_t)it.nodes[ord[q]] + 1];
+        bool resolved = false;
+        const int w = contour_winding(args.data(), it.N, 0.5 * M_PI, &resolved, nullptr);
+        if (resolved) it.W = w;
+        // N doubles by the midpoints while the count is unresolved, up to max_points
+        it.adding = !resolved && 2 * it.N <= it.ct.max_points;
+    }
+}
+
+bool ContourRounds::plan_moments(const int* info, std::vector<int>& which, std::vector<int>& off, std::vector<int>& idx,
+                                 std::vector<double>& wz) const {
+    which.clear(), idx.clear();
+    off.assign(1, 0);
+    wz.assign(4 * (size_t)nodes(), 0.0);
+    for (int k = 0; k < (int)items.size(); ++k) {
+        const Item& it = items[k];
+        if (it.dropped || !it.doubling) continue;
+        const double ea = it.ct.semi_axes[0], eb = it.ct.semi_axes[1], rho = std::max(ea, eb);
+        for (size_t q = 0; q < it.nodes.size(); ++q) {
+            const int node = it.nodes[q];
+            // trapezoid weights of the item's final N: w = omega'(t) / (i N), z = (omega - c) / rho
+            const double t = 2.0 * M_PI * it.node_m[q] / it.ct.max_points;
+            const double dre = -ea * std::sin(t), dim_ = eb * std::cos(t);
+            double* o = &wz[4 * (size_t)node];
+            o[0] = dim_ / it.N, o[1] = -dre / it.N;
+            o[2] = ea * std::cos(t) / rho, o[3] = eb * std::sin(t) / rho;
+            if (info[node] == 0) idx.push_back(node);
+        }
+        which.push_back(k);
+        off.push_back((int)idx.size());
+    }
+    return !which.empty();
+}
+
+bool ContourRounds::take_rank(int item, int k, int* l0, int* nl) {
+    Item& it = items[item];
+    it.k = k;
+    // L doubles while A0 keeps full numerical rank
+    if (k < it.L || it.L >= 64) {
+        it.doubling = false;
+        return false;
+    }
+    const int L2 = std::min(2 * it.L, 64);
+    *l0 = it.L, *nl = L2 - it.L;
+    it.L = L2;
+    return true;
+}
+
 }  // namespace emme
 
 extern "C" {

@@ -408,6 +408,41 @@ int emme_contour_moments_batch(emme_ctx_t* ctx, int n, int nq, const double* M, 
                                const double* w, int L, const double* V, double* A0, double* A1,
                                double* logdet, int* info);
 
+/* The same with the matrices dealt into ngroups groups (an addition within version 4: find it by symbol lookup;
+ * DESIGN.md §13.9): group[j] in [0, ngroups) names the group of matrix j (host, nq ints; groups need not be
+ * contiguous), and A0 / A1 hold ngroups blocks of n*L complex, block g = the sums over the matrices of group g in
+ * ascending j, matrices with info != 0 left out; an empty group gives zeros.  One factorisation, one solve and one
+ * moments launch for all groups.  logdet, info per matrix as above.  ngroups <= 65535. */
+int emme_contour_moments_groups(emme_ctx_t* ctx, int n, int nq, const double* M, const int* group, int ngroups,
+                                const double* z, const double* w, int L, const double* V, double* A0,
+                                double* A1, double* logdet, int* info);
+
+/* Region search over parameter sets (an addition within version 4: find it by symbol lookup): item k
+ * is emme_find_roots_in_contour on the bound parameter set set[k] (emme_ctx_bind_param_sets) and the contour
+ * contours[k], and the items advance in lock step -- per round ONE fill over sets, one factorisation, one log-det and
+ * one solve launch for the new nodes of all items, then one moments launch per L pass and one emme_solve_roots_sets
+ * for the candidates of all items.  Per item the node sequence (points, doubled by the midpoints up to the item's own
+ * max_points), the winding rule, the L doubling from the item's own probes with its rank_tol, the candidate radius 1.5,
+ * the drop rules and the sort by Im omega descending are those of the single call.  exact = 0: the polish is the
+ * context's iteration_method (emme_solve_roots), exact = 1: the Newton search on the exact derivative
+ * (emme_solve_roots_newton); tol and step_limit are the call's, for every item.
+ * Outputs are per item: roots 2*max_roots doubles, iters / info max_roots ints (item k at offset k*max_roots roots),
+ * n_roots, winding, points_used, status one int each.  status[k] = EMME_OK, or the error that took item k out of the
+ * call: a node whose fill fails gives EMME_ENUMERIC, winding -1 and n_roots 0 for ITS item, the other items go on, and
+ * emme_last_error names the first such item and its node.
+ * The call returns EMME_EINVAL (the message names the item) without a binding, for a set[k] outside [0, nsets),
+ * nitems outside 1 .. 65535 or a contour that fails emme_find_roots_in_contour's argument rules -- all checked BEFORE
+ * the device is looked for; EMME_ECONFIG for dim > 2048.
+ * Afterwards emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) refer to the polish, as after
+ * emme_solve_roots_sets; its chains are the candidates of the items in item order and, inside an item, in the order
+ * emme_contour_eigs returned them (candidates outside normalised radius 1.5 have no chain; neither have items that
+ * left the call).  Memory: the factors and X of the nodes actually used, nodes * (dim^2 + 64 dim) * 16 bytes, in one
+ * block per round. */
+int emme_find_roots_in_contours_sets(emme_ctx_t* ctx, int nitems, const int* set, const emme_contour_t* contours,
+                                     int exact, double tol, int step_limit, int max_roots, double* roots,
+                                     int* iters, int* info, int* n_roots, int* winding, int* points_used,
+                                     int* status);
+
 /* Host only: the Beyn step on given moments (row-major n x L complex).  B = U_k^H A1 W_k S_k^-1 from the thin SVD
  * A0 = U S W^H (one-sided Jacobi), k = #{s_i > rank_tol s_1}; mu = eigenvalues of B (Hessenberg + shifted QR).
  * mu: 2*max_eigs (min(k, max_eigs) written), *k = numerical rank used (k == L: the probes may be too few),
