@@ -1,22 +1,24 @@
-// contour.hip -- the device half of the contour eigensolver and its two C entry points:
-// emme_contour_moments_batch (moments of caller matrices) and emme_find_roots_in_contour (every root inside an
-// ellipse: Beyn's method, W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, seeded into the Newton search).
+// contour.hip -- the device half of the contour eigensolver and its C entry points: the moments
+// of caller matrices (emme_contour_moments_batch, emme_contour_moments_groups) and the region search (every root inside
+// an ellipse: Beyn's method, W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, seeded into the Newton search) on
+// one contour (emme_find_roots_in_contour) or on many (parameter set, contour) items at once
+// (emme_find_roots_in_contours_sets).
 //
 // The nodes' matrices are factored once by the nullSpace factorisation (lu_factor_batch: P M = L U in place, row
 // order in panel snapshots) and kept for the whole call.  Three small kernels read the factors:
-//   k_contour_solve    X = M^-1 V for a group of G right-hand sides per workgroup: permute, then forward (L) and
-//                      back (U) substitution in blocks of 16 rows -- the rows' coupling to every finished block in dot
-//                      form (a wave per row, rows are contiguous), then the block's 16 x 16 triangle with 16 lanes
-//                      per column (a row each, the solved unknown broadcast by a shuffle), coefficients in LDS;
+//   k_contour_solve    X = M^-1 V for a group of G right-hand sides per workgroup, the matrices of a launch from a
+//                      list, each with its own column range: permute, then forward (L) and back (U) substitution in
+//                      blocks of 16 rows -- the rows' coupling to every finished block in dot form (a wave per row,
+//                      rows are contiguous), then the block's 16 x 16 triangle with 16 lanes per column (a row each,
+//                      the solved unknown broadcast by a shuffle), coefficients in LDS;
 //   k_contour_logdet   log det M = sum log u_ii + i pi (parity of the row order), fixed-order reductions;
-//   k_contour_moments  A0 = sum_j w_j X_j, A1 = sum_j w_j z_j X_j: a thread per entry, the nodes summed in order
-//                      (no atomics: two calls on the same inputs are bit-identical).
+//   k_contour_moments_groups  A0 = sum_j w_j X_j, A1 = sum_j w_j z_j X_j per group of nodes: a thread per entry, a
+//                      group's nodes summed in order (no atomics: two calls on the same inputs are bit-identical).
 // The probes V come from a counter-based hash of (row, column) with a fixed seed (k_contour_probes), so that the
 // first L columns do not depend on L and doubling L solves only the new ones.
-// Over many (parameter set, contour) items at once: emme_find_roots_in_contours_sets walks the round
-// plan of host_contour.cpp (ContourRounds) with one fill over sets, one factorisation, one log-det and one restricted
-// solve (k_contour_solve<G, true>: a list of matrices, each with its own column range) per round, the moments per item
-// by k_contour_moments_groups; emme_contour_moments_groups is that kernel on caller matrices.
+// Both searches are search_contours, which walks the round plan of host_contour.cpp (ContourRounds) with one fill, one
+// factorisation, one log-det and one solve launch per node round and takes the moments per item; the search on one
+// contour is its one-item case without a parameter set.
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -45,47 +47,36 @@ __device__ __forceinline__ double wsum(double v) {
     return v;
 }
 
-struct SolveArgs {
-    int n, map_nb, nblk;   // order; rows per row-order snapshot and snapshots per matrix
-    const double2* A;      // [nmat][n][n]  P M = L U in place
-    const int* maps;       // [nmat][nblk][n]
-    const int* lu_info;    // [nmat]
-    const double2* V;      // [n][ldv] probes
-    int ldv, l0, nl;       // columns l0 .. l0 + nl - 1 of V and X
-    double2* X;            // [nmat][n][ldx]
-    int ldx;
-    const struct SolveItem* list;  // the restricted solve: one entry per workgroup row of the grid (below)
-};
-
-// The restricted solve: matrix q of the launch is any factored matrix of the call, with its own
-// column range -- when one item of a search over (set, contour) items doubles L, only its nodes get the new columns.
-// The matrices of a call live in one buffer per node round, so an entry carries the matrix's own pointers.
+// Matrix q of a solve launch is any factored matrix of the call, with its own column range: when one
+// item of a search doubles L, only its nodes get the new columns.  The matrices of a call live in one buffer per node
+// round, so an entry carries the matrix's own pointers.
 struct SolveItem {
-    const double2* A;    // [n][n] factors
+    const double2* A;    // [n][n]  P M = L U in place
     const int* maps;     // [nblk][n]
     const int* lu_info;  // its info
     double2* X;          // [n][ldx]
-    int map_nb, l0, nl;  // rows per row-order snapshot; columns l0 .. l0 + nl - 1
+    int map_nb, l0, nl;  // rows per row-order snapshot; columns l0 .. l0 + nl - 1 of V and X
 };
 
-// one workgroup per (matrix, group of G columns).  LISTED = false: matrix blockIdx.x of P.A, columns P.l0 .. of every
-// matrix; LISTED = true: the matrix and columns of P.list[blockIdx.x] (a sibling kernel read from the same text: the
-// arithmetic of a column is the same in both)
-template <int G, bool LISTED>
+struct SolveArgs {
+    int n;
+    const double2* V;       // [n][ldv] probes
+    int ldv, ldx, nl;       // nl: the widest column range of the list
+    const SolveItem* list;  // one entry per workgroup row of the grid
+};
+
+// one workgroup per (matrix, group of G columns): the matrix and columns of P.list[blockIdx.x]
+template <int G>
 __global__ __launch_bounds__(CT) void k_contour_solve(SolveArgs P) {
     extern __shared__ double2 sm[];
-    const int n = P.n, b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int l0 = P.l0, nl = P.nl, map_nb = P.map_nb, nblk = P.nblk;
-    double2* out = P.X + (size_t)b * n * P.ldx;
-    const double2* a = P.A + (size_t)b * n * n;
-    const int* maps = P.maps + (size_t)b * P.nblk * n;
-    const int* lu_info = P.lu_info + b;
-    if constexpr (LISTED) {
-        const SolveItem it = P.list[b];
-        l0 = it.l0, nl = it.nl, map_nb = it.map_nb, nblk = (n + map_nb - 1) / map_nb;
-        out = it.X, a = it.A, maps = it.maps, lu_info = it.lu_info;
-        if ((int)blockIdx.y * G >= nl) return;  // (the grid is as deep as the widest range of the list)
-    }
+    const int n = P.n, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const SolveItem it = P.list[blockIdx.x];
+    const int l0 = it.l0, nl = it.nl, map_nb = it.map_nb;
+    double2* out = it.X;
+    const double2* a = it.A;
+    const int* maps = it.maps;
+    const int* lu_info = it.lu_info;
+    if ((int)blockIdx.y * G >= nl) return;  // (the grid is as deep as the widest range of the list)
     const int c0 = l0 + blockIdx.y * G;  // first column of the group
     const int gn = min(G, l0 + nl - c0);
     if (*lu_info != 0) {  // no factors: no solution
@@ -205,28 +196,12 @@ __global__ __launch_bounds__(CT) void k_contour_logdet(int n, const double2* A, 
     }
 }
 
-// A0[i][l] = sum_j w_j X_j[i][l], A1[i][l] = sum_j w_j z_j X_j[i][l], j in order; nodes with info != 0 left out
-__global__ void k_contour_moments(int n, int L, int nq, const double2* X, int ldx, const double2* wz, const int* info,
-                                  double2* A0, double2* A1) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= n * L) return;
-    const int i = e / L, l = e % L;
-    cd s0 = mk(0.0, 0.0), s1 = mk(0.0, 0.0);
-    for (int j = 0; j < nq; ++j) {
-        if (info[j] != 0) continue;
-        const double2 xv = X[((size_t)j * n + i) * ldx + l];
-        const double2 w = wz[2 * j], z = wz[2 * j + 1];
-        const cd t = mk(w.x, w.y) * mk(xv.x, xv.y);
-        s0 = s0 + t, s1 = s1 + t * mk(z.x, z.y);
-    }
-    A0[e] = make_double2(s0.x, s0.y), A1[e] = make_double2(s1.x, s1.y);
-}
-
-// The same sums per group: group g (blockIdx.y) sums the nodes idx[off[g]] .. idx[off[g + 1] - 1] in
-// that order, with its own column count Ls[g] (null: L for every group), into A0 / A1 + g * ostride.  A thread per
-// (group, entry), consecutive threads on consecutive l of a row of X; no atomics, so two calls on the same inputs are
-// bit-identical and a group's sum runs in the order k_contour_moments uses on the group alone.  Xn[node]: the node's X
-// ([n][ldx]); wz[2 node], wz[2 node + 1]: its w and z; info (nullable): nodes with info != 0 are left out.
+// A0[i][l] = sum_j w_j X_j[i][l], A1[i][l] = sum_j w_j z_j X_j[i][l] per group: group g (blockIdx.y)
+// sums the nodes idx[off[g]] .. idx[off[g + 1] - 1] in that order, with its own column count Ls[g] (null: L for every
+// group), into A0 / A1 + g * ostride.  A thread per (group, entry), consecutive threads on consecutive l of a row of X;
+// no atomics, so two calls on the same inputs are bit-identical and a group's sum does not depend on the other groups.
+// Xn[node]: the node's X ([n][ldx]); wz[2 node], wz[2 node + 1]: its w and z; info (nullable): nodes with info != 0 are
+// left out.
 __global__ void k_contour_moments_groups(int n, int L, const int* Ls, const int* off, const int* idx,
                                          const double2* const* Xn, int ldx, const double2* wz, const int* info, double2* A0,
                                          double2* A1, size_t ostride) {
@@ -272,166 +247,116 @@ int solve_group(int n, int nl, int nmat, int n_cu) {
     return G;
 }
 
-template <int G, bool LISTED>
+template <int G>
 hipError_t launch_solve_g(const SolveArgs& P, int nmat, hipStream_t st) {
     const size_t lds = solve_lds(P.n, G);
     if (lds > 150 * 1024) return hipErrorNotSupported;
     if (lds > 48 * 1024) {
-        const hipError_t ea = hipFuncSetAttribute((const void*)k_contour_solve<G, LISTED>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t ea = hipFuncSetAttribute((const void*)k_contour_solve<G>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return ea;
     }
-    hipLaunchKernelGGL((k_contour_solve<G, LISTED>), dim3(nmat, (P.nl + G - 1) / G), dim3(CT), lds, st, P);
+    hipLaunchKernelGGL((k_contour_solve<G>), dim3(nmat, (P.nl + G - 1) / G), dim3(CT), lds, st, P);
     return hipGetLastError();
 }
 
-// P.list null: columns P.l0 .. P.l0 + P.nl - 1 of the nmat matrices of P.A; else the nmat entries of P.list, P.nl the
-// widest of their column ranges
-template <bool LISTED>
-hipError_t launch_contour_solve_as(const SolveArgs& P, int nmat, int n_cu, hipStream_t st) {
+// the nmat entries of P.list, P.nl the widest of their column ranges
+hipError_t launch_contour_solve(const SolveArgs& P, int nmat, int n_cu, hipStream_t st) {
     switch (solve_group(P.n, P.nl, nmat, n_cu)) {
-        case 16: return launch_solve_g<16, LISTED>(P, nmat, st);
-        case 8: return launch_solve_g<8, LISTED>(P, nmat, st);
-        case 4: return launch_solve_g<4, LISTED>(P, nmat, st);
-        case 2: return launch_solve_g<2, LISTED>(P, nmat, st);
-        default: return launch_solve_g<1, LISTED>(P, nmat, st);
+        case 16: return launch_solve_g<16>(P, nmat, st);
+        case 8: return launch_solve_g<8>(P, nmat, st);
+        case 4: return launch_solve_g<4>(P, nmat, st);
+        case 2: return launch_solve_g<2>(P, nmat, st);
+        default: return launch_solve_g<1>(P, nmat, st);
     }
 }
-hipError_t launch_contour_solve(const SolveArgs& P, int nmat, int n_cu, hipStream_t st) {
-    return P.list ? launch_contour_solve_as<true>(P, nmat, n_cu, st) : launch_contour_solve_as<false>(P, nmat, n_cu, st);
+
+// the right-hand sides of a call: the internal probes, or a caller's V
+struct Probes {
+    DeviceBuffer<double> V;
+    int ld = LCAP;
+};
+
+int make_probes(emme_ctx* c, int n, Probes& pr) {
+    HIP_TRY(pr.V.grow(sizeof(double) * 2 * (size_t)n * LCAP));
+    pr.ld = LCAP;
+    hipLaunchKernelGGL(k_contour_probes, dim3((n * LCAP + 255) / 256), dim3(256), 0, c->stream, n, (double2*)pr.V.get());
+    HIP_TRY(hipGetLastError());
+    return EMME_OK;
 }
 
-// matrices factored in one batch, with their own copy of the row order (the factorisation's scratch is reused)
-struct NodeSet {
-    int first = 0, count = 0, map_nb = 1;
-    DeviceBuffer<double> A;  // factors
-    DeviceBuffer<int> maps;
-};
-
+// `count` matrices factored in one batch and what the call keeps of each: the factors, their own copy of the row order
+// (the factorisation's scratch is reused), X, log det and info.  One device allocation holds all five: a call frees as
+// many buffers as it has node rounds, and a region search on a context of its own (create, search, destroy) is as
+// fast as it was with one buffer set per call (five allocations per round cost it 5 % at n = 64)
 struct ContourState {
-    emme_ctx* c;
-    int n;
-    int ldx;
-    DeviceBuffer<double> X, logdet, V, wz, A0, A1;
-    DeviceBuffer<int> info;
-    std::vector<NodeSet> sets;
-    int ldv = LCAP;
-    const double2* Vp() const { return (const double2*)V.get(); }
+    emme_ctx* c = nullptr;
+    int n = 0, count = 0, ldx = 0, map_nb = 1;
+    DeviceBuffer<char> mem;  // A | X | logdet | maps | info
+    double *A = nullptr, *X = nullptr, *logdet = nullptr;
+    int *maps = nullptr, *info = nullptr;
+    // matrix q with the columns [l0, l0 + nl)
+    SolveItem item(int q, int l0, int nl) const {
+        const size_t per_map = (size_t)n * ((n + map_nb - 1) / map_nb);
+        SolveItem e{};
+        e.A = (const double2*)A + (size_t)n * n * q, e.maps = maps + per_map * q, e.lu_info = info + q;
+        e.X = (double2*)X + (size_t)q * n * ldx, e.map_nb = map_nb, e.l0 = l0, e.nl = nl;
+        return e;
+    }
 };
 
-// factor set.A in place (count matrices from node index set.first), keep the row order and info, log det
-int factor_set(ContourState& S, NodeSet& set, const char* who) {
+int alloc_nodes(ContourState& S, emme_ctx* c, int n, int count, int ldx) {
+    S.c = c, S.n = n, S.count = count, S.ldx = ldx;
+    const size_t nA = 2 * (size_t)n * n * count, nX = 2 * (size_t)count * n * ldx, nld = 2 * (size_t)count;
+    // (the row order of the unblocked LU has one snapshot; the most any branch writes is one per trace_solve_nb() rows)
+    const size_t nmaps = (size_t)n * ((n + trace_solve_nb() - 1) / trace_solve_nb()) * count;
+    HIP_TRY(S.mem.grow(sizeof(double) * (nA + nX + nld) + sizeof(int) * (nmaps + count)));
+    S.A = (double*)S.mem.get(), S.X = S.A + nA, S.logdet = S.X + nX;
+    S.maps = (int*)(S.logdet + nld), S.info = S.maps + nmaps;
+    return EMME_OK;
+}
+
+// factor S.A in place, keep the row order and info, log det
+int factor_nodes(ContourState& S, const char* who) {
     emme_ctx* c = S.c;
     const int n = S.n;
     LuScratch scr;
     int map_nb = 1;
-    const size_t per_map_max = (size_t)n * ((n + trace_solve_nb() - 1) / trace_solve_nb());  // (the unblocked LU: one)
-    HIP_TRY(set.maps.grow(sizeof(int) * per_map_max * set.count));
-    const int rc = lu_factor_batch(c, n, set.count, set.A, scr, who,
+    const int rc = lu_factor_batch(c, n, S.count, S.A, scr, who,
                                    [&](int b0, int nb, const int* maps, int mnb, const int* lu_info) -> hipError_t {
                                        map_nb = mnb;
                                        const size_t per = (size_t)n * ((n + mnb - 1) / mnb);
-                                       hipError_t e = hipMemcpyAsync(set.maps + per * b0, maps, sizeof(int) * per * nb,
+                                       hipError_t e = hipMemcpyAsync(S.maps + per * b0, maps, sizeof(int) * per * nb,
                                                                      hipMemcpyDeviceToDevice, c->stream);
                                        if (e == hipSuccess)
-                                           e = hipMemcpyAsync(S.info + set.first + b0, lu_info, sizeof(int) * nb,
-                                                              hipMemcpyDeviceToDevice, c->stream);
+                                           e = hipMemcpyAsync(S.info + b0, lu_info, sizeof(int) * nb, hipMemcpyDeviceToDevice,
+                                                              c->stream);
                                        return e;
                                    });
     if (rc) return rc;
-    set.map_nb = map_nb;
+    S.map_nb = map_nb;
     ScopedSpan sp(c, K_OTHER);
-    hipLaunchKernelGGL(k_contour_logdet, dim3(set.count), dim3(CT), 2 * sizeof(int) * n, c->stream, n,
-                       (const double2*)set.A.get(), set.maps.get(), map_nb, (n + map_nb - 1) / map_nb,
-                       S.info + set.first, (double2*)S.logdet.get() + set.first);
+    hipLaunchKernelGGL(k_contour_logdet, dim3(S.count), dim3(CT), 2 * sizeof(int) * n, c->stream, n,
+                       (const double2*)S.A, S.maps, map_nb, (n + map_nb - 1) / map_nb, S.info,
+                       (double2*)S.logdet);
     HIP_TRY(hipGetLastError());
     return EMME_OK;
 }
 
-// X columns [l0, l0 + nl) of every node of the set
-int solve_set(ContourState& S, const NodeSet& set, int l0, int nl) {
-    SolveArgs P;
-    P.n = S.n, P.map_nb = set.map_nb, P.nblk = (S.n + set.map_nb - 1) / set.map_nb;
-    P.A = (const double2*)set.A.get();
-    P.maps = set.maps;
-    P.lu_info = S.info + set.first;
-    P.V = S.Vp(), P.ldv = S.ldv, P.l0 = l0, P.nl = nl;
-    P.X = (double2*)S.X.get() + (size_t)set.first * S.n * S.ldx;
-    P.ldx = S.ldx;
-    P.list = nullptr;
-    ScopedSpan sp(S.c, K_OTHER);
-    HIP_TRY(launch_contour_solve(P, set.count, S.c->n_cu, S.c->stream));
+// one solve launch for the entries of `list` (X of every entry [n][ldx])
+int solve_listed(emme_ctx* c, int n, const Probes& pr, int ldx, const std::vector<SolveItem>& list,
+                 DeviceBuffer<SolveItem>& d_list) {
+    if (list.empty()) return EMME_OK;
+    HIP_TRY(d_list.grow(sizeof(SolveItem) * list.size()));
+    HIP_TRY(hipMemcpyAsync(d_list, list.data(), sizeof(SolveItem) * list.size(), hipMemcpyHostToDevice, c->stream));
+    SolveArgs P{};
+    P.n = n, P.V = (const double2*)pr.V.get(), P.ldv = pr.ld, P.ldx = ldx, P.list = d_list;
+    for (const SolveItem& it : list) P.nl = std::max(P.nl, it.nl);
+    ScopedSpan sp(c, K_OTHER);
+    HIP_TRY(launch_contour_solve(P, (int)list.size(), c->n_cu, c->stream));
     return EMME_OK;
 }
 
-// moments over nodes [0, nq) with weights wz (host, (w_j, z_j) per node) into host A0, A1 (n x L)
-int moments(ContourState& S, int nq, const std::vector<double>& wz, int L, double* A0, double* A1) {
-    emme_ctx* c = S.c;
-    HIP_TRY(hipMemcpyAsync(S.wz, wz.data(), sizeof(double) * 4 * nq, hipMemcpyHostToDevice, c->stream));
-    {
-        ScopedSpan sp(c, K_OTHER);
-        const int ne = S.n * L;
-        hipLaunchKernelGGL(k_contour_moments, dim3((ne + 255) / 256), dim3(256), 0, c->stream, S.n, L, nq,
-                           (const double2*)S.X.get(), S.ldx, (const double2*)S.wz.get(), S.info.get(),
-                           (double2*)S.A0.get(), (double2*)S.A1.get());
-        HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(hipMemcpyAsync(A0, S.A0, sizeof(double) * 2 * S.n * L, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(A1, S.A1, sizeof(double) * 2 * S.n * L, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EMME_OK;
-}
-
-// X, log det and info of `nodes` matrices
-int alloc_nodes(ContourState& S, int nodes, int ldx) {
-    S.ldx = ldx;
-    HIP_TRY(S.X.grow(sizeof(double) * 2 * (size_t)nodes * S.n * ldx));
-    HIP_TRY(S.logdet.grow(sizeof(double) * 2 * nodes));
-    HIP_TRY(S.info.grow(sizeof(int) * nodes));
-    return EMME_OK;
-}
-
-int alloc_state(ContourState& S, int nodes, int ldx) {
-    EMME_TRY(alloc_nodes(S, nodes, ldx));
-    HIP_TRY(S.wz.grow(sizeof(double) * 4 * nodes));
-    HIP_TRY(S.A0.grow(sizeof(double) * 2 * (size_t)S.n * LCAP));
-    HIP_TRY(S.A1.grow(sizeof(double) * 2 * (size_t)S.n * LCAP));
-    return EMME_OK;
-}
-
-int make_probes(ContourState& S) {
-    HIP_TRY(S.V.grow(sizeof(double) * 2 * (size_t)S.n * LCAP));
-    S.ldv = LCAP;
-    hipLaunchKernelGGL(k_contour_probes, dim3((S.n * LCAP + 255) / 256), dim3(256), 0, S.c->stream, S.n, (double2*)S.V.get());
-    HIP_TRY(hipGetLastError());
-    return EMME_OK;
-}
-
-// what the two building blocks share: caller matrices M (nq of order n, host or device) factored, log det taken and
-// X = M^-1 V solved for L columns (V null: the internal probes), all in S
-int solve_caller_matrices(emme_ctx* c, ContourState& S, const char* who, int n, int nq, const double* M, int L, const double* V) {
-    HIP_TRY(hipSetDevice(c->device));
-    EMME_TRY(ensure_batch(c, nq));
-    S.c = c, S.n = n;
-    EMME_TRY(alloc_state(S, nq, L));
-    if (V) {
-        HIP_TRY(S.V.grow(sizeof(double) * 2 * (size_t)n * L));
-        S.ldv = L;
-        HIP_TRY(hipMemcpyAsync(S.V, V, sizeof(double) * 2 * (size_t)n * L,
-                               is_device_ptr(V) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    } else {
-        EMME_TRY(make_probes(S));
-    }
-    S.sets.emplace_back();
-    NodeSet& set = S.sets.back();
-    set.first = 0, set.count = nq;
-    const size_t mbytes = sizeof(double) * 2 * (size_t)n * n * nq;
-    HIP_TRY(set.A.grow(mbytes));
-    HIP_TRY(hipMemcpyAsync(set.A, M, mbytes, is_device_ptr(M) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
-    EMME_TRY(factor_set(S, set, who));
-    return solve_set(S, set, 0, L);
-}
-
-// device images of the lists of a grouped-moments launch, and its sums
+// device images of the lists of a moments launch, and its sums
 struct GroupBuffers {
     DeviceBuffer<int> ints;  // off | idx | Ls
     DeviceBuffer<const double2*> Xn;
@@ -473,83 +398,42 @@ int moments_groups(emme_ctx* c, int n, int L, const std::vector<int>* Ls, const 
     return EMME_OK;
 }
 
-// one restricted solve (k_contour_solve<G, true>) for the entries of `list`
-int solve_listed(emme_ctx* c, int n, const double2* V, int ldv, const std::vector<SolveItem>& list,
-                 DeviceBuffer<SolveItem>& d_list) {
-    if (list.empty()) return EMME_OK;
-    HIP_TRY(d_list.grow(sizeof(SolveItem) * list.size()));
-    HIP_TRY(hipMemcpyAsync(d_list, list.data(), sizeof(SolveItem) * list.size(), hipMemcpyHostToDevice, c->stream));
-    SolveArgs P{};
-    P.n = n, P.V = V, P.ldv = ldv, P.ldx = LCAP, P.list = d_list;
-    for (const SolveItem& it : list) P.nl = std::max(P.nl, it.nl);
-    ScopedSpan sp(c, K_OTHER);
-    HIP_TRY(launch_contour_solve(P, (int)list.size(), c->n_cu, c->stream));
-    return EMME_OK;
-}
-
-}  // namespace
-}  // namespace emme
-
-using namespace emme;
-
-extern "C" {
-
-int emme_contour_moments_batch(emme_ctx_t* c, int n, int nq, const double* M, const double* z, const double* w, int L,
-                               const double* V, double* A0, double* A1, double* logdet, int* info) {
-    if (!c || !M || !z || !w || !A0 || !A1 || !logdet || !info || n < 1 || nq < 1 || L < 1 || L > LCAP) {
-        set_error("emme_contour_moments_batch: need M, z, w, A0, A1, logdet, info, n >= 1, nq >= 1 and 1 <= L <= 64");
-        return EMME_EINVAL;
-    }
-    if (n > 2048) {
-        set_error("emme_contour_moments_batch: order above 2048 is not supported (the factorisation's range)");
-        return EMME_ECONFIG;
+// What emme_contour_moments_groups and emme_contour_moments_batch (group null: every matrix in group 0) are: caller
+// matrices M (nq of order n, host or device) factored, log det taken, X = M^-1 V solved for L columns (V null: the
+// internal probes) and summed per group, ascending j inside a group; a matrix with info != 0 is left out on the device
+int caller_moments(emme_ctx* c, const char* who, int n, int nq, const double* M, const int* group, int ngroups,
+                   const double* z, const double* w, int L, const double* V, double* A0, double* A1, double* logdet,
+                   int* info) {
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nq));
+    Probes pr;
+    if (V) {
+        HIP_TRY(pr.V.grow(sizeof(double) * 2 * (size_t)n * L));
+        pr.ld = L;
+        HIP_TRY(hipMemcpyAsync(pr.V, V, sizeof(double) * 2 * (size_t)n * L,
+                               is_device_ptr(V) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    } else {
+        EMME_TRY(make_probes(c, n, pr));
     }
     ContourState S;
-    int rc = solve_caller_matrices(c, S, "emme_contour_moments_batch", n, nq, M, L, V);
-    if (rc) return rc;
-    std::vector<double> wz(4 * (size_t)nq);
-    for (int j = 0; j < nq; ++j) wz[4 * j] = w[2 * j], wz[4 * j + 1] = w[2 * j + 1], wz[4 * j + 2] = z[2 * j], wz[4 * j + 3] = z[2 * j + 1];
-    rc = moments(S, nq, wz, L, A0, A1);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(logdet, S.logdet, sizeof(double) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, S.info, sizeof(int) * nq, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EMME_OK;
-}
-
-int emme_contour_moments_groups(emme_ctx_t* c, int n, int nq, const double* M, const int* group, int ngroups,
-                                const double* z, const double* w, int L, const double* V, double* A0, double* A1,
-                                double* logdet, int* info) {
-    if (!c || !M || !group || !z || !w || !A0 || !A1 || !logdet || !info || n < 1 || nq < 1 || L < 1 || L > LCAP ||
-        ngroups < 1 || ngroups > 65535) {
-        set_error("emme_contour_moments_groups: need M, group, z, w, A0, A1, logdet, info, n >= 1, nq >= 1, 1 <= L <= 64 and "
-                  "1 <= ngroups <= 65535");
-        return EMME_EINVAL;
-    }
-    for (int j = 0; j < nq; ++j)
-        if (group[j] < 0 || group[j] >= ngroups) {
-            set_error("emme_contour_moments_groups: group[" + std::to_string(j) + "] = " + std::to_string(group[j]) +
-                      " is outside [0, " + std::to_string(ngroups) + ")");
-            return EMME_EINVAL;
-        }
-    if (n > 2048) {
-        set_error("emme_contour_moments_groups: order above 2048 is not supported (the factorisation's range)");
-        return EMME_ECONFIG;
-    }
-    ContourState S;
-    EMME_TRY(solve_caller_matrices(c, S, "emme_contour_moments_groups", n, nq, M, L, V));
-    // the groups' node lists, ascending j inside a group
-    std::vector<int> off(ngroups + 1, 0), idx(nq);
-    for (int j = 0; j < nq; ++j) ++off[group[j] + 1];
-    for (int g = 0; g < ngroups; ++g) off[g + 1] += off[g];
-    std::vector<int> at(off.begin(), off.end() - 1);
-    for (int j = 0; j < nq; ++j) idx[at[group[j]]++] = j;
+    EMME_TRY(alloc_nodes(S, c, n, nq, L));
+    HIP_TRY(hipMemcpyAsync(S.A, M, sizeof(double) * 2 * (size_t)n * n * nq,
+                           is_device_ptr(M) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    EMME_TRY(factor_nodes(S, who));
+    std::vector<SolveItem> list(nq);
     std::vector<const double2*> Xn(nq);
     std::vector<double> wz(4 * (size_t)nq);
+    std::vector<int> off(ngroups + 1, 0), idx(nq);
     for (int j = 0; j < nq; ++j) {
-        Xn[j] = (const double2*)S.X.get() + (size_t)j * n * L;
+        list[j] = S.item(j, 0, L), Xn[j] = list[j].X;
         wz[4 * j] = w[2 * j], wz[4 * j + 1] = w[2 * j + 1], wz[4 * j + 2] = z[2 * j], wz[4 * j + 3] = z[2 * j + 1];
+        ++off[(group ? group[j] : 0) + 1];
     }
+    DeviceBuffer<SolveItem> d_list;
+    EMME_TRY(solve_listed(c, n, pr, L, list, d_list));
+    for (int g = 0; g < ngroups; ++g) off[g + 1] += off[g];
+    std::vector<int> at(off.begin(), off.end() - 1);
+    for (int j = 0; j < nq; ++j) idx[at[group ? group[j] : 0]++] = j;
     GroupBuffers G;
     EMME_TRY(moments_groups(c, n, L, nullptr, off, idx, Xn, L, wz, S.info, G, (size_t)n * L, A0, A1));
     HIP_TRY(hipMemcpyAsync(logdet, S.logdet, sizeof(double) * 2 * nq, hipMemcpyDeviceToHost, c->stream));
@@ -558,25 +442,20 @@ int emme_contour_moments_groups(emme_ctx_t* c, int n, int nq, const double* M, c
     return EMME_OK;
 }
 
-int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, const emme_contour_t* contours, int exact,
-                                     double tol, int step_limit, int max_roots, double* roots, int* iters, int* info,
-                                     int* n_roots, int* winding, int* points_used, int* status) {
-    const std::string who = "emme_find_roots_in_contours_sets";
-    if (nitems < 1 || nitems > 65535) {
-        set_error(who + ": nitems must lie in 1 .. 65535");
-        return EMME_EINVAL;
-    }
-    if (!c || !set || !contours || !roots || !iters || !info || !n_roots || !winding || !points_used || !status ||
-        max_roots < 1 || step_limit < 0 || !(tol > 0.0)) {
-        set_error(who + ": need a context, sets, contours, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
-        return EMME_EINVAL;
-    }
-    for (int k = 0; k < nitems; ++k)
-        if (const char* bad = contour_arg_error(&contours[k])) {
-            set_error(who + ": item " + std::to_string(k) + ": " + bad);
-            return EMME_EINVAL;
-        }
-    EMME_TRY(check_set_indices(c, set, nitems, who.c_str()));
+// where a region search puts what it found: item k's roots at roots[k max_roots ..], one of everything else per item
+struct SearchOutputs {
+    double* roots;
+    int *iters, *info, *n_roots, *winding, *points_used, *status;
+};
+
+// The region search on nitems (set, contour) items in lock step: the round plan of host_contour.cpp
+// (ContourRounds) with one fill, one factorisation, one log-det and one solve launch per node round, moment passes
+// while L doubles, one polish.  set null is the single search of emme_find_roots_in_contour, one item
+// on the context's own parameters: its fills carry no set (so they may go through the node cache), its polish is
+// emme_solve_roots with the context's method (`exact` is not read), and an error of the item is the call's error,
+// named without an item number.
+int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* set, const emme_contour_t* contours,
+                    int exact, double tol, int step_limit, int max_roots, const SearchOutputs& out) {
     const int n = c->dim;
     if (n > 2048) {
         set_error(who + ": dim above 2048 is not supported (the factorisation's range)");
@@ -584,9 +463,8 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
     }
     HIP_TRY(hipSetDevice(c->device));
     ContourRounds plan(nitems, set, contours);
-    ContourState probes;  // (only V: every item reads the same probes)
-    probes.c = c, probes.n = n;
-    EMME_TRY(make_probes(probes));
+    Probes probes;  // (every item reads the same probes)
+    EMME_TRY(make_probes(c, n, probes));
     std::vector<ContourState> rounds;    // the nodes of a node round: factors, X, log det, info
     std::vector<SolveItem> node;         // every node's factors and X, columns unset
     std::vector<const double2*> Xn;
@@ -595,9 +473,10 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
     std::vector<SolveItem> list;
     DeviceBuffer<SolveItem> d_list;
     std::string first_error;
+    auto label = [&](int item) { return set ? who + ": item " + std::to_string(item) + ": " : who + ": "; };
     auto drop = [&](int item, int rc, const std::string& msg) {
         plan.drop(item, rc);
-        if (first_error.empty()) first_error = who + ": item " + std::to_string(item) + ": " + msg;
+        if (first_error.empty()) first_error = msg;
     };
     // ---- node rounds: one fill, one factorisation, one log-det and one solve launch for the new nodes of all items
     while (plan.plan_nodes()) {
@@ -605,19 +484,16 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
         EMME_TRY(ensure_batch(c, cnt));
         rounds.emplace_back();
         ContourState& S = rounds.back();
-        S.c = c, S.n = n;
-        EMME_TRY(alloc_nodes(S, cnt, LCAP));
-        S.sets.emplace_back();
-        NodeSet& ns = S.sets.back();
-        ns.first = 0, ns.count = cnt;
+        EMME_TRY(alloc_nodes(S, c, n, cnt, LCAP));
         const size_t msize = 2 * (size_t)n * n;
-        HIP_TRY(ns.A.grow(sizeof(double) * msize * cnt));
-        EMME_TRY(upload_set_indices(c, plan.r_set.data(), cnt));
         EMME_TRY(upload_omega(c, plan.r_omega.data(), cnt));
         EMME_TRY(reset_fill_counters(c, cnt));
-        FillRequest rq(cnt, c->d_omega, ns.A);
+        FillRequest rq(cnt, c->d_omega, S.A);
         rq.host_omega = plan.r_omega.data();
-        rq.d_set = c->d_set, rq.host_set = plan.r_set.data();
+        if (set) {
+            EMME_TRY(upload_set_indices(c, plan.r_set.data(), cnt));
+            rq.d_set = c->d_set, rq.host_set = plan.r_set.data();
+        }
         EMME_TRY(fill(c, rq));
         std::vector<unsigned long long> iv;
         std::vector<int> stv;
@@ -630,23 +506,17 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
             char buf[160];
             snprintf(buf, sizeof buf, "the fill of the node omega = %.17g%+.17gi failed (quadrature depth cap or non-finite integral)",
                      plan.r_omega[2 * q], plan.r_omega[2 * q + 1]);
-            drop(plan.r_item[q], EMME_ENUMERIC, buf);
-            HIP_TRY(hipMemsetAsync(ns.A + msize * q, 0, sizeof(double) * msize, c->stream));
+            drop(plan.r_item[q], EMME_ENUMERIC, label(plan.r_item[q]) + buf);
+            HIP_TRY(hipMemsetAsync(S.A + msize * q, 0, sizeof(double) * msize, c->stream));
         }
-        EMME_TRY(factor_set(S, ns, who.c_str()));
-        const size_t per_map = (size_t)n * ((n + ns.map_nb - 1) / ns.map_nb);
+        EMME_TRY(factor_nodes(S, who.c_str()));
         list.clear();
         for (int q = 0; q < cnt; ++q) {
-            SolveItem e{};
-            e.A = (const double2*)ns.A.get() + (size_t)n * n * q, e.maps = ns.maps + per_map * q, e.lu_info = S.info + q;
-            e.X = (double2*)S.X.get() + (size_t)q * n * LCAP, e.map_nb = ns.map_nb;
-            node.push_back(e), Xn.push_back(e.X);
             const ContourRounds::Item& it = plan.items[plan.r_item[q]];
-            if (it.dropped) continue;
-            e.l0 = 0, e.nl = it.L;
-            list.push_back(e);
+            node.push_back(S.item(q, 0, it.L)), Xn.push_back(node.back().X);
+            if (!it.dropped) list.push_back(node.back());
         }
-        EMME_TRY(solve_listed(c, n, probes.Vp(), probes.ldv, list, d_list));
+        EMME_TRY(solve_listed(c, n, probes, LCAP, list, d_list));
         ld.resize(2 * (size_t)plan.nodes()), h_info.resize(plan.nodes());
         // (in order on the context's stream, which may be a non-blocking one: not a null-stream copy)
         HIP_TRY(hipMemcpyAsync(&ld[2 * (size_t)first], S.logdet, sizeof(double) * 2 * cnt, hipMemcpyDeviceToHost, c->stream));
@@ -675,12 +545,15 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
             const int rc = emme_contour_eigs(n, Ls[g], &A0[2 * ostride * g], &A1[2 * ostride * g], ct.rank_tol, LCAP, mu.data(),
                                              &k, sig.data());
             if (rc) {
-                drop(item, rc, emme_last_error());
+                drop(item, rc, set ? label(item) + emme_last_error() : emme_last_error());
                 continue;
             }
-            if (std::getenv("EMME_DEBUG"))
-                fprintf(stderr, "[emme] contours: item %d N %d L %d k %d W %d\n", item, plan.items[item].N, Ls[g], k,
+            if (std::getenv("EMME_DEBUG")) {
+                fprintf(stderr, "[emme] contour item %d N %d L %d k %d W %d sigma:", item, plan.items[item].N, Ls[g], k,
                         plan.items[item].W);
+                for (int l = 0; l < Ls[g]; ++l) fprintf(stderr, " %.3e", sig[l]);
+                fprintf(stderr, "\n");
+            }
             if (!plan.take_rank(item, k, &l0, &nl)) {
                 // the candidates (normalised radius below 1.5: the others are no eigenvalues inside)
                 contour_candidates(ct, k, mu.data(), guesses[item]);
@@ -692,15 +565,15 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
                 list.push_back(e);
             }
         }
-        EMME_TRY(solve_listed(c, n, probes.Vp(), probes.ldv, list, d_list));
+        EMME_TRY(solve_listed(c, n, probes, LCAP, list, d_list));
     }
-    // ---- one search over sets polishes the candidates of all items: items in order, an item's in the order of mu
+    // ---- one search polishes the candidates of all items: items in order, an item's in the order of mu
     std::vector<double> g_all;
     std::vector<int> g_set, g_first(nitems + 1, 0);
     for (int k = 0; k < nitems; ++k) {
         if (!plan.items[k].dropped) {
             g_all.insert(g_all.end(), guesses[k].begin(), guesses[k].end());
-            g_set.insert(g_set.end(), guesses[k].size() / 2, set[k]);
+            g_set.insert(g_set.end(), guesses[k].size() / 2, plan.items[k].set);
         }
         g_first[k + 1] = (int)g_set.size();
     }
@@ -708,9 +581,10 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
     std::vector<double> r(2 * (size_t)ng), path(2 * (size_t)ng * (step_limit + 1));
     std::vector<int> its(ng), inf(ng);
     if (ng > 0)
-        EMME_TRY(emme_solve_roots_sets(c, g_set.data(), g_all.data(), ng, exact, tol, step_limit, r.data(), its.data(),
-                                       inf.data(), path.data()));
-    else
+        EMME_TRY(set ? emme_solve_roots_sets(c, g_set.data(), g_all.data(), ng, exact, tol, step_limit, r.data(), its.data(),
+                                             inf.data(), path.data())
+                     : emme_solve_roots(c, g_all.data(), ng, tol, step_limit, r.data(), its.data(), inf.data(), path.data()));
+    else if (set)
         c->last_n = 0;  // (no polish: emme_ctx_get_matrix has nothing to refer to)
     for (int k = 0; k < nitems; ++k) {
         const ContourRounds::Item& it = plan.items[k];
@@ -721,12 +595,78 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, 
                                        &path[2 * (size_t)o * (step_limit + 1)]);
         for (int q = 0; q < std::min((int)found.size(), max_roots); ++q) {
             const size_t at = (size_t)k * max_roots + q;
-            roots[2 * at] = found[q].re, roots[2 * at + 1] = found[q].im, iters[at] = found[q].it, info[at] = found[q].inf;
+            out.roots[2 * at] = found[q].re, out.roots[2 * at + 1] = found[q].im, out.iters[at] = found[q].it,
+                           out.info[at] = found[q].inf;
         }
-        n_roots[k] = (int)found.size(), winding[k] = it.W, points_used[k] = it.N, status[k] = it.status;
+        out.n_roots[k] = (int)found.size(), out.winding[k] = it.W, out.points_used[k] = it.N, out.status[k] = it.status;
     }
     if (!first_error.empty()) set_error(first_error);
     return EMME_OK;
+}
+
+}  // namespace
+}  // namespace emme
+
+using namespace emme;
+
+extern "C" {
+
+int emme_contour_moments_batch(emme_ctx_t* c, int n, int nq, const double* M, const double* z, const double* w, int L,
+                               const double* V, double* A0, double* A1, double* logdet, int* info) {
+    if (!c || !M || !z || !w || !A0 || !A1 || !logdet || !info || n < 1 || nq < 1 || L < 1 || L > LCAP) {
+        set_error("emme_contour_moments_batch: need M, z, w, A0, A1, logdet, info, n >= 1, nq >= 1 and 1 <= L <= 64");
+        return EMME_EINVAL;
+    }
+    if (n > 2048) {
+        set_error("emme_contour_moments_batch: order above 2048 is not supported (the factorisation's range)");
+        return EMME_ECONFIG;
+    }
+    return caller_moments(c, "emme_contour_moments_batch", n, nq, M, nullptr, 1, z, w, L, V, A0, A1, logdet, info);
+}
+
+int emme_contour_moments_groups(emme_ctx_t* c, int n, int nq, const double* M, const int* group, int ngroups,
+                                const double* z, const double* w, int L, const double* V, double* A0, double* A1,
+                                double* logdet, int* info) {
+    if (!c || !M || !group || !z || !w || !A0 || !A1 || !logdet || !info || n < 1 || nq < 1 || L < 1 || L > LCAP ||
+        ngroups < 1 || ngroups > 65535) {
+        set_error("emme_contour_moments_groups: need M, group, z, w, A0, A1, logdet, info, n >= 1, nq >= 1, 1 <= L <= 64 and "
+                  "1 <= ngroups <= 65535");
+        return EMME_EINVAL;
+    }
+    for (int j = 0; j < nq; ++j)
+        if (group[j] < 0 || group[j] >= ngroups) {
+            set_error("emme_contour_moments_groups: group[" + std::to_string(j) + "] = " + std::to_string(group[j]) +
+                      " is outside [0, " + std::to_string(ngroups) + ")");
+            return EMME_EINVAL;
+        }
+    if (n > 2048) {
+        set_error("emme_contour_moments_groups: order above 2048 is not supported (the factorisation's range)");
+        return EMME_ECONFIG;
+    }
+    return caller_moments(c, "emme_contour_moments_groups", n, nq, M, group, ngroups, z, w, L, V, A0, A1, logdet, info);
+}
+
+int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, const emme_contour_t* contours, int exact,
+                                     double tol, int step_limit, int max_roots, double* roots, int* iters, int* info,
+                                     int* n_roots, int* winding, int* points_used, int* status) {
+    const std::string who = "emme_find_roots_in_contours_sets";
+    if (nitems < 1 || nitems > 65535) {
+        set_error(who + ": nitems must lie in 1 .. 65535");
+        return EMME_EINVAL;
+    }
+    if (!c || !set || !contours || !roots || !iters || !info || !n_roots || !winding || !points_used || !status ||
+        max_roots < 1 || step_limit < 0 || !(tol > 0.0)) {
+        set_error(who + ": need a context, sets, contours, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
+        return EMME_EINVAL;
+    }
+    for (int k = 0; k < nitems; ++k)
+        if (const char* bad = contour_arg_error(&contours[k])) {
+            set_error(who + ": item " + std::to_string(k) + ": " + bad);
+            return EMME_EINVAL;
+        }
+    EMME_TRY(check_set_indices(c, set, nitems, who.c_str()));
+    return search_contours(c, who, nitems, set, contours, exact, tol, step_limit, max_roots,
+                           {roots, iters, info, n_roots, winding, points_used, status});
 }
 
 int emme_find_roots_in_contour(emme_ctx_t* c, const emme_contour_t* ct, double tol, int step_limit, int max_roots,
@@ -740,140 +680,11 @@ int emme_find_roots_in_contour(emme_ctx_t* c, const emme_contour_t* ct, double t
         set_error(std::string("emme_find_roots_in_contour: ") + bad);
         return EMME_EINVAL;
     }
-    const double cx = ct->center[0], cy = ct->center[1], ea = ct->semi_axes[0], eb = ct->semi_axes[1];
-    const int n = c->dim;
-    if (n > 2048) {
-        set_error("emme_find_roots_in_contour: dim above 2048 is not supported (the factorisation's range)");
-        return EMME_ECONFIG;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    const int cap = ct->max_points;
-    ContourState S;
-    S.c = c, S.n = n;
-    int rc = alloc_state(S, cap, LCAP);
-    if (rc) return rc;
-    rc = make_probes(S);
-    if (rc) return rc;
-    const double rho = std::max(ea, eb);
-    std::vector<int> node_m;  // node k sits at t = 2 pi node_m[k] / cap
-    auto omega_at = [&](int m, double* o) {
-        const double t = 2.0 * M_PI * m / cap;
-        o[0] = cx + ea * std::cos(t), o[1] = cy + eb * std::sin(t);
-    };
-    int L = ct->probes;
-    // fill, factor and solve a batch of new nodes
-    auto add_nodes = [&](const std::vector<int>& ms) -> int {
-        const int cnt = (int)ms.size();
-        int r = ensure_batch(c, cnt);
-        if (r) return r;
-        std::vector<double> om(2 * (size_t)cnt);
-        for (int k = 0; k < cnt; ++k) omega_at(ms[k], &om[2 * k]);
-        S.sets.emplace_back();
-        NodeSet& set = S.sets.back();
-        set.first = (int)node_m.size(), set.count = cnt;
-        HIP_TRY(set.A.grow(sizeof(double) * 2 * (size_t)n * n * cnt));
-        r = upload_omega(c, om.data(), cnt);
-        if (r) return r;
-        r = reset_fill_counters(c, cnt);
-        if (r) return r;
-        FillRequest nodes(cnt, c->d_omega, set.A);
-        nodes.host_omega = om.data();
-        r = fill(c, nodes);
-        if (r) return r;
-        int k = 0;
-        r = collect_fill_status(c, cnt, nullptr, &k);
-        if (r == EMME_ENUMERIC) {
-            char buf[200];
-            snprintf(buf, sizeof buf, "emme_find_roots_in_contour: the fill of the node omega = %.17g%+.17gi failed "
-                     "(quadrature depth cap or non-finite integral)", om[2 * k], om[2 * k + 1]);
-            set_error(buf);
-        }
-        if (r) return r;
-        for (int m : ms) node_m.push_back(m);
-        r = factor_set(S, set, "emme_find_roots_in_contour");
-        if (r) return r;
-        return solve_set(S, set, 0, L);
-    };
-    int N = ct->points;
-    {
-        std::vector<int> ms(N);
-        for (int j = 0; j < N; ++j) ms[j] = j * (cap / N);
-        rc = add_nodes(ms);
-        if (rc) return rc;
-    }
-    // argument principle on the nodes; N doubles by the midpoints while the count is unresolved
-    int W = -1;
-    for (;;) {
-        std::vector<double> ld(2 * node_m.size());
-        // (in order on the context's stream, which may be a non-blocking one: not a null-stream copy)
-        HIP_TRY(hipMemcpyAsync(ld.data(), S.logdet, sizeof(double) * ld.size(), hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(hipStreamSynchronize(c->stream));
-        std::vector<int> ord(node_m.size());
-        for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
-        std::sort(ord.begin(), ord.end(), [&](int x, int y) { return node_m[x] < node_m[y]; });
-        std::vector<double> args(ord.size());
-        for (size_t k = 0; k < ord.size(); ++k) args[k] = ld[2 * ord[k] + 1];
-        bool resolved = false;
-        const int w = contour_winding(args.data(), N, 0.5 * M_PI, &resolved, nullptr);
-        if (resolved) {
-            W = w;
-            break;
-        }
-        if (2 * N > cap) break;
-        std::vector<int> ms(N);
-        for (int j = 0; j < N; ++j) ms[j] = (2 * j + 1) * (cap / (2 * N));
-        rc = add_nodes(ms);
-        if (rc) return rc;
-        N *= 2;
-    }
-    // Beyn: moments with the trapezoid weights of the final N, L doubled while A0 keeps full numerical rank
-    const int nq = (int)node_m.size();
-    std::vector<double> wz(4 * (size_t)nq);
-    for (int k = 0; k < nq; ++k) {
-        const double t = 2.0 * M_PI * node_m[k] / cap;
-        // w = omega'(t) / (i N), z = (omega - c) / rho
-        const double dre = -ea * std::sin(t), dim_ = eb * std::cos(t);
-        wz[4 * k] = dim_ / N, wz[4 * k + 1] = -dre / N;
-        wz[4 * k + 2] = ea * std::cos(t) / rho, wz[4 * k + 3] = eb * std::sin(t) / rho;
-    }
-    std::vector<double> A0(2 * (size_t)n * LCAP), A1(2 * (size_t)n * LCAP), mu(2 * LCAP), sig(LCAP);
-    int k = 0;
-    for (;;) {
-        rc = moments(S, nq, wz, L, A0.data(), A1.data());
-        if (rc) return rc;
-        rc = emme_contour_eigs(n, L, A0.data(), A1.data(), ct->rank_tol, LCAP, mu.data(), &k, sig.data());
-        if (rc) return rc;
-        if (std::getenv("EMME_DEBUG")) {
-            fprintf(stderr, "[emme] contour N %d L %d k %d W %d sigma:", N, L, k, W);
-            for (int l = 0; l < L; ++l) fprintf(stderr, " %.3e", sig[l]);
-            fprintf(stderr, "\n");
-        }
-        if (k < L || L >= LCAP) break;
-        const int L2 = std::min(2 * L, LCAP);
-        for (const NodeSet& set : S.sets) {
-            rc = solve_set(S, set, L, L2 - L);
-            if (rc) return rc;
-        }
-        L = L2;
-    }
-    // the candidates (normalised radius below 1.5: the others are no eigenvalues inside) seed the Newton search
-    std::vector<double> guesses;
-    contour_candidates(*ct, k, mu.data(), guesses);
-    const int ng = (int)guesses.size() / 2;
-    std::vector<ContourRoot> found;
-    if (ng > 0) {
-        std::vector<double> r(2 * ng), path(2 * (size_t)ng * (step_limit + 1));
-        std::vector<int> its(ng), inf(ng);
-        rc = emme_solve_roots(c, guesses.data(), ng, tol, step_limit, r.data(), its.data(), inf.data(), path.data());
-        if (rc) return rc;
-        found = contour_keep_roots(*ct, tol, step_limit, ng, r.data(), its.data(), inf.data(), path.data());
-    }
-    for (int q = 0; q < std::min((int)found.size(), max_roots); ++q)
-        roots[2 * q] = found[q].re, roots[2 * q + 1] = found[q].im, iters[q] = found[q].it, info[q] = found[q].inf;
-    *n_roots = (int)found.size();
-    *winding = W;
-    *points_used = N;
-    return EMME_OK;
+    // one item on the context's own parameters; what takes the item out of the search is the call's error
+    int status = EMME_OK;
+    const int rc = search_contours(c, "emme_find_roots_in_contour", 1, nullptr, ct, 0, tol, step_limit, max_roots,
+                                   {roots, iters, info, n_roots, winding, points_used, &status});
+    return rc ? rc : status;
 }
 
 }  // extern "C"

@@ -223,7 +223,7 @@ std::vector<ContourRoot> contour_keep_roots(const emme_contour_t& ct, double tol
 
 // ---- the round plan of a region search over (set, contour) items -------------------------------
 ContourRounds::ContourRounds(int nitems, const int* set, const emme_contour_t* contours) : items(nitems) {
-    for (int k = 0; k < nitems; ++k) items[k].set = set[k], items[k].ct = contours[k], items[k].L = contours[k].probes;
+    for (int k = 0; k < nitems; ++k) items[k].set = set ? set[k] : 0, items[k].ct = contours[k], items[k].L = contours[k].probes;
 }
 
 bool ContourRounds::plan_nodes() {

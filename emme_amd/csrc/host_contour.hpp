@@ -1,6 +1,8 @@
-// host_contour.hpp -- the host arithmetic of the contour eigensolver (host_contour.cpp, plain C++): what
-// emme_find_roots_in_contour and emme_find_roots_in_contours_sets (contour.hip) use besides the C ABI's
-// emme_contour_eigs.
+// host_contour.hpp -- the host half of the contour eigensolver (host_contour.cpp, plain C++) besides the C ABI's
+// emme_contour_eigs: the argument rules, the count, the candidates and the kept roots of a region search, and its round
+// plan ContourRounds.  The plan is the search: search_contours (contour.hip), the one driver behind
+// emme_find_roots_in_contour and emme_find_roots_in_contours_sets, only carries out on the device what the plan asks
+// for -- which nodes exist, where they sit, what they weigh and when L doubles is decided here and nowhere else.
 #pragma once
 #include <vector>
 
@@ -33,8 +35,9 @@ void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::
 
 // The round plan of a region search over many (parameter set, contour) items that advance in lock step (DESIGN.md
 // §13.9).  No device: the caller fills, factors and solves what the plan asks for and hands the log-dets and ranks
-// back.  Nodes are numbered over the whole call in the order they are created; an item's own nodes are in the order a
-// single search on its contour creates them.
+// back.  Nodes are numbered over the whole call in the order they are created; an item's own nodes do not depend on
+// the other items of the call: the search on one contour is the call with one item.  set null (that search): every
+// item's set is 0 and r_set is not to be read.
 struct ContourRounds {
     struct Item {
         int set = 0;

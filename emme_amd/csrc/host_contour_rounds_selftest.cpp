@@ -1,9 +1,11 @@
 // host_contour_rounds_selftest.cpp -- the round plan of the region search over (parameter set, contour) items
-// (host_contour.cpp: ContourRounds) and the argument rules, candidates and root filter it shares with
-// the single search, built without device code and run under AddressSanitizer + UBSan by `make -C emme_amd/csrc
-// host-sanitize`.  The log-dets a device would hand back are made up: arg det = W t on the item's ellipse, so an item
+// (host_contour.cpp: ContourRounds), of which the search on one contour is the one-item case without a
+// set, and the argument rules, candidates and root filter, built without device code and run under AddressSanitizer +
+// UBSan by `make -C emme_amd/csrc host-sanitize`.  The log-dets a device would hand back are made up: arg det = W t on the item's ellipse, so an item
 // resolves its count once 2 pi W / N <= pi / 2.  Covered: ragged doubling, an item dropped in mid-call, an item at its
-// max_points, two items on one set, L doubling of a subset, nodes without factors left out of the sums.
+// max_points, two items on one set, L doubling of a subset, nodes without factors left out of the sums, the node sequence
+// and weights of one item without a set.
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <string>
@@ -133,6 +135,60 @@ int main() {
         CHECK(two.plan_nodes());
         two.drop(0, EMME_ENUMERIC);
         CHECK(two.plan_moments(info.data(), which, off, idx, wz) && which == std::vector<int>({1}));
+    }
+    // The search on one contour is this plan with one item and no set.  Spelled out, what the driver that
+    // emme_find_roots_in_contour had of its own did with points = 4, max_points = 16 and a count that resolves on 16
+    // nodes: nodes at t = 2 pi m / 16 with m = 0, 4, 8, 12, then the midpoints 2, 6, 10, 14, then the odd m; omega from
+    // the centre and the semi-axes; the count on the nodes sorted by m; the weights of all 16 nodes with the final N.
+    {
+        const double cx = -0.8, cy = 0.2, ea = 0.2, eb = 0.1, rho = std::max(ea, eb);
+        const emme_contour_t c1 = contour(cx, cy, ea, eb, 4, 16, 8);
+        ContourRounds one(1, nullptr, &c1);
+        CHECK(one.items[0].set == 0 && one.items[0].L == 8);
+        const int want_m[16] = {0, 4, 8, 12, 2, 6, 10, 14, 1, 3, 5, 7, 9, 11, 13, 15};
+        const int first[3] = {0, 4, 8}, cnt[3] = {4, 4, 8};
+        const ContourRounds::Item& it = one.items[0];
+        for (int r = 0; r < 3; ++r) {
+            CHECK(one.plan_nodes());
+            CHECK(one.r_first == first[r] && (int)one.r_item.size() == cnt[r] && one.nodes() == first[r] + cnt[r]);
+            CHECK(it.N == first[r] + cnt[r] && (int)it.nodes.size() == it.N && (int)one.r_omega.size() == 2 * cnt[r]);
+            for (int q = 0; q < cnt[r]; ++q) {
+                const int j = first[r] + q, m = want_m[j];
+                CHECK(one.r_item[q] == 0 && it.nodes[j] == j && it.node_m[j] == m);
+                const double t = 2.0 * M_PI * m / 16;
+                CHECK(one.r_omega[2 * q] == cx + ea * std::cos(t) && one.r_omega[2 * q + 1] == cy + eb * std::sin(t));
+            }
+            // steps of 2.8 between neighbours on the contour leave the count open; on 16 nodes arg det = 2 t
+            ld.assign(2 * (size_t)one.nodes(), 0.0);
+            for (int j = 0; j < it.N; ++j)
+                ld[2 * j + 1] = r < 2 ? ((it.node_m[j] / (16 / it.N)) & 1 ? 2.8 : 0.0)
+                                      : std::remainder(2 * 2.0 * M_PI * it.node_m[j] / 16, 2.0 * M_PI);
+            one.take_logdets(ld.data());
+            CHECK(it.adding == (r < 2) && it.W == (r < 2 ? -1 : 2));
+        }
+        CHECK(!one.plan_nodes() && it.N == 16 && one.nodes() == 16);
+        std::vector<int> ok(16, 0);
+        CHECK(one.plan_moments(ok.data(), which, off, idx, wz));
+        CHECK(which == std::vector<int>({0}) && off == std::vector<int>({0, 16}) && wz.size() == 64);
+        for (int j = 0; j < 16; ++j) {
+            // w = omega'(t) / (i N), z = (omega - c) / rho with rho = max(a, b)
+            const double t = 2.0 * M_PI * want_m[j] / 16, dre = -ea * std::sin(t), dim_ = eb * std::cos(t);
+            CHECK(idx[j] == j && wz[4 * j] == dim_ / 16 && wz[4 * j + 1] == -dre / 16);
+            CHECK(wz[4 * j + 2] == ea * std::cos(t) / rho && wz[4 * j + 3] == eb * std::sin(t) / rho);
+        }
+        // a count left open at max_points goes on to the moments all the same, with winding -1
+        const emme_contour_t c2 = contour(cx, cy, ea, eb, 4, 4, 8);
+        ContourRounds capped(1, nullptr, &c2);
+        CHECK(capped.plan_nodes());
+        ld.assign(8, 0.0);
+        ld[3] = ld[7] = 2.8;
+        capped.take_logdets(ld.data());
+        CHECK(!capped.plan_nodes() && capped.items[0].W == -1 && capped.items[0].N == 4);
+        CHECK(capped.plan_moments(ok.data(), which, off, idx, wz) && off.back() == 4);
+        // no set with several items: every item on set 0
+        ContourRounds none(5, nullptr, cts);
+        CHECK(none.plan_nodes() && none.r_item.size() == 40);
+        for (int k = 0; k < 5; ++k) CHECK(none.items[k].set == 0);
     }
     // the argument rules
     {

@@ -393,7 +393,8 @@ void emme_contour_default(emme_contour_t* c);
  * numerical rank, both on the factors already held.  EMME_EINVAL: an ellipse reaching Re omega = 0, non-positive
  * semi-axes, points not a power of two >= 4, max_points < points, probes outside 1..64, rank_tol outside (0, 1);
  * EMME_ECONFIG: dim > 2048; a node whose fill fails (depth cap, non-finite) ends the call with its error, the message
- * names the node.  Chains that did not converge (info != 0, or the last of step_limit + 1 steps still above tol) are
+ * names the node (on that return *n_roots = 0, *winding = -1 and *points_used = the nodes so far are written, as for a
+ * dropped item of emme_find_roots_in_contours_sets: do not read them as a result).  Chains that did not converge (info != 0, or the last of step_limit + 1 steps still above tol) are
  * dropped. */
 int emme_find_roots_in_contour(emme_ctx_t* ctx, const emme_contour_t* c, double tol, int step_limit,
                                int max_roots, double* roots, int* iters, int* info,

@@ -101,7 +101,9 @@ def test_moments_groups_match_numpy_and_the_ungrouped_call(emme, n):
                 dang = np.angle(np.exp(1j * (ld[ok].imag - np.angle(sgn))))
                 assert np.all(np.abs(dang) <= 1e-10)
                 assert np.isneginf(ld[5].real)
-    assert bit_equal  # every (n, L, V, group) measured bit-equal
+    # the two calls share one kernel (k_contour_moments_groups; the ungrouped call is one group), so this holds by
+    # construction; the comparison with the ungrouped kernel that used to be is tests/test_gpu_contour_frozen.py
+    assert bit_equal
 
 
 # ---- 2. the whole search against per-set contexts, electrostatic GK15 ---------------------------------------------
