@@ -172,6 +172,8 @@ def load():
     lib.emme_ctx_set_stream.argtypes = [P, P]
     lib.emme_ctx_set_tile_shapes.argtypes = [P, C.c_int]
     lib.emme_ctx_get_tile_shapes.argtypes = [P]
+    lib.emme_ctx_set_deriv_cache_shapes.argtypes = [P, C.c_int]
+    lib.emme_ctx_get_deriv_cache_shapes.argtypes = [P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
     lib.emme_ctx_last_deferred.argtypes = [P]
@@ -442,6 +444,9 @@ COMM_ID_BYTES = 128
 # emme_ctx_set_tile_shapes (include/emme_hip.h)
 TILE_SHAPES_ES15 = 0
 TILE_SHAPES_ALL = 1
+# emme_ctx_set_deriv_cache_shapes (include/emme_hip.h)
+DERIV_CACHE_SHAPES_ES15 = 0
+DERIV_CACHE_SHAPES_ALL = 1
 
 
 def comm_available() -> bool:
@@ -554,6 +559,18 @@ class Context:
         TILE_SHAPES_ALL (electromagnetic and GK31 contexts as well: k_assemble_tile_shape, and for calls over bound
         parameter sets k_assemble_tile_shape_sets, fill mode 7).  From the next call on."""
         _check(self.lib.emme_ctx_set_tile_shapes(self.h, int(shapes)))
+
+    def set_deriv_cache_shapes(self, shapes: int) -> None:
+        """Which shapes the option deriv_cached sends through the node cache: DERIV_CACHE_SHAPES_ES15 (default:
+        electrostatic GK15 only) or DERIV_CACHE_SHAPES_ALL (electromagnetic and GK31 contexts with the tiled cache as
+        well: k_assemble_dense_shape_deriv).  No effect while deriv_cached = 0.  From the next call on."""
+        _check(self.lib.emme_ctx_set_deriv_cache_shapes(self.h, int(shapes)))
+
+    def deriv_cache_shapes(self) -> int:
+        v = self.lib.emme_ctx_get_deriv_cache_shapes(self.h)
+        if v < 0:
+            _check(v)
+        return v
 
     def tile_shapes(self) -> int:
         v = self.lib.emme_ctx_get_tile_shapes(self.h)

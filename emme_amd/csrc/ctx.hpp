@@ -100,6 +100,9 @@ struct emme_ctx {
     int last_fill_counters = 1;  // ... and how many counters that work list has (3: the sets bound at that fill)
     int tile_shapes = EMME_TILE_SHAPES_ES15;  // shapes the option tile_uncached serves (emme_ctx_set_tile_shapes;
                                // EMME_TILE_SHAPES read at creation)
+    int deriv_cache_shapes = EMME_DERIV_CACHE_SHAPES_ES15;  // shapes whose derivative fills the option deriv_cached sends
+                               // through the node cache (emme_ctx_set_deriv_cache_shapes; EMME_DERIV_CACHE_SHAPES
+                               // read at creation)
     emme_options_t opt{};      // per-context options (emme_options_t; environment overrides applied at creation)
     // HBM cache of omega-independent node records, per contour class (omi = +1, -1)
     int cache_depth = -1;      // -1: not decided yet, -2: disabled / does not fit, else dfull
@@ -188,7 +191,8 @@ struct FillRequest {
     const int* host_active = nullptr;
     double* d_M;
     double* d_Md = nullptr;              // set: the exact dM/domega beside M; through the node cache
-                                         // only with the option deriv_cached, where k_assemble_dense_deriv applies
+                                         // only with the option deriv_cached, where k_assemble_dense_deriv or (derivative
+                                         // cache shapes ALL) k_assemble_dense_shape_deriv applies
     const double* d_Mold = nullptr;      // fused secant: Mp = (M - Mold) / domega
     double* d_Mp = nullptr;
     const double* d_domega = nullptr;

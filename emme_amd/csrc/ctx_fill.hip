@@ -19,11 +19,14 @@ FillShape shape_of(const emme_ctx* c) {
 }
 
 // A derivative request that may go through the node cache (option deriv_cached): k_assemble_dense_deriv
-// exists for electrostatic GK15 on the tiled layout, and the contour classes need the omegas' host values.  Every other
-// derivative request keeps the uncached kernels.
+// exists for electrostatic GK15 on the tiled layout, k_assemble_dense_shape_deriv<PTS, NM> for tiled
+// electromagnetic and GK31 contexts once the context's derivative cache shapes are EMME_DERIV_CACHE_SHAPES_ALL
+// (emme_ctx_set_deriv_cache_shapes), and the contour classes need the omegas' host values.  Every other derivative
+// request keeps the uncached kernels.
+bool deriv_shape_is_es15(const emme_ctx* c) { return c->nm == 1 && c->p.integration_start_points == 15; }
 bool deriv_from_cache(const emme_ctx* c, const FillRequest& r) {
-    return r.d_Md && c->opt.deriv_cached != 0 && c->tiled && c->nm == 1 && c->p.integration_start_points == 15 &&
-           r.host_omega != nullptr;
+    return r.d_Md && c->opt.deriv_cached != 0 && c->tiled &&
+           (deriv_shape_is_es15(c) || c->deriv_cache_shapes == EMME_DERIV_CACHE_SHAPES_ALL) && r.host_omega != nullptr;
 }
 
 // what the fill kernels are told: the context's tables and counters, the request's operands and, for the plain
@@ -234,9 +237,13 @@ int launch_cached_lanes(emme_ctx* c, const AssembleLaunch& L, const NodeCacheVie
 // the integrals that left the cache through the list-driven from-scratch derivative kernel
 int launch_dense_deriv(emme_ctx* c, const AssembleLaunch& L, const NodeCacheView& cache, const FillRequest& r, int n_lane,
                        int nchunks) {
+    // (electromagnetic and GK31 contexts, DESIGN.md 12.5: twin columns too -- 8 electrostatic omegas, 2 x 3 moments)
+    const bool es15 = deriv_shape_is_es15(c);
+    const int chunk_max = es15 ? 8 : dense_shape_deriv_chunk(c->nm);
     for (int k = 0; k < nchunks; ++k)
-        if (c->h_chunks[2 * k + 1] > 8) {
-            set_error("derivative fill: a chunk of more than 8 omegas was planned");
+        if (c->h_chunks[2 * k + 1] > chunk_max) {
+            set_error(es15 ? "derivative fill: a chunk of more than 8 omegas was planned"
+                           : "derivative fill: a chunk wider than the twin-column layout of this shape was planned");
             return EMME_EINVAL;
         }
     const int n_int = node_cache_intervals(c->cache_geom);
@@ -244,16 +251,22 @@ int launch_dense_deriv(emme_ctx* c, const AssembleLaunch& L, const NodeCacheView
     if (need > c->d_btab.bytes()) HIP_TRY(c->d_btab.grow(need + need / 4));
     {
         ScopedSpan s(c, K_OTHER);
-        HIP_TRY(launch_btab_deriv(n_int, cache, r.d_omega, c->d_actidx, n_lane, c->d_chunks + 2 * nchunks, nchunks, c->d_btab,
-                                  c->stream));
+        if (es15)
+            HIP_TRY(launch_btab_deriv(n_int, cache, r.d_omega, c->d_actidx, n_lane, c->d_chunks + 2 * nchunks, nchunks,
+                                      c->d_btab, c->stream));
+        else
+            HIP_TRY(launch_btab_shape_deriv(L.gk_points, c->nm, n_int, cache, r.d_omega, c->d_actidx, n_lane,
+                                            c->d_chunks + 2 * nchunks, nchunks, c->d_btab, c->stream));
     }
     {
         ScopedSpan s(c, K_ASM);
-        HIP_TRY(launch_assemble_dense_deriv(L, cache, c->d_btab, c->d_worklist, c->d_worklist_count, c->d_defer_info,
-                                            c->d_actidx, c->d_chunks, nchunks, c->d_rounds, c->stream));
+        HIP_TRY((es15 ? launch_assemble_dense_deriv : launch_assemble_dense_shape_deriv)(
+            L, cache, c->d_btab, c->d_worklist, c->d_worklist_count, c->d_defer_info, c->d_actidx, c->d_chunks, nchunks,
+            c->d_rounds, c->stream));
     }
     ScopedSpan s(c, K_DEFER);
-    HIP_TRY(launch_assemble_deriv_list(L, c->d_worklist, c->d_worklist_count, c->stream));
+    HIP_TRY((es15 ? launch_assemble_deriv_list : launch_assemble_deriv_list_shape)(L, c->d_worklist, c->d_worklist_count,
+                                                                                   c->stream));
     return EMME_OK;
 }
 
@@ -311,8 +324,9 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
 // are EMME_TILE_SHAPES_ALL (emme_ctx_set_tile_shapes).
 // A derivative request asks for the option deriv_cached as well: it is what hands such a request
 // the host omegas, costs and feedback, and so lets it follow the plain fills' policy.  Neither a tiled layout nor a
-// cache budget is asked for, and the tile shapes count on contexts that have a node cache too, since no derivative
-// request of those shapes reads it (deriv_from_cache).
+// cache budget is asked for, and the tile shapes count on contexts that have a node cache too: a derivative request of
+// those shapes reads it only under EMME_DERIV_CACHE_SHAPES_ALL (deriv_from_cache), and then the cache takes what its
+// policy gives it and the tile fill what that policy leaves without a cache -- the rule of electrostatic GK15.
 bool tile_shape_is_es15(const emme_ctx* c) { return c->nm == 1 && c->p.integration_start_points == 15; }
 bool tile_fill_applies(const emme_ctx* c, const FillRequest& r, bool omega_lane) {
     if (r.d_Md && c->opt.deriv_cached == 0) return false;

@@ -270,6 +270,10 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     // (developer override, read once per context like the options': EMME_TILE_SHAPES=1 is emme_ctx_set_tile_shapes(ALL))
     if (const char* v = std::getenv("EMME_TILE_SHAPES"))
         c->tile_shapes = std::atoi(v) == EMME_TILE_SHAPES_ALL ? EMME_TILE_SHAPES_ALL : EMME_TILE_SHAPES_ES15;
+    // (the same for the shapes of deriv_cached: EMME_DERIV_CACHE_SHAPES=1 is emme_ctx_set_deriv_cache_shapes(ALL))
+    if (const char* v = std::getenv("EMME_DERIV_CACHE_SHAPES"))
+        c->deriv_cache_shapes =
+            std::atoi(v) == EMME_DERIV_CACHE_SHAPES_ALL ? EMME_DERIV_CACHE_SHAPES_ALL : EMME_DERIV_CACHE_SHAPES_ES15;
     const int N = p->npoints;
     c->N = N;
     const bool es = std::fpclassify(p->beta_e) == FP_ZERO;  // include/solver.h:406-407
@@ -367,6 +371,21 @@ int emme_ctx_set_tile_shapes(emme_ctx_t* c, int shapes) {
 }
 
 int emme_ctx_get_tile_shapes(const emme_ctx_t* c) { return c ? c->tile_shapes : EMME_EINVAL; }
+
+int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* c, int shapes) {
+    if (!c) {
+        set_error("emme_ctx_set_deriv_cache_shapes: NULL context");
+        return EMME_EINVAL;
+    }
+    if (shapes != EMME_DERIV_CACHE_SHAPES_ES15 && shapes != EMME_DERIV_CACHE_SHAPES_ALL) {
+        set_error("emme_ctx_set_deriv_cache_shapes: value out of range (EMME_DERIV_CACHE_SHAPES_ES15, EMME_DERIV_CACHE_SHAPES_ALL)");
+        return EMME_EINVAL;
+    }
+    c->deriv_cache_shapes = shapes;
+    return EMME_OK;
+}
+
+int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* c) { return c ? c->deriv_cache_shapes : EMME_EINVAL; }
 
 int emme_ctx_set_stream(emme_ctx_t* c, void* s) {
     if (!c) return EMME_EINVAL;

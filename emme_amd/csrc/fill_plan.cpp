@@ -71,8 +71,9 @@ ChunkPlan plan_chunks(const FillShape& s, const std::vector<int>& order, const u
         // EMME_DENSE_MIN_TASKS (2000; 8000 while every lane ended with a global atomic -- with the counters
         // summed per workgroup 0 .. 3000 are equal, 44.7 ms of fill per bench search, and 8000 costs 45.8)
         // (dense fill: a chunk is 16 COLUMNS -- 16 omegas, or 5 omegas x 3 moments)
-        // (a derivative request, s.deriv: K and K' of an omega are twin columns -- 8 omegas)
-        const int tile_cap = s.deriv ? 8 : 16 / s.nm;
+        // (a derivative request, s.deriv: K and K' of a column are twin columns -- 8 K columns: 8 omegas, or 2 omegas
+        // x 3 moments)
+        const int tile_cap = (s.deriv ? 8 : 16) / s.nm;
         int dense_cap = s.tiled ? tile_cap : gw;
         if (s.tiled) {
             const long ntiles = (s.npairs + 15) / 16;

@@ -15,7 +15,7 @@ struct FillShape {
     int dense_min_tasks = 2000;
     double dense_cost_ratio = 4.0;
     int union_ipg_few = 2, union_few_chunks = 3;
-    bool deriv = false;  // a derivative request on the tiled cache: twin columns, so a chunk holds 8 omegas, never wide
+    bool deriv = false;  // a derivative request on the tiled cache: twin columns, so a chunk holds 8 / nm omegas, never wide
     int lane_group() const { return gk_points == 15 ? 16 : 32; }
 };
 

@@ -128,6 +128,22 @@ hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheV
 hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
                                       const unsigned int* count, hipStream_t stream);
 
+// ---- the same for electromagnetic and GK31 contexts: assemble_dense_shape_deriv.hip (DESIGN.md 12.5;
+// k_assemble_dense_shape_deriv<PTS, NM> for (15, 3), (31, 1), (31, 3); hipErrorInvalidValue for electrostatic GK15,
+// without L.Md or with L.Mold) ------
+// Twin columns: a chunk holds dense_shape_deriv_chunk(nm) omegas -- 8 electrostatic ones, or 2 x 3 moments; column
+// nm w + m of a chunk's phase block is E' W^m of omega w, column nm w + m + 8 its D' = T E' W^m (btab_bytes(cached
+// intervals, chunks, gk_points) as for the plain fill).  Work-list entries are the plain dense fill's,
+// (b << 32) | (pair nm + moment): launch_assemble_deriv_list_shape finishes them.
+int dense_shape_deriv_chunk(int nm);
+hipError_t launch_btab_shape_deriv(int gk_points, int nm, int nslots, const NodeCacheView& cache, const double* omega,
+                                   const int* act_idx, int n_act, const int* wmap, int nchunks, void* btab,
+                                   hipStream_t stream);
+hipError_t launch_assemble_dense_shape_deriv(const AssembleLaunch& L, const NodeCacheView& cache, const void* btab,
+                                             unsigned long long* worklist, unsigned int* worklist_count,
+                                             unsigned long long* defer_info, const int* act_idx, const void* chunks,
+                                             int nchunks, unsigned long long* stats, hipStream_t stream);
+
 // ---- table-free tile fill (no node cache).  One text, assemble_tile_text.hpp, read by one thin translation unit per
 // kernel: EMME_TILE_SHAPE 0 -> assemble_tile.hip, assemble_tile_deriv.hip (electrostatic GK15),
 // EMME_TILE_SHAPE 1 -> assemble_tile_shape.hip, assemble_tile_shape_deriv.hip (electromagnetic, GK31); the parameter-set

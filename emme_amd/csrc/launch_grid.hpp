@@ -17,6 +17,14 @@ inline unsigned lane_group_grid_x(long nitems, int items_per_group, int groups_p
     return (unsigned)gx;
 }
 
+// x extent of a dense fill's grid: one workgroup per (group of 4 tiles, omega chunk).  xcd_grouped: the tile groups are
+// rounded up to a multiple of the eight XCDs, so that workgroup id & 7 names the XCD whose L2 a tile group's chunks share
+// (DESIGN.md 5.1c); the kernel returns at once for the tile groups past the last one
+inline unsigned dense_tile_grid_x(int ntiles, int nchunks, bool xcd_grouped) {
+    const long ntg = (ntiles + 3) / 4;
+    return (unsigned)((xcd_grouped ? (ntg + 7) / 8 * 8 : ntg) * nchunks);
+}
+
 // bytes of the eta | g | b tables of an N-point lattice, padded to a double2 boundary
 inline size_t tables_lds_bytes(int N) { return ((size_t)3 * N + (3 * N & 1)) * sizeof(double); }
 

@@ -116,7 +116,10 @@ typedef struct emme_options {
     /* ---- exact derivative (addition within version 4: present if size covers it) ---- */
     int deriv_cached;         /* 1: derivative fills of electrostatic GK15 contexts with the tiled node cache read and
                                  grow that cache (k_assemble_dense_deriv): derivative fills follow the
-                                 plain fills' policy.  Where that policy finds no cache to read (no budget, a cache that
+                                 plain fills' policy.  Electromagnetic and GK31 contexts with the tiled cache do the same
+                                 once emme_ctx_set_deriv_cache_shapes(EMME_DERIV_CACHE_SHAPES_ALL) is set
+                                 (k_assemble_dense_shape_deriv<PTS, NM>); with the shapes at their
+                                 default they keep the uncached kernels bit for bit.  Where that policy finds no cache to read (no budget, a cache that
                                  does not fit, a call below cache_min_batch, the minority contour class of a call) and
                                  tile_uncached = 1 is set as well, they go through the table-free tile fill
                                  (k_assemble_tile_deriv, DESIGN.md 12.3: electrostatic GK15, integration_accuracy >= 1e-9,
@@ -188,6 +191,24 @@ void emme_release_pooled_memory(void);
 #define EMME_TILE_SHAPES_ALL  1 /* tile_uncached serves electromagnetic and GK31 contexts as well */
 int emme_ctx_set_tile_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range */
 int emme_ctx_get_tile_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
+/* Which shapes the option deriv_cached sends through the node cache (additions within version 4, found by symbol
+ * lookup).  The cached derivative fill exists for all four shapes of the tiled cache: k_assemble_dense_deriv for
+ * electrostatic GK15 and k_assemble_dense_shape_deriv<PTS, NM> for electromagnetic
+ * contexts and the 31-point rule -- K and K' of a column as twin columns of the GEMM, so that a chunk holds 8
+ * electrostatic omegas or 2 omegas x 3 moments.  With EMME_DERIV_CACHE_SHAPES_ALL, derivative fills with host omegas
+ * of such a context that has the tiled cache (emme_assemble_derivative_batch, emme_solve_roots_newton, the exact polish
+ * of emme_find_roots_in_contour) follow the cache policy of the plain fills as electrostatic GK15 ones do under
+ * deriv_cached: same interval trees, M and M' within the project's 1e-10 bar of the uncached fill, the cache may be
+ * built or grown, and emme_ctx_last_deferred reports the integrals that left the cache (finished from scratch by
+ * k_assemble_deriv_list_shape<PTS>).  With tile_uncached = 1 and EMME_TILE_SHAPES_ALL set as well, the cache takes what
+ * its policy gives it and k_assemble_tile_shape_deriv what that policy leaves without a cache.  No effect while
+ * deriv_cached = 0.  Not a layout setting: it may change on a live context and takes effect from the next call.
+ * emme_ctx_fill_mode keeps naming the last plain fill.  Calls over bound parameter sets never read a node cache and
+ * are not affected. */
+#define EMME_DERIV_CACHE_SHAPES_ES15 0 /* default: deriv_cached serves electrostatic GK15 only */
+#define EMME_DERIV_CACHE_SHAPES_ALL  1 /* deriv_cached serves electromagnetic and GK31 contexts as well */
+int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range */
+int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
 /* Launch everything on this hipStream_t (e.g. torch's current stream). NULL = default. */
 int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
@@ -269,7 +290,10 @@ int emme_solve_roots(emme_ctx_t* ctx, const double* guesses, int n, double tol, 
  * set, and emme_ctx_fill_mode keeps naming the last plain fill.  With the option deriv_cached, a call with host omegas
  * on an electrostatic GK15 context with the tiled cache follows the cache policy of emme_assemble_batch instead: M and
  * M' come from the cached records (k_assemble_dense_deriv), the same interval trees, M and M' within the project's
- * 1e-10 bar of the uncached fill, and the cache may be built or grown.  With deriv_cached and tile_uncached
+ * 1e-10 bar of the uncached fill, and the cache may be built or grown.  Electromagnetic and GK31 contexts with the tiled
+ * cache do the same once their derivative cache shapes are EMME_DERIV_CACHE_SHAPES_ALL
+ * (emme_ctx_set_deriv_cache_shapes: k_assemble_dense_shape_deriv<PTS, NM>); at the default they keep the uncached
+ * kernels under deriv_cached.  With deriv_cached and tile_uncached
  * both set, what that policy leaves without a cache goes through k_assemble_tile_deriv where k_assemble_tile would serve
  * the plain fill: M is the plain tile fill's bit for bit, the interval trees are the same, M' is within the same bar, and
  * emme_ctx_last_deferred reports the integrals handed to the from-scratch list kernel.  EMME_ENUMERIC as the plain fill (depth cap, non-finite
@@ -282,7 +306,8 @@ int emme_assemble_derivative_batch(emme_ctx_t* ctx, const double* omega, int nba
  * at the current omega of the live chains.  The step is the context's iteration_method on (M, M'): trace form
  * domega = -1/tr(M^-1 M'), QR form domega = -1/q.  emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) see the
  * last fill's M per chain afterwards.  Derivative fills count in the emme_profile_t fill counters.  With the option
- * deriv_cached the fills of the search go through the node cache where emme_assemble_derivative_batch's would, and
+ * deriv_cached the fills of the search go through the node cache where emme_assemble_derivative_batch's would
+ * (electromagnetic and GK31 contexts: under EMME_DERIV_CACHE_SHAPES_ALL, emme_ctx_set_deriv_cache_shapes), and
  * with tile_uncached as well through the table-free tile fill (k_assemble_tile_deriv) where there is no cache. */
 int emme_solve_roots_newton(emme_ctx_t* ctx, const double* guesses, int n, double tol, int step_limit,
                             double* roots, int* iters, int* info, double* iterates);
