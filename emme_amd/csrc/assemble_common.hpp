@@ -1,5 +1,6 @@
 // assemble_common.hpp -- the leaf pieces that the fill kernels share (assemble.hip, assemble_wl.hip,
-// assemble_cached.hip, assemble_dense.hip, assemble_dense_deriv.hip, assemble_dense_shape_deriv.hip, the table-free tile fills assemble_tile*.hip
+// assemble_cached.hip, assemble_dense.hip, the cached derivative fills assemble_dense_deriv.hip and
+// assemble_dense_shape_deriv.hip through assemble_dense_deriv_text.hpp, the table-free tile fills assemble_tile*.hip
 // through assemble_tile_text.hpp; probe.hip for the tables): the Gauss-Kronrod
 // tables, the caps, the accept / split rule of the adaptive quadrature, kappa_e, the pair weights, the three ways an
 // entry of M is stored, the small helpers of the dense fills and the leaves of the tile fills.  The kernel BODIES stay

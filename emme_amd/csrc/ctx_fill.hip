@@ -239,7 +239,7 @@ int launch_dense_deriv(emme_ctx* c, const AssembleLaunch& L, const NodeCacheView
                        int nchunks) {
     // (electromagnetic and GK31 contexts, DESIGN.md 12.5: twin columns too -- 8 electrostatic omegas, 2 x 3 moments)
     const bool es15 = deriv_shape_is_es15(c);
-    const int chunk_max = es15 ? 8 : dense_shape_deriv_chunk(c->nm);
+    const int chunk_max = dense_shape_deriv_chunk(c->nm);  // (8 for every electrostatic shape)
     for (int k = 0; k < nchunks; ++k)
         if (c->h_chunks[2 * k + 1] > chunk_max) {
             set_error(es15 ? "derivative fill: a chunk of more than 8 omegas was planned"

@@ -115,7 +115,11 @@ hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& c
                                  const void* chunks, int nchunks, unsigned long long* stats, hipStream_t stream,
                                  int n_wide = 0, unsigned int* overflow = nullptr);
 
-// ---- M and the exact dM/domega from the tiled cache: assemble_dense_deriv.hip (electrostatic GK15, L.Md set) ------
+// ---- M and the exact dM/domega from the tiled cache.  One text, assemble_dense_deriv_text.hpp, read by two units
+// (DESIGN.md 12.2.3): EMME_DENSE_DERIV_SHAPE 0 -> assemble_dense_deriv.hip (electrostatic GK15),
+// EMME_DENSE_DERIV_SHAPE 1 -> assemble_dense_shape_deriv.hip (electromagnetic, GK31).  Both launchers answer
+// hipErrorInvalidValue to a shape of the other family, to a missing L.Md and to a set L.Mold. ------
+// -- assemble_dense_deriv.hip: electrostatic GK15 --
 // chunks hold <= 8 omegas: column c of a chunk's phase block is E' of omega c, column c + 8 its D' = T E'
 // (btab_bytes(cached intervals, chunks) as for the plain fill)
 hipError_t launch_btab_deriv(int nslots, const NodeCacheView& cache, const double* omega, const int* act_idx, int n_act,
@@ -128,9 +132,9 @@ hipError_t launch_assemble_dense_deriv(const AssembleLaunch& L, const NodeCacheV
 hipError_t launch_assemble_deriv_list(const AssembleLaunch& L, const unsigned long long* worklist,
                                       const unsigned int* count, hipStream_t stream);
 
-// ---- the same for electromagnetic and GK31 contexts: assemble_dense_shape_deriv.hip (DESIGN.md 12.5;
-// k_assemble_dense_shape_deriv<PTS, NM> for (15, 3), (31, 1), (31, 3); hipErrorInvalidValue for electrostatic GK15,
-// without L.Md or with L.Mold) ------
+// -- assemble_dense_shape_deriv.hip: electromagnetic and GK31 contexts (DESIGN.md 12.5;
+// k_assemble_dense_shape_deriv<PTS, NM> for (15, 3), (31, 1), (31, 3); launch_btab_shape_deriv answers
+// hipErrorNotSupported to electrostatic GK15) --
 // Twin columns: a chunk holds dense_shape_deriv_chunk(nm) omegas -- 8 electrostatic ones, or 2 x 3 moments; column
 // nm w + m of a chunk's phase block is E' W^m of omega w, column nm w + m + 8 its D' = T E' W^m (btab_bytes(cached
 // intervals, chunks, gk_points) as for the plain fill).  Work-list entries are the plain dense fill's,

@@ -25,11 +25,13 @@ def _code_lines(path):
 TILE_UNITS = ["assemble_tile.hip", "assemble_tile_deriv.hip", "assemble_tile_sets.hip", "assemble_tile_sets_deriv.hip",
               "assemble_tile_shape.hip", "assemble_tile_shape_deriv.hip"]
 TILE_SELECTORS = {"EMME_TILE_SHAPE", "EMME_TILE_SETS", "EMME_TILE_DERIV"}
+# the two units of the cached derivative fill and the reading of assemble_dense_deriv_text.hpp that each is
+DENSE_DERIV_UNITS = {"assemble_dense_deriv.hip": "0", "assemble_dense_shape_deriv.hip": "1"}
 
 
 def test_there_are_texts():
-    assert TEXTS == ["assemble_deriv_list_text.hpp", "assemble_nodes_text.hpp", "assemble_sets_list_text.hpp",
-                     "assemble_tile_text.hpp", "assemble_wl_text.hpp"], TEXTS
+    assert TEXTS == ["assemble_dense_deriv_text.hpp", "assemble_deriv_list_text.hpp", "assemble_nodes_text.hpp",
+                     "assemble_sets_list_text.hpp", "assemble_tile_text.hpp", "assemble_wl_text.hpp"], TEXTS
 
 
 def test_every_tile_unit_defines_the_three_selectors():
@@ -40,6 +42,18 @@ def test_every_tile_unit_defines_the_three_selectors():
         defs = [m.group(1) for line in lines[:inc] for m in [re.match(r"\s*#\s*define\s+(\w+)\s+[01]\s*$", line)] if m]
         assert sorted(defs) == sorted(TILE_SELECTORS), (u, defs)
         assert not any(re.match(r"\s*#\s*define\s+EMME_TILE_", line) for line in lines[inc:]), u
+
+
+def test_both_dense_deriv_units_define_the_selector():
+    """The text's one selector, once, to the unit's own value, before the unit reads the text; none after it."""
+    for u, value in DENSE_DERIV_UNITS.items():
+        lines = _code_lines(CSRC / u)
+        inc = next(k for k, line in enumerate(lines)
+                   if re.match(r'\s*#\s*include\s+"assemble_dense_deriv_text\.hpp"', line))
+        defs = [m.groups() for line in lines[:inc]
+                for m in [re.match(r"\s*#\s*define\s+(EMME_DENSE_DERIV_\w+)\s+(\S+)\s*$", line)] if m]
+        assert defs == [("EMME_DENSE_DERIV_SHAPE", value)], (u, defs)
+        assert not any(re.match(r"\s*#\s*define\s+EMME_DENSE_DERIV_", line) for line in lines[inc:]), u
 
 
 def test_every_text_is_a_makefile_header():
