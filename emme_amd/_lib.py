@@ -197,6 +197,8 @@ def load():
     lib.emme_ctx_param_sets.argtypes = [P]
     lib.emme_assemble_sets_batch.argtypes = [P, P, P, C.c_int, P, P, P]
     lib.emme_solve_roots_sets.argtypes = [P, P, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P]
+    lib.emme_solve_eigenpairs.argtypes = [P, P, P, C.c_int, P, C.c_double, C.c_int, P, P, P, P, P, P]
+    lib.emme_eigenpair_step_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P]
     lib.emme_run_json_lockstep.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
     lib.emme_scan_plan.argtypes = [C.c_char_p, C.c_int, P, P, P, P, C.c_int, P, P, P]
     lib.emme_null_vector.argtypes = [P, C.c_int, P]
@@ -826,6 +828,63 @@ class Context:
                                               roots.ctypes.data, iters.ctypes.data, info.ctypes.data,
                                               its.ctypes.data if want_iterates else None))
         return (roots, iters, info, its) if want_iterates else (roots, iters, info)
+
+    # ---- Newton on the eigenpair ----
+    def solve_eigenpairs(self, guesses, set=None, v0=None, tol=None, step_limit=None, want_iterates=False):
+        """Newton on (omega, v) from omega_0 = guesses (emme_solve_eigenpairs): one LU without right-hand sides per step,
+        and the unit eigenvector and the residual |M v| / |M|_F come with the root.  set: chain b on the bound parameter
+        set set[b]; v0 [n, dim]: start vectors (default: from M(omega_0)^-1 s).  Returns (roots, vecs, resid, iters,
+        info[, iterates]); info = 0 also for a chain that used every step -- resid tells."""
+        g = _c128(np.atleast_1d(guesses))
+        n = g.shape[0]
+        st = None
+        if set is not None:
+            st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+            if st.shape[0] != n:
+                raise ValueError("set needs one entry per guess")
+        if v0 is not None:
+            v0 = np.ascontiguousarray(_c128(v0))
+            if v0.shape != (n, self.dim):
+                raise ValueError("v0 must be [len(guesses), dim]")
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros(n, dtype=np.complex128)
+        vecs = np.zeros((n, self.dim), dtype=np.complex128)
+        resid = np.zeros(n, dtype=np.float64)
+        iters = np.zeros(n, dtype=np.int32)
+        info = np.zeros(n, dtype=np.int32)
+        its = np.zeros((n, step_limit + 1), dtype=np.complex128) if want_iterates else None
+        _check(self.lib.emme_solve_eigenpairs(self.h, st.ctypes.data if st is not None else None, g.ctypes.data, n,
+                                              v0.ctypes.data if v0 is not None else None, tol, step_limit,
+                                              roots.ctypes.data, vecs.ctypes.data, resid.ctypes.data, iters.ctypes.data,
+                                              info.ctypes.data, its.ctypes.data if want_iterates else None))
+        return (roots, vecs, resid, iters, info, its) if want_iterates else (roots, vecs, resid, iters, info)
+
+    def eigenpair_step(self, M, Mp, v=None):
+        """One eigenpair step on caller matrices (emme_eigenpair_step_batch): u = M^-1 Mp v, tau = v^H u (domega = -1/tau),
+        resid = |M v| / |M|_F before the step.  v None: the step starts from M^-1 s / |M^-1 s| (include/emme_hip.h).
+        Returns (u / |u|, tau, resid, info)."""
+        M = _c128(M)
+        Mp = _c128(Mp)
+        if M.ndim == 2:
+            M, Mp = M[None], Mp[None]
+        M, Mp = np.ascontiguousarray(M), np.ascontiguousarray(Mp)
+        nb, n = M.shape[0], M.shape[1]
+        if M.shape != (nb, n, n) or Mp.shape != M.shape:
+            raise ValueError("M and Mp must be [nbatch, n, n]")
+        if v is None:
+            vv = np.zeros((nb, n), dtype=np.complex128)
+        else:
+            vv = np.array(_c128(v), dtype=np.complex128, order="C", copy=True).reshape(-1, n)
+            if vv.shape != (nb, n):
+                raise ValueError("v must be [nbatch, n]")
+        tau = np.zeros(nb, dtype=np.complex128)
+        resid = np.zeros(nb, dtype=np.float64)
+        info = np.zeros(nb, dtype=np.int32)
+        _check(self.lib.emme_eigenpair_step_batch(self.h, n, nb, M.ctypes.data, Mp.ctypes.data, vv.ctypes.data,
+                                                  0 if v is None else 1, tau.ctypes.data, resid.ctypes.data,
+                                                  info.ctypes.data))
+        return vv, tau, resid, info
 
     def null_vectors(self, M=None, nbatch=None):
         """nullSpace (include/solver.h:58-112) on the device, batched: right singular vector of the smallest

@@ -139,6 +139,7 @@ struct emme_ctx {
     DeviceBuffer<unsigned int> d_tile_count;
     DeviceBuffer<double> d_M, d_Mold, d_Mp, d_work;  // matrix sets
     DeviceBuffer<double> d_iterates;
+    DeviceBuffer<double> d_vecs, d_resid;  // eigenpair search: the chains' vectors [n][dim], residuals [n]
     int last_n = 0;
     // profiling
     bool prof = false;
@@ -246,7 +247,8 @@ struct LuScratch {
     DeviceBuffer<int> maps;  // row order of the unblocked factorisation
 };
 int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
-                    const std::function<hipError_t(int b0, int nb, const int* maps, int map_nb, const int* lu_info)>& after);
+                    const std::function<hipError_t(int b0, int nb, const int* maps, int map_nb, const int* lu_info)>& after,
+                    const int* d_items = nullptr, int nitems = 0);
 
 // host wall time of the cache allocations (hipMalloc of tens of GB: the cold cost of a context)
 struct AllocTimer {

@@ -1,6 +1,7 @@
 // ctx_linstep.hip -- the Newton linear step and the batched LU above their kernels (linstep*.hip, nullspace.hip):
 // which kernel and how many workgroups a launch gets (linstep_plan.hpp), operands staged where the kernels can read
-// them, and the entry points emme_trace_solve_batch, emme_qr_secant_batch, emme_null_vectors_batch.
+// them, and the entry points emme_trace_solve_batch, emme_qr_secant_batch, emme_null_vectors_batch,
+// emme_eigenpair_step_batch.
 #include "ctx.hpp"
 #include "linstep_plan.hpp"
 
@@ -109,23 +110,34 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
 // snapshots (logical row x of slice item b is physical row maps[(b ceil(n / map_nb) + x / map_nb) n + x]) and their
 // info (0 or the column at which the factorisation stopped), both valid until the next slice is factored.  Used by
 // emme_null_vectors_batch and the contour solver (contour.hip); the launches are stream-ordered on c->stream.
+// With an item list (d_items: device list of nitems batch indices, the root search's live chains) only the listed
+// matrices are factored, and nothing is relative to a slice: `after(i0, ni, ...)` gets the list positions i0 .. i0 + ni
+// - 1 of the slice, maps and lu_info are indexed by the batch index itself, and the info goes to c->d_info[b].  (A
+// context whose multi-workgroup LU has timed out once, lu_one_wg, takes the unblocked kernel instead of the chunked.)
 int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
-                    const std::function<hipError_t(int, int, const int*, int, const int*)>& after) {
+                    const std::function<hipError_t(int, int, const int*, int, const int*)>& after, const int* d_items,
+                    int nitems) {
     const size_t mbytes = batch_bytes(n, 1);
     const bool one_wg = trace_solve_blocked_lds(n) <= 150 * 1024;  // the whole L21 panel in one workgroup's LDS
-    if (one_wg || n <= 1024) {
-        const int slice_max = one_wg ? nbatch : std::max(1, c->n_cu / 2);
-        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, std::min(nbatch, slice_max))));
-        if (!one_wg) HIP_TRY(s.b.grow(mbytes * std::min(nbatch, slice_max)));
-        for (int b0 = 0; b0 < nbatch; b0 += slice_max) {
-            const int nb = std::min(slice_max, nbatch - b0);
-            double* a0 = work + (size_t)b0 * n * n * 2;
+    const int todo = d_items ? nitems : nbatch;  // matrices to factor
+    if (todo < 1) return EMME_OK;
+    if (one_wg || (n <= 1024 && !(d_items && c->lu_one_wg))) {
+        const int slice_max = one_wg ? todo : std::max(1, c->n_cu / 2);
+        // (with a list the kernels index scratch, right-hand sides and row orders by the batch index)
+        const int held = d_items ? nbatch : std::min(nbatch, slice_max);
+        HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, held)));
+        if (!one_wg) HIP_TRY(s.b.grow(mbytes * held));
+        for (int b0 = 0; b0 < todo; b0 += slice_max) {
+            const int nb = std::min(slice_max, todo - b0);
+            double* a0 = d_items ? work : work + (size_t)b0 * n * n * 2;
+            const int* list = d_items ? d_items + b0 : nullptr;
+            const int dimb = d_items ? nbatch : nb;  // what the kernels' batch index runs over
             ScopedSpan sp(c, K_NULL);
             if (one_wg) {
-                HIP_TRY(launch_lu_inplace(n, nb, a0, nullptr, nb, c->d_info, c->d_lu_scratch, c->stream));
+                HIP_TRY(launch_lu_inplace(n, dimb, a0, list, nb, c->d_info, c->d_lu_scratch, c->stream));
             } else {
-                HIP_TRY(hipMemsetAsync(s.b, 0, mbytes * nb, c->stream));
-                const hipError_t e = launch_trace_solve_blocked(n, nb, a0, s.b, nullptr, c->d_tr, c->d_info, 2, nullptr, nb,
+                HIP_TRY(hipMemsetAsync(s.b, 0, mbytes * dimb, c->stream));
+                const hipError_t e = launch_trace_solve_blocked(n, dimb, a0, s.b, nullptr, c->d_tr, c->d_info, 2, list, nb,
                                                                 c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
@@ -133,13 +145,13 @@ int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, 
                     return EMME_EDEVICE;
                 }
             }
-            HIP_TRY(after(b0, nb, trace_solve_rowmaps(c->d_lu_scratch, n, nb), trace_solve_nb(), c->d_info));
+            HIP_TRY(after(b0, nb, trace_solve_rowmaps(c->d_lu_scratch, n, dimb), trace_solve_nb(), c->d_info));
         }
     } else {
         HIP_TRY(s.maps.grow(sizeof(int) * (size_t)n * nbatch));
         ScopedSpan sp(c, K_NULL);
-        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, s.maps, c->d_info, c->stream));
-        HIP_TRY(after(0, nbatch, s.maps, n, c->d_info));
+        HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, s.maps, c->d_info, c->stream, d_items, nitems));
+        HIP_TRY(after(0, todo, s.maps, n, c->d_info));
     }
     return EMME_OK;
 }
@@ -249,6 +261,51 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
                               });
     if (rc) return rc;
     HIP_TRY(hipMemcpyAsync(vecs, t_v, sizeof(double) * 2 * (size_t)n * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
+}
+
+// One eigenpair step (eigpair.hip) on caller matrices, which are not modified
+int emme_eigenpair_step_batch(emme_ctx_t* c, int n, int nbatch, const double* M, const double* Mp, double* v, int have_v,
+                              double* tau, double* resid, int* info) {
+    if (!c || !M || !Mp || !v || !tau || !resid || !info || n < 1 || nbatch < 1) {
+        set_error("emme_eigenpair_step_batch: a required pointer is NULL, n < 1 or nbatch < 1");
+        return EMME_EINVAL;
+    }
+    if (n > 2048) {
+        set_error("emme_eigenpair_step_batch: order above 2048 is not supported");
+        return EMME_ECONFIG;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    const size_t bytes = batch_bytes(n, nbatch), vbytes = sizeof(double) * 2 * (size_t)n * nbatch;
+    DeviceOperands ops;
+    hipError_t staged = hipSuccess;
+    EMME_TRY(ops.stage(c, M, Mp, bytes, &staged));
+    HIP_TRY(staged);
+    // device scratch of this call: the work copy the factorisation overwrites, vectors, tau, residuals, info
+    DeviceBuffer<double> t_a, t_v, t_tau, t_res;
+    DeviceBuffer<int> t_info;
+    HIP_TRY(t_a.grow(bytes));
+    HIP_TRY(t_v.grow(vbytes));
+    HIP_TRY(t_tau.grow(sizeof(double) * 2 * nbatch));
+    HIP_TRY(t_res.grow(sizeof(double) * nbatch));
+    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
+    HIP_TRY(hipMemcpyAsync(t_a, ops.A, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (have_v) HIP_TRY(hipMemcpyAsync(t_v, v, vbytes, hipMemcpyHostToDevice, c->stream));
+    LuScratch scratch;
+    const int rc = lu_factor_batch(c, n, nbatch, t_a, scratch, "emme_eigenpair_step_batch",
+                                   [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+                                       const size_t m0 = (size_t)b0 * n * n * 2;
+                                       return launch_eigpair_step(n, ops.A + m0, ops.B + m0, t_a + m0, maps, map_nb, nullptr, nb,
+                                                                  nullptr, lu_info, t_v + (size_t)b0 * n * 2, t_tau + 2 * b0,
+                                                                  t_res + b0, t_info + b0, !have_v, c->stream);
+                                   });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(v, t_v, vbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tau, t_tau, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(resid, t_res, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     return EMME_OK;

@@ -1,7 +1,8 @@
 // ctx_search.hip -- the two root searches: what stands where the reference has EigenSolver's constructor and
 // newtonTraceSecantIteration (include/solver.h:396-415, 113-160) under the solve_once_eigen loop (src/main.cpp:19-80),
-// and the Newton search on the exact derivative.  Entry points: emme_solve_roots,
-// emme_solve_roots_newton, emme_newton_step_batch.
+// the Newton search on the exact derivative and, in the same loop, Newton on the eigenpair.
+// Entry points: emme_solve_roots, emme_solve_roots_newton, emme_solve_roots_sets, emme_solve_eigenpairs,
+// emme_newton_step_batch.
 #include "ctx.hpp"
 
 using namespace emme;
@@ -18,6 +19,9 @@ struct RootSearch {
     bool want_iterates;
     int method = 0;
     const int* set = nullptr;  // host, n ints: chain b searches on the bound parameter set set[b] (null: the context's own)
+    bool eigpair = false;      // newton_loop's linear step is the eigenpair step: `method` is not consulted
+    const double* v0 = nullptr;  // eigenpair search: host, n * dim complex unit start vectors (null: from M(omega_0)^-1 s)
+    LuScratch lu;              // ... and what its factorisations keep between launches
     std::vector<int> act, zeros;  // host image of d_active (every chain live at the start); n zeros
     int stride() const { return step_limit + 1; }
     // the parameter sets of the chains (uploaded by search_begin), for the loops' FillRequests
@@ -43,6 +47,12 @@ int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
     }
     s.act.assign(n, 1), s.zeros.assign(n, 0);
     if (s.set) EMME_TRY(upload_set_indices(c, s.set, n));
+    if (s.eigpair) {
+        const size_t vbytes = sizeof(double) * 2 * (size_t)n * c->dim;
+        HIP_TRY(c->d_vecs.grow(vbytes));
+        HIP_TRY(c->d_resid.grow(sizeof(double) * n));
+        if (s.v0) HIP_TRY(hipMemcpyAsync(c->d_vecs, s.v0, vbytes, hipMemcpyHostToDevice, c->stream));
+    }
     HIP_TRY(hipMemcpyAsync(c->d_active, s.act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_iters, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(hipMemcpyAsync(c->d_info, s.zeros.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
@@ -196,7 +206,32 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     return EMME_OK;
 }
 
-// The Newton search of emme_solve_roots_newton, between search_begin and search_end.
+// One eigenpair step (eigpair.hip) for the chains still iterating, on the work copies newton_loop has just made:
+// factor the live ones only (lu_factor_batch with their list; its launches count as K_NULL spans), then
+// k_eigpair_step on the same list leaves tau in d_tr for launch_newton_update, the new vectors in d_vecs and the
+// residual before the step in d_resid.  A factorisation that stops leaves the column in d_info: the chain retires.
+int eigpair_step(emme_ctx* c, RootSearch& search, bool first) {
+    const int n = search.n, dim = c->dim;
+    int* slot = nullptr;
+    HIP_TRY(c->d_lu_items.grow(sizeof(int) * n));
+    HIP_TRY(c->lists.take(n, &slot));
+    int n_live = 0;
+    for (int b = 0; b < n; ++b)
+        if (search.act[b] == 1) slot[n_live++] = b;  // (2: converged at the last step and retired behind its fill)
+    if (n_live == 0) return EMME_OK;
+    HIP_TRY(launch_stage_ints(slot, c->d_lu_items, n_live, nullptr, 0, c->stream));
+    HIP_TRY(c->lists.read_on(c->stream));
+    return lu_factor_batch(
+        c, dim, n, c->d_work, search.lu, "emme_solve_eigenpairs",
+        [&](int i0, int ni, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+            return launch_eigpair_step(dim, c->d_M, c->d_Mp, c->d_work, maps, map_nb, c->d_lu_items + i0, ni, c->d_active,
+                                       lu_info, c->d_vecs, c->d_tr, c->d_resid, c->d_info, first, c->stream);
+        },
+        c->d_lu_items, n_live);
+}
+
+// The Newton search of emme_solve_roots_newton, between search_begin and search_end; with
+// search.eigpair, that of emme_solve_eigenpairs: the same loop around another linear step.
 int newton_loop(emme_ctx* c, RootSearch& search) {
     const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
     const double tol = search.tol;
@@ -239,10 +274,13 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
             // both operands; M' is filled again before it is needed), QR form on the transpose
             ScopedSpan s(c, K_LIN);
             const bool trace = method == EMME_METHOD_TRACE_SECANT;
-            if (trace) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
-            HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
-                                act.data(), trace));
+            if (trace || search.eigpair) HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
+            if (!search.eigpair)
+                HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
+                                    act.data(), trace));
         }
+        // the eigenpair search: d_tr <- v^H M^-1 M' v instead, and the chain's vector moves with it
+        if (search.eigpair) EMME_TRY(eigpair_step(c, search, j == 0 && !search.v0));
         {
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
@@ -271,16 +309,25 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
             HIP_TRY(publish());
         }
     }
+    if (search.eigpair) {
+        // every chain whose last step was followed by a fill (converged, or out of steps): the residual of what is
+        // returned, omega and v, on that matrix.  (Chains that failed hold anything: emme_solve_eigenpairs blanks them.)
+        ScopedSpan s(c, K_LIN);
+        HIP_TRY(launch_eigpair_resid(c->dim, c->d_M, nullptr, n, c->d_vecs, c->d_resid, c->stream));
+    }
     return EMME_OK;
 }
 
+// eigpair: the eigenpair search (newton_loop only; v0: its start vectors or null), which consults no iteration method
 int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_limit, double* roots, int* iters, int* info,
-               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&), const int* set = nullptr) {
+               double* iterates, int mat_sets, int (*loop)(emme_ctx*, RootSearch&), const int* set = nullptr,
+               bool eigpair = false, const double* v0 = nullptr) {
     if (!c || !guesses || !roots || !iters || !info || n < 1 || step_limit < 0) return EMME_EINVAL;
     RootSearch s{guesses, n, tol, step_limit, iterates != nullptr};
     s.method = c->p.iteration_method;  // src/main.cpp:45-49
     s.set = set;
-    EMME_TRY(check_method(c, s.method));
+    s.eigpair = eigpair, s.v0 = v0;
+    if (!eigpair) EMME_TRY(check_method(c, s.method));
     HIP_TRY(hipSetDevice(c->device));
     for (;;) {
         bool repeat = false;
@@ -368,6 +415,49 @@ int emme_solve_roots_sets(emme_ctx_t* c, const int* set, const double* guesses, 
     EMME_TRY(check_set_indices(c, set, n, "emme_solve_roots_sets"));
     return exact ? run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop, set)
                  : run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 2 | 4 | 8, secant_loop, set);
+}
+
+// Newton on the eigenpair: newton_loop around k_eigpair_step
+int emme_solve_eigenpairs(emme_ctx_t* c, const int* set, const double* guesses, int n, const double* v0, double tol,
+                          int step_limit, double* roots, double* vecs, double* resid, int* iters, int* info,
+                          double* iterates) {
+    if (!c || !guesses || !roots || !vecs || !resid || !iters || !info || n < 1 || step_limit < 0 || !(tol > 0.0)) {
+        set_error("emme_solve_eigenpairs: a required pointer is NULL, n < 1, step_limit < 0 or tol <= 0");
+        return EMME_EINVAL;
+    }
+    const int dim = c->dim;
+    if (dim > 2048) {
+        set_error("emme_solve_eigenpairs: matrix dimension above 2048 is not supported");
+        return EMME_ECONFIG;
+    }
+    if (set) EMME_TRY(check_set_indices(c, set, n, "emme_solve_eigenpairs"));
+    std::vector<double> vn;  // the caller's start vectors, each of unit 2-norm
+    if (v0) {
+        vn.assign(v0, v0 + 2 * (size_t)n * dim);
+        for (int b = 0; b < n; ++b) {
+            double* row = vn.data() + 2 * (size_t)b * dim;
+            double s2 = 0.0;
+            for (int i = 0; i < 2 * dim; ++i) s2 += row[i] * row[i];
+            const double nrm = std::sqrt(s2);
+            if (!(nrm > 0.0) || !std::isfinite(nrm)) {
+                set_error("emme_solve_eigenpairs: v0 row " + std::to_string(b) + " is zero or not finite");
+                return EMME_EINVAL;
+            }
+            for (int i = 0; i < 2 * dim; ++i) row[i] /= nrm;
+        }
+    }
+    EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop, set, true,
+                        v0 ? vn.data() : nullptr));
+    HIP_TRY(hipMemcpyAsync(vecs, c->d_vecs, sizeof(double) * 2 * (size_t)n * dim, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(resid, c->d_resid, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int b = 0; b < n; ++b)
+        if (info[b] != 0) {  // a failed chain has no pair
+            std::fill(vecs + 2 * (size_t)b * dim, vecs + 2 * (size_t)(b + 1) * dim, qnan);
+            resid[b] = qnan;
+        }
+    return EMME_OK;
 }
 
 }  // extern "C"

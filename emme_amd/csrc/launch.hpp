@@ -287,13 +287,29 @@ int trace_solve_nb();  // rows per panel = rows per row-order snapshot of the bl
 // row-order snapshots inside a blocked factorisation's scratch: logical row x of matrix b is physical row
 // maps[(b ceil(n / nb) + x / nb) n + x]
 const int* trace_solve_rowmaps(const void* scratch, int n, int nbatch);
-// any order up to ~8000: unblocked, slow; maps [nbatch][n] receives the row order (one snapshot, nb = n)
-hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream);
+// any order up to ~8000: unblocked, slow; maps [nbatch][n] receives the row order (one snapshot, nb = n); items
+// (device list of nitems batch indices, null = all nbatch): the matrices to factor
+hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream,
+                                       const int* items = nullptr, int nitems = 0);
 size_t null_iterate_lds(int n);
 // right singular vector of the smallest singular value of every matrix, from its in-place LU: vecs [nbatch][n]
 // complex, info 0 / lu_info's code / EMME_ENUMERIC for a non-finite result
 hipError_t launch_null_iterate(int n, const double* A_lu, const int* rowmaps, int nb, const int* items, int nitems,
                                const int* lu_info, double* vecs, int* info, int max_sweeps, hipStream_t stream);
+
+// ---- Newton on the eigenpair (eigpair.hip) ------------------------------------------------
+// One step per listed matrix (items: device list of nitems batch indices, null = 0 .. nitems-1; active, nullable: an
+// item whose flag is 0 is left alone): resid[b] = |M v| / |M|_F on the un-factored M, u = M^-1 M' v through the factors
+// A_lu / rowmaps / nb / lu_info of launch_null_iterate, tau[b] = v^H u, vecs[b] <- u / |u|.  first: v is not read but
+// started at M^-1 s / |M^-1 s|, s[i] = (1 + 0.37 sin(1 + i)) + 0.21 cos(2 i) i (include/emme_hip.h).  info[b]: 0,
+// lu_info's code (vector, tau and resid NaN) or EMME_ENUMERIC for a non-finite tau or u.  n <= 2048
+// (null_iterate_lds(n) of LDS).  Two runs are bit-identical.
+hipError_t launch_eigpair_step(int n, const double* M, const double* Mp, const double* A_lu, const int* rowmaps, int nb,
+                               const int* items, int nitems, const int* active, const int* lu_info, double* vecs,
+                               double* tau, double* resid, int* info, bool first, hipStream_t stream);
+// the residual alone, in the same order of sums: no factors are read, vecs is left as it is
+hipError_t launch_eigpair_resid(int n, const double* M, const int* items, int nitems, const double* vecs, double* resid,
+                                hipStream_t stream);
 
 // QR-secant form of the step (linstep_qr.hip, reference include/solver.h:210-383): Wt holds the
 // TRANSPOSE of each matrix (destroyed), Mp the secant derivative (read only); writes

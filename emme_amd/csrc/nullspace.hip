@@ -14,33 +14,21 @@
 // order in panel snapshots.  k_null_iterate then runs the four triangular solves of a sweep with one
 // 1024-thread workgroup per matrix: the non-transposed ones in dot form (a wave per row of a 16-row block,
 // rows are contiguous), the transposed ones in axpy form (a thread per column, the 16 rows of the block are
-// contiguous across threads), the 16 x 16 triangles by one wave with the block's entries in registers.
+// contiguous across threads), the 16 x 16 triangles by one wave with the block's entries in registers.  The solves
+// themselves live in tri_solve.hpp, which k_eigpair_step (eigpair.hip) reads too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <type_traits>
 
 #include "emme_device.hpp"
 #include "launch.hpp"
+#include "tri_solve.hpp"
 
 namespace emme {
 
 namespace {
 
-constexpr int NT = 512;  // (256 vector registers per thread: the chain wave holds two 16 x 16 coefficient rows)
-constexpr int NW = NT / 64;
-constexpr int TB = 16;  // rows per block of the triangular solves
-
-__device__ __forceinline__ cd ld2(const double2* p) {
-    const double2 v = *p;
-    return mk(v.x, v.y);
-}
-__device__ __forceinline__ cd conj_(cd a) { return mk(a.x, -a.y); }
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-    return v;
-}
+using namespace trisolve;  // NT, NW, TB, ld2, conj_, wave_sum and the triangular solves (tri_solve.hpp)
 
 struct NullArgs {
     int n, nb, nblk;       // order; rows per panel snapshot and snapshots per matrix of the factorisation
@@ -90,122 +78,15 @@ __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
         for (int i = tid; i < n; i += NT) v[i] = make_double2(v[i].x * r, v[i].y * r);
         __syncthreads();
     };
-    // ---- the triangular solves, pipelined over blocks of TB = 16 unknowns ------------------------------------------------
-    // One right-hand side is a chain of n dependent steps whatever one does; what can be taken OFF that chain is
-    // everything else.  Per stage (one block of 16 unknowns) the workgroup splits into
-    //   wave 0   the chain: rhs of the block's 16 equations (already updated with all blocks but the previous one),
-    //            minus the previous block's coupling (16 x 16, the previous solution still in its registers, read with
-    //            v_readlane), then the 16 x 16 triangle -- 32 readlane steps, operands from LDS;
-    //   wave 1   stages the NEXT stage's two 16 x 16 coefficient blocks from the factors (global memory) into LDS;
-    //   others   apply the PREVIOUS block's solution to all equations beyond the next block;
-    // and ONE barrier ends the stage.  (The first version had wave 0 wait for the other waves' dots and the other
-    // waves wait for wave 0's triangle, two barriers and a global-memory latency per block on the chain: 0.3 ms per
-    // sweep at n = 256, 19 ms for the 128 matrices of the headline search, eight of which are not singular and take
-    // all 60 sweeps.)
-    // coef(i, j) = coefficient of unknown j in equation i:  M(i, j) = a[rowmap[i] n + j] of the factor, or conj M(j, i)
-    // for the transposed systems; LOWER = unit diagonal (L, L^H), else divide by coef(i, i) (U, U^H).
-    double2* bA = sm + 3 * (size_t)n + ((size_t)n * sizeof(int) + 15) / 16;  // [2][TB][TB + 1] coupling with the previous block
-    double2* bD = bA + 2 * TB * (TB + 1);                                     // [2][TB][TB + 1] the block's own triangle
-    const int B = (n + TB - 1) / TB;
-    auto readlane_c = [&](cd x, int k) -> cd {
-        const long long bx = __double_as_longlong(x.x), by = __double_as_longlong(x.y);
-        const unsigned xl = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)bx, k), xh = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(bx >> 32), k);
-        const unsigned yl = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)by, k), yh = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(by >> 32), k);
-        return mk(__longlong_as_double((long long)(((unsigned long long)xh << 32) | xl)), __longlong_as_double((long long)(((unsigned long long)yh << 32) | yl)));
-    };
-    // x: right-hand side on entry, solution on exit (LDS, indexed by equation = unknown)
-    auto solve_tri = [&](auto trans_tag, auto lower_tag, double2* x) {
-        constexpr bool TRANS = decltype(trans_tag)::value, LOWER = decltype(lower_tag)::value;
-        constexpr bool FWD = LOWER != TRANS;
-        auto blk0 = [&](int s) { return (FWD ? s : B - 1 - s) * TB; };   // first unknown of the block of stage s
-        auto blkn = [&](int s) { return min(TB, n - blk0(s)); };
-        // stage the coefficient blocks of stage s (equations of block s x unknowns of block s - 1 / of block s)
-        auto stage_blocks = [&](int s) {
-            const int r1 = blk0(s), n1 = blkn(s);
-            const int rp = s > 0 ? blk0(s - 1) : 0, np = s > 0 ? blkn(s - 1) : 0;
-            double2* dA = bA + (s & 1) * TB * (TB + 1);
-            double2* dD = bD + (s & 1) * TB * (TB + 1);
-#pragma unroll
-            for (int it = 0; it < 4; ++it) {
-                const int e = it * 64 + lane;
-                // (contiguous in memory along the fast index: columns of a row for the plain systems, rows for the transposed)
-                const int l = TRANS ? (e & 15) : (e >> 4), kk = TRANS ? (e >> 4) : (e & 15);
-                double2 va = make_double2(0.0, 0.0), vd = make_double2(0.0, 0.0);
-                if (l < n1 && kk < n1) {
-                    vd = TRANS ? a[(size_t)rowmap[r1 + kk] * n + r1 + l] : a[(size_t)rowmap[r1 + l] * n + r1 + kk];
-                    if (TRANS) vd.y = -vd.y;
-                }
-                if (l < n1 && kk < np) {
-                    va = TRANS ? a[(size_t)rowmap[rp + kk] * n + r1 + l] : a[(size_t)rowmap[r1 + l] * n + rp + kk];
-                    if (TRANS) va.y = -va.y;
-                }
-                dA[l * (TB + 1) + kk] = va, dD[l * (TB + 1) + kk] = vd;
-            }
-        };
-        if (wave == 1) stage_blocks(0);
-        __syncthreads();
-        cd xprev = mk(0.0, 0.0);  // wave 0: the previous block's solution, unknown kk in lane kk
-        for (int s = 0; s < B; ++s) {
-            const int r0 = blk0(s), nbk = blkn(s);
-            if (wave == 0) {
-                const double2* dA = bA + (s & 1) * TB * (TB + 1) + (lane & 15) * (TB + 1);
-                const double2* dD = bD + (s & 1) * TB * (TB + 1) + (lane & 15) * (TB + 1);
-                const bool on = lane < nbk;
-                cd sv = on ? mk(x[r0 + lane].x, x[r0 + lane].y) : mk(0.0, 0.0);
-                cd ca[TB], cdg[TB];
-#pragma unroll
-                for (int kk = 0; kk < TB; ++kk) ca[kk] = mk(dA[kk].x, dA[kk].y), cdg[kk] = mk(dD[kk].x, dD[kk].y);
-                if (s > 0) {
-#pragma unroll
-                    for (int kk = 0; kk < TB; ++kk) sv = sv - ca[kk] * readlane_c(xprev, kk);  // (rows beyond the block hold zeros)
-                }
-#pragma unroll
-                for (int q = 0; q < TB; ++q) {
-                    const int kk = FWD ? q : TB - 1 - q;
-                    if (kk < nbk) {  // uniform
-                        if (!LOWER && lane == kk) sv = sv * rcp(cdg[kk]);
-                        const cd xk = readlane_c(sv, kk);
-                        if (on && (FWD ? lane > kk : lane < kk)) sv = sv - cdg[kk] * xk;
-                    }
-                }
-                if (on) x[r0 + lane] = make_double2(sv.x, sv.y);
-                xprev = sv;
-            } else if (wave == 1) {
-                if (s + 1 < B) stage_blocks(s + 1);
-            } else if (s > 0) {
-                // apply the previous block's solution (final in x since the last barrier) to the equations beyond this block
-                const int rp = blk0(s - 1), np = blkn(s - 1);
-                const int lo = FWD ? r0 + nbk : 0, hi = FWD ? n : r0;  // equations [lo, hi)
-                if (!TRANS) {
-                    // 16 contiguous coefficients per equation: four equations per wave and trip, 16-lane sums
-                    const int kk = lane & 15;
-                    const cd xk = kk < np ? mk(x[rp + kk].x, x[rp + kk].y) : mk(0.0, 0.0);
-                    for (int i = lo + (wave - 2) * 4 + (lane >> 4); i < hi; i += (NW - 2) * 4) {
-                        const cd c = kk < np ? ld2(&a[(size_t)rowmap[i] * n + rp + kk]) : mk(0.0, 0.0);
-                        const cd pr = c * xk;
-                        const double sx = row16_sum(pr.x), sy = row16_sum(pr.y);
-                        if (kk == 0) x[i] = make_double2(x[i].x - sx, x[i].y - sy);
-                    }
-                } else {
-                    // coefficients of one unknown are contiguous along the equations: an equation per thread
-                    for (int i = lo + (wave - 2) * 64 + lane; i < hi; i += (NW - 2) * 64) {
-                        cd acc = mk(x[i].x, x[i].y);
-#pragma unroll
-                        for (int kk = 0; kk < TB; ++kk)
-                            if (kk < np) acc = acc - conj_(ld2(&a[(size_t)rowmap[rp + kk] * n + i])) * mk(x[rp + kk].x, x[rp + kk].y);
-                        x[i] = make_double2(acc.x, acc.y);
-                    }
-                }
-            }
-            __syncthreads();
-        }
-    };
-    using T_ = std::true_type;
-    using F_ = std::false_type;
+    // the triangular solves, pipelined over blocks of TB = 16 unknowns: tri_solve.hpp
+    Factors F;
+    F.n = n, F.a = a, F.rowmap = rowmap;
+    F.bA = sm + 3 * (size_t)n + rowmap_slots(n);  // [2][TB][TB + 1] coupling with the previous block
+    F.bD = F.bA + 2 * TB * (TB + 1);              // [2][TB][TB + 1] the block's own triangle
     // z = M^-H b:  U^H w = b, L^H z' = w, z = P^T z'
     auto solve_h = [&]() {
-        solve_tri(T_{}, F_{}, v);
-        solve_tri(T_{}, T_{}, v);
+        solve_tri<true, false>(F, v);
+        solve_tri<true, true>(F, v);
         for (int r = tid; r < n; r += NT) t[rowmap[r]] = v[r];
         __syncthreads();
         for (int r = tid; r < n; r += NT) v[r] = t[r];
@@ -213,10 +94,7 @@ __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
     };
     // y = M^-1 b:  c = P b, L c' = c, U y = c'
     auto solve_n = [&]() {
-        for (int r = tid; r < n; r += NT) t[r] = v[rowmap[r]];
-        __syncthreads();
-        solve_tri(F_{}, T_{}, t);
-        solve_tri(F_{}, F_{}, t);
+        solve_plain(F, v, t);
         for (int r = tid; r < n; r += NT) v[r] = t[r];
         __syncthreads();
     };
@@ -257,14 +135,14 @@ __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
 // workgroup per matrix, the pivot row staged in LDS, rows never moved (row map in LDS, written out as ONE
 // snapshot: nb = n).  O(n) barriers per column block of one -- slow, and only there so that every order the
 // Newton step accepts has a device nullSpace too.
-__global__ __launch_bounds__(NT) void k_lu_unblocked_inplace(int n, double2* A, int* maps, int* info_out) {
+__global__ __launch_bounds__(NT) void k_lu_unblocked_inplace(int n, double2* A, int* maps, int* info_out, const int* items) {
     extern __shared__ double2 sm[];
     __shared__ double s_val[NW];
     __shared__ int s_idx[NW];
     __shared__ int s_piv, s_info;
     double2* prow = sm;
     int* rowmap = reinterpret_cast<int*>(sm + n);
-    const int b = blockIdx.x;
+    const int b = items ? items[blockIdx.x] : blockIdx.x;
     double2* a = A + (size_t)b * n * n;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int r = tid; r < n; r += NT) rowmap[r] = r;
@@ -327,14 +205,16 @@ size_t null_iterate_lds(int n) {
     return (size_t)3 * n * sizeof(double2) + (((size_t)n * sizeof(int) + 15) / 16) * 16 + (size_t)4 * TB * (TB + 1) * sizeof(double2);
 }
 
-hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream) {
+hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream,
+                                       const int* items, int nitems) {
     const size_t lds = (size_t)n * sizeof(double2) + (size_t)n * sizeof(int);
     if (lds > 150 * 1024) return hipErrorNotSupported;
     if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
         const hipError_t ea = hipFuncSetAttribute((const void*)k_lu_unblocked_inplace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (ea != hipSuccess) return ea;
     }
-    hipLaunchKernelGGL(k_lu_unblocked_inplace, dim3(nbatch), dim3(NT), lds, stream, n, (double2*)A, maps, info);
+    hipLaunchKernelGGL(k_lu_unblocked_inplace, dim3(items ? nitems : nbatch), dim3(NT), lds, stream, n, (double2*)A, maps,
+                       info, items);
     return hipGetLastError();
 }
 

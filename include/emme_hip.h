@@ -390,6 +390,41 @@ int emme_null_vector(const double* M, int n, double* vec /* 2n doubles */);
  * factorisation is exactly zero (no vector: NaN), EMME_ENUMERIC = non-finite result.  n <= 2048. */
 int emme_null_vectors_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, double* vecs, int* info);
 
+/* ---- Newton on the eigenpair (additions within version 4: find them by symbol lookup) ------------
+ * Nonlinear inverse iteration on (omega, v), |v| = 1:
+ *     u = M(omega_k)^-1 M'(omega_k) v_k,   omega_k+1 = omega_k - 1 / (v_k^H u),   v_k+1 = u / |u|
+ * with the exact M' of emme_assemble_derivative_batch.  A step is one LU WITHOUT right-hand sides, one matrix-vector
+ * product and one pair of triangular solves (the trace form factors with n right-hand sides), the convergence to a
+ * simple eigenpair is quadratic, and the eigenvector and the residual |M(omega) v| / |M(omega)|_F come with the root.
+ *
+ * emme_solve_eigenpairs: omega_0 = g as emme_solve_roots_newton; stopping rule, iters, info codes and NaN-padded
+ * iterates as there; fills routed as there (deriv_cached, tile_uncached, the shape switches, parameter sets).  The
+ * context's iteration_method is NOT consulted: trace-secant and QR-secant contexts give the same result.
+ *   set       NULL: the context's own parameters; else host, n ints, checked as in emme_solve_roots_sets
+ *   v0        NULL: chain b starts from v_0 = M(g_b)^-1 s / |M(g_b)^-1 s| with
+ *                 s[i] = (1 + 0.37 sin(1 + i)) + 0.21 cos(2 i) i,   i = 0 .. dim-1
+ *             (the start vector of emme_null_vectors_batch); else host, n*dim complex, each row normalised on entry
+ *             (a zero or non-finite row: EMME_EINVAL)
+ *   vecs      host, n*dim complex: unit 2-norm, arbitrary phase; NaN for a failed chain (info != 0)
+ *   resid     host, n: |M(omega) v| / |M(omega)|_F at the returned omega with the returned vector; NaN where there is
+ *             none.  A chain that used every step keeps info = 0, as in the other searches: info = 0 says "no failure",
+ *             and resid is what tells a root (rounding level, 1e-16 .. 1e-15) from a chain that merely stopped.
+ * All pointer and range checks (NULL ctx / guesses / roots / vecs / resid / iters / info, n < 1, step_limit < 0,
+ * tol <= 0: EMME_EINVAL) come before the device is looked for.  EMME_ECONFIG for dim > 2048.  emme_ctx_get_matrix and
+ * emme_null_vectors_batch(M = NULL) work afterwards. */
+int emme_solve_eigenpairs(emme_ctx_t* ctx, const int* set /* NULL: the context's own set */, const double* guesses,
+                          int n, const double* v0 /* NULL, or n*dim complex */, double tol, int step_limit,
+                          double* roots, double* vecs /* n*dim complex */, double* resid /* n */, int* iters, int* info,
+                          double* iterates /* nullable */);
+/* One such step on caller matrices (eigpair.hip): M, Mp nbatch*n*n complex, row-major, both host or both device, not
+ * modified.  v (host, nbatch*n complex): in, the current vectors, taken as they are (unit 2-norm expected) -- with
+ * have_v = 0 not read: the step starts from M^-1 s / |M^-1 s|, s as above; out, u / |u|.  tau[b] = v^H u (host, complex:
+ * domega = -1 / tau), resid[b] = |M v| / |M|_F BEFORE the step (host).  info (host): 0, k > 0 = column k of the
+ * factorisation is exactly zero (vector, tau and resid NaN), EMME_ENUMERIC = non-finite tau or u.  Two calls give the
+ * same bits.  n <= 2048 (EMME_ECONFIG above); argument checks come before the device is looked for. */
+int emme_eigenpair_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* Mp,
+                              double* v /* in/out, host */, int have_v, double* tau, double* resid, int* info);
+
 /* ---- region search: every root inside a contour (version 4) ---------------------------------------
  * The reference only polishes guesses (src/main.cpp:19-80).  These entry points answer "which modes lie in this part of
  * the omega plane": Beyn's contour-integral method (W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, algorithm 1)
