@@ -174,6 +174,9 @@ def load():
     lib.emme_ctx_get_tile_shapes.argtypes = [P]
     lib.emme_ctx_set_deriv_cache_shapes.argtypes = [P, C.c_int]
     lib.emme_ctx_get_deriv_cache_shapes.argtypes = [P]
+    if hasattr(lib, "emme_ctx_set_mirror_pairs"):  # (an older library loaded through EMME_LIB for an A/B has neither)
+        lib.emme_ctx_set_mirror_pairs.argtypes = [P, C.c_int]
+        lib.emme_ctx_get_mirror_pairs.argtypes = [P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
     lib.emme_ctx_last_deferred.argtypes = [P]
@@ -576,6 +579,18 @@ class Context:
 
     def tile_shapes(self) -> int:
         v = self.lib.emme_ctx_get_tile_shapes(self.h)
+        if v < 0:
+            _check(v)
+        return v
+
+    def set_mirror_pairs(self, on: bool) -> None:
+        """Fill one pair of every mirror-image couple (i, j) / (N-1-j, N-1-i) on symmetric grids (DESIGN.md §5.0c;
+        default on, electrostatic GK15 on the tiled cache only).  A layout setting: rejected once the node cache exists."""
+        _check(self.lib.emme_ctx_set_mirror_pairs(self.h, 1 if on else 0))
+
+    def mirror_pairs(self) -> int:
+        """1 if the node cache is (or, before it exists, would be) laid out over the half pair list."""
+        v = self.lib.emme_ctx_get_mirror_pairs(self.h)
         if v < 0:
             _check(v)
         return v

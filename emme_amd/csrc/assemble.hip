@@ -54,6 +54,8 @@ struct AsmArgs {
     unsigned int count_lo, count_hi;  // k_assemble_coop: run only if count_lo <= list length < count_hi
     int skip_lost;  // LIST mode: integrals of a matrix whose status flag is already set are skipped
     const unsigned char* tile_poison[2];  // tiled cache: tiles that hold a poisoned (pair, interval) block, per class
+    int mirror;  // LIST mode, electrostatic: `pairs` holds one pair of every mirror-image couple -- an
+                 // integral is scattered to (N-1-j, N-1-i) too and its intervals count twice
 };
 
 // Value of the integrand at one quadrature node when a node-record cache may hold the
@@ -299,6 +301,13 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
                         const cd v = (-(w * P.dx)) * kap;
                         store(i, j, v);
                         store(j, i, v);
+                        if (LIST && A.mirror && i + j != N - 1) {  // the mirror-image pair: as k_assemble_dense
+                            const int i2 = N - 1 - j, j2 = N - 1 - i;
+                            const cd v2 = (-(pair_weight(i2, j2, N) * P.dx)) * kap;
+                            store(i2, j2, v2);
+                            store(j2, i2, v2);
+                            item_intervals *= 2;
+                        }
                     } else if (m == 1) {
                         // B block and its mirrors (include/solver.h:480-504)
                         const cd v = P.dx * kap;
@@ -521,6 +530,13 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
                 const cd v = (-(w * P.dx)) * kap;
                 store(i, j, v);
                 store(j, i, v);
+                if (A.mirror && i + j != N - 1) {  // the mirror-image pair: as k_assemble_dense
+                    const int i2 = N - 1 - j, j2 = N - 1 - i;
+                    const cd v2 = (-(pair_weight(i2, j2, N) * P.dx)) * kap;
+                    store(i2, j2, v2);
+                    store(j2, i2, v2);
+                    n_intervals *= 2;
+                }
             } else if (m == 1) {  // include/solver.h:480-504
                 const cd v = P.dx * kap;
                 store(i, j + N, v);
@@ -559,6 +575,7 @@ hipError_t launch_assemble(const AssembleLaunch& L, hipStream_t stream) {
     A.intervals = L.intervals;
     A.status = L.status;
     A.skip_lost = L.skip_lost;
+    A.mirror = 0;
     A.worklist = nullptr;
     A.worklist_count = nullptr;
     A.folded = 0;
@@ -609,6 +626,8 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
     A.intervals = L.intervals;
     A.status = L.status;
     A.skip_lost = L.skip_lost;
+    if (L.mirror && L.P.nm != 1) return hipErrorInvalidValue;  // (only electrostatic integrals have mirror entries)
+    A.mirror = L.mirror;
     A.worklist = worklist;
     A.worklist_count = count;
     A.folded = folded ? 1 : 0;

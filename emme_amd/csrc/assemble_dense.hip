@@ -226,6 +226,7 @@ struct DenseArgs {
     int nch_launch;             // chunks this launch serves (chunk0 .. chunk0 + nch_launch - 1)
     int tile_major;             // task order: the chunks of a tile group back to back on one XCD (else chunk-major)
     unsigned int* overflow;     // [nbatch] integrals handed over because a level list was full (null: not counted)
+    int mirror;                 // electrostatic GK15: `pairs` holds one pair of every mirror-image couple
 };
 
 // ---- the fill: level by level ----------------------------------------------------------------------
@@ -930,6 +931,15 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 const cd v = (-(pair_weight(i, j, N) * P.dx)) * kap;
                 store(i, j, v, rdw);
                 store(j, i, v, rdw);
+                if (PTS == 15 && A.mirror && i + j != N - 1) {
+                    // the mirror-image pair (N-1-j, N-1-i) of a symmetric grid has this integral: the same kappa
+                    // under its own weight, and the intervals the reference would have spent on it
+                    const int i2 = N - 1 - j, j2 = N - 1 - i;
+                    const cd v2 = (-(pair_weight(i2, j2, N) * P.dx)) * kap;
+                    store(i2, j2, v2, rdw);
+                    store(j2, i2, v2, rdw);
+                    my_intervals += (unsigned long long)s_count[wave][r][lane];
+                }
             } else {
                 // blocks A (m = 0), B and its mirrors (m = 1), D (m = 2): include/solver.h:472-509
                 const double de = A.tab[i] - A.tab[j], dg = A.tab[N + i] - A.tab[N + j];
@@ -1099,6 +1109,8 @@ hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& c
     const int ntiles = (L.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
     const int ntg = (ntiles + 3) / 4;
     const int nm = L.P.dim == L.P.N ? 1 : 3;
+    if (L.mirror && (nm != 1 || L.gk_points != 15)) return hipErrorInvalidValue;  // (only electrostatic GK15 writes mirrors)
+    A.mirror = L.mirror;
     if (nm == 3) {  // electromagnetic (64-entry level lists only; tile-major, XCD-aware order)
         const dim3 grid((unsigned)((long)((ntg + 7) / 8) * 8 * A.nchunks));
         if (L.gk_points == 31)

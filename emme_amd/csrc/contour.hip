@@ -490,6 +490,7 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
         EMME_TRY(reset_fill_counters(c, cnt));
         FillRequest rq(cnt, c->d_omega, S.A);
         rq.host_omega = plan.r_omega.data();
+        rq.may_mirror = false;  // (a context whose first cached call is a region search keeps the full pair list)
         if (set) {
             EMME_TRY(upload_set_indices(c, plan.r_set.data(), cnt));
             rq.d_set = c->d_set, rq.host_set = plan.r_set.data();

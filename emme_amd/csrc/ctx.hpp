@@ -23,6 +23,7 @@
 #include "buffers.hpp"
 #include "launch.hpp"
 #include "options.hpp"
+#include "pair_list.hpp"
 #include "step_feedback.hpp"
 
 namespace emme {
@@ -77,6 +78,14 @@ struct emme_ctx {
     int N = 0, dim = 0, nm = 1, npairs = 0;
     DeviceBuffer<double> d_tab;
     DeviceBuffer<ushort2> d_pairs;
+    // Mirror-image pairs: on a grid symmetric under i -> N-1-i the integral of pair (i, j) is that of
+    // (N-1-j, N-1-i), so the tiled cache and the dense fill behind it take one pair of each couple (d_pairs_half, same
+    // order as d_pairs) and the result section writes both.  Every other kernel family keeps d_pairs.
+    int npairs_half = 0;
+    DeviceBuffer<ushort2> d_pairs_half;
+    bool mirror_ok = false;    // electrostatic GK15 on a symmetric grid: decided at creation (mirror_wanted)
+    int mirror_opt = 1;        // emme_ctx_set_mirror_pairs (EMME_MIRROR read at creation); fixed once a cache exists
+    bool mirror = false;       // the tiled cache is laid out over d_pairs_half: fixed when it is first allocated
     // parameter sets bound to the context (emme_ctx_bind_param_sets): each has the shape of `p`
     std::vector<emme_params_t> sets;   // host copy
     DeviceBuffer<DevParams> d_sets;    // the kernels' scalars, one per set
@@ -177,8 +186,17 @@ namespace emme {
 
 // ---- ctx_cache.hip: buffer pool (pool_alloc / pool_free / malloc_retry: buffers.hpp) and node cache ------------
 void pool_release_all();
+// what a tiled cache allocated now would be laid out over: the half list on a symmetric electrostatic GK15 grid, unless
+// switched off or the context serves cached derivative fills (their kernels read the full list)
+inline bool mirror_wanted(const emme_ctx* c) {
+    return c->mirror_ok && c->mirror_opt != 0 && c->tiled && c->opt.deriv_cached == 0;
+}
+// pairs the tiled cache is laid out over, and with it its builder, the dense fill and the deferred pass
+inline int cache_npairs(const emme_ctx* c) { return c->mirror ? c->npairs_half : c->npairs; }
 long cache_items(const emme_ctx* c);
 size_t cache_part_bytes(const emme_ctx* c, int gk_points, const NodeCacheGeom& g, int part);
+// a cached derivative request has reached a mirrored cache: the context gives mirroring up for good
+int drop_mirror(emme_ctx* c);
 bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls);
 void add_cache_subtree(emme_ctx* c, const AssembleLaunch& L, int depth, unsigned long long path, int cls);
 
@@ -202,6 +220,9 @@ struct FillRequest {
     bool force_uncached = false;         // omega-lane kernel whatever the batch size and the cache
     const int* d_set = nullptr;          // set: item b belongs to the bound parameter set d_set[b]: the
     const int* host_set = nullptr;       // fills over sets (launch_sets); and its host image
+    bool may_mirror = true;              // false: a node cache this request is the first to allocate is laid out over the
+                                         // full pair list (the region searches: their nodes' matrices, and with them the
+                                         // roots they return, are pinned bit for bit to that list -- DESIGN.md 5.0c)
     FillRequest(int n, const double* omega, double* M) : nbatch(n), d_omega(omega), d_M(M) {}
 };
 int fill(emme_ctx* c, const FillRequest& r);

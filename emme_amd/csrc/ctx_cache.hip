@@ -76,16 +76,16 @@ void pool_free(void* p, size_t bytes, int device) {
 
 // items the node cache is indexed by: (pair, moment), or pairs alone in the shared EM layout
 long cache_items(const emme_ctx* c) { return (long)c->npairs * (c->em_shared ? 1 : c->nm); }
-// bytes of one part of the node cache in this context's record layout
+// bytes of one part of the node cache in this context's record layout (a mirrored tiled cache: over the half list)
 size_t cache_part_bytes(const emme_ctx* c, int gk_points, const NodeCacheGeom& g, int part) {
-    return c->tiled ? node_cache_bytes_tiled(c->npairs, g, part, gk_points) : node_cache_bytes(gk_points, cache_items(c), g, part);
+    return c->tiled ? node_cache_bytes_tiled(cache_npairs(c), g, part, gk_points) : node_cache_bytes(gk_points, cache_items(c), g, part);
 }
 hipError_t build_cache_part(emme_ctx* c, const AssembleLaunch& L, const NodeCacheGeom& g, int part, int cls, void* recs) {
     const double omi = cls == 0 ? 1.0 : -1.0;
     NodeCacheClass& cc = c->cache[cls];
     if (c->tiled) {
         if (!cc.tile_poison) {
-            const size_t ntiles = ((size_t)c->npairs + 15) / 16;
+            const size_t ntiles = ((size_t)cache_npairs(c) + 15) / 16;
             if (cc.tile_poison.grow(ntiles) != hipSuccess) return hipErrorOutOfMemory;
             const hipError_t e = hipMemsetAsync(cc.tile_poison, 0, ntiles, c->stream);
             if (e != hipSuccess) return e;
@@ -93,7 +93,7 @@ hipError_t build_cache_part(emme_ctx* c, const AssembleLaunch& L, const NodeCach
         hipError_t e = launch_node_cache_tiled(L, g, part, omi, recs, cc.ttab, c->d_scale, c->stream, cc.tile_poison,
                                                c->nm > 1 ? cc.wtab : nullptr);
         if (e == hipSuccess && std::getenv("EMME_DEBUG")) {
-            const size_t ntiles = ((size_t)c->npairs + 15) / 16;
+            const size_t ntiles = ((size_t)cache_npairs(c) + 15) / 16;
             std::vector<unsigned char> flags(ntiles);
             (void)hipMemcpyAsync(flags.data(), cc.tile_poison, ntiles, hipMemcpyDeviceToHost, c->stream);
             (void)hipStreamSynchronize(c->stream);
@@ -128,7 +128,10 @@ bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls) {
             if (o[0] < min_depth) break;
             NodeCacheGeom g{};
             g.dfull = o[0], g.nsub = 1, g.rd[0] = o[1], g.dd[0] = o[2], g.rp[0] = (1ull << o[1]) - 1ull;
-            if ((double)cache_part_bytes(c, L.gk_points, g, -1) <= 0.25 * budget) {
+            // (the geometry is chosen for the full pair list, mirrored or not: a mirrored cache is half the size, not deeper)
+            const size_t full_bytes = c->tiled ? node_cache_bytes_tiled(c->npairs, g, -1, L.gk_points)
+                                               : cache_part_bytes(c, L.gk_points, g, -1);
+            if ((double)full_bytes <= 0.25 * budget) {
                 c->cache_geom = g;
                 found = true;
                 break;
@@ -163,6 +166,26 @@ bool ensure_node_cache(emme_ctx* c, const AssembleLaunch& L, int cls) {
         return false;
     }
     return true;
+}
+
+// A derivative request that reads the node cache (option deriv_cached) has reached a context whose cache is laid out
+// over the half pair list, which no derivative kernel reads: the cache goes back to the pool and is built again, on
+// demand, over the full list -- and stays there (mirror_opt = 0).  The deferral feedback of the last fill goes with it.
+int drop_mirror(emme_ctx* c) {
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    for (auto& k : c->cache) {
+        k.recs.reset();
+        for (auto& e : k.recs_ext) e.reset();
+        k.tile_poison.reset();
+    }
+    c->cache_bytes_used = 0.0;
+    c->cache_depth = -1;
+    c->cache_geom = NodeCacheGeom{};
+    c->ext_failed = false;
+    c->fb.pub_valid = false, c->fb.last_deferred = 0;
+    if (c->d_worklist_count) HIP_TRY(hipMemsetAsync(c->d_worklist_count, 0, sizeof(unsigned int), c->stream));
+    c->mirror = false, c->mirror_opt = 0;
+    return EMME_OK;
 }
 
 // Which registered subtree covers interval (depth, path)?  -1 if none.

@@ -8,10 +8,11 @@ namespace emme {
 
 namespace {
 
-FillShape shape_of(const emme_ctx* c) {
+// (mirrored: the request runs on the half pair list -- runs_mirrored)
+FillShape shape_of(const emme_ctx* c, bool mirrored = false) {
     FillShape s;
     s.tiled = c->tiled, s.folded = c->folded;
-    s.nm = c->nm, s.gk_points = c->p.integration_start_points, s.npairs = c->npairs;
+    s.nm = c->nm, s.gk_points = c->p.integration_start_points, s.npairs = mirrored ? c->npairs_half : c->npairs;
     s.fill_lanes = c->opt.fill == EMME_FILL_LANES;
     s.dense_min_tasks = c->opt.dense_min_tasks, s.dense_cost_ratio = c->opt.dense_cost_ratio;
     s.union_ipg_few = c->opt.union_ipg_few, s.union_few_chunks = c->opt.union_few_chunks;
@@ -29,16 +30,24 @@ bool deriv_from_cache(const emme_ctx* c, const FillRequest& r) {
            (deriv_shape_is_es15(c) || c->deriv_cache_shapes == EMME_DERIV_CACHE_SHAPES_ALL) && r.host_omega != nullptr;
 }
 
+// A request runs mirrored -- on one pair of every mirror-image couple -- when the context's tiled cache
+// is laid out that way and the request goes to it: the plain dense fill and its deferred pass.  Every other kernel
+// family (tile fills, omega-lane, lanes-are-nodes, sets, every derivative kernel) keeps the full list.
+bool runs_mirrored(const emme_ctx* c, const FillRequest& r, bool use_cache) {
+    return c->mirror && c->tiled && use_cache && !r.d_Md && !r.d_set;
+}
+
 // what the fill kernels are told: the context's tables and counters, the request's operands and, for the plain
 // fills, the context's options (a derivative fill runs its two kernels on the struct defaults)
-AssembleLaunch make_launch(const emme_ctx* c, const FillRequest& r) {
+AssembleLaunch make_launch(const emme_ctx* c, const FillRequest& r, bool mirrored) {
     AssembleLaunch L;
     L.P = c->P;
     L.gk_points = c->p.integration_start_points;
     L.nbatch = r.nbatch;
-    L.npairs = c->npairs;
+    L.npairs = mirrored ? c->npairs_half : c->npairs;
     L.tab = c->d_tab;
-    L.pairs = c->d_pairs;
+    L.pairs = mirrored ? c->d_pairs_half : c->d_pairs;
+    L.mirror = mirrored ? 1 : 0;
     L.omega = r.d_omega;
     L.active = r.d_active;
     L.M = r.d_M;
@@ -161,7 +170,7 @@ struct DenseStamps {
                 "sum / 2048 wave slots %.0f; rounds dense %llu sparse %llu\n", n_lane, nchunks, tasks, ms,
                 tasks > 0 ? tot / tasks : 0.0, (double)r1[9], tot / 2048.0, r1[0] - r0[0], r1[1] - r0[1]);
         // how the tiles' times are spread (all chunks of the launch added up per tile)
-        const size_t nt = std::min<size_t>(((size_t)c->npairs + 15) / 16, 8192);
+        const size_t nt = std::min<size_t>(((size_t)cache_npairs(c) + 15) / 16, 8192);
         std::vector<unsigned long long> tt(nt);
         HIP_TRY(hipMemcpy(tt.data(), c->d_rounds + 16, nt * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         HIP_TRY(hipMemset(c->d_rounds + 16, 0, nt * sizeof(unsigned long long)));
@@ -181,7 +190,7 @@ void print_deferred(emme_ctx* c, int n_act) {
     std::vector<unsigned long long> wl(cnt < 8 ? cnt : 8);
     if (!wl.empty()) (void)hipMemcpy(wl.data(), c->d_worklist, wl.size() * 8, hipMemcpyDeviceToHost);
     fprintf(stderr, "[emme] cached fill: %d items, %u integrals deferred (of %ld)", n_act, cnt,
-            (long)c->npairs * c->nm * n_act);
+            (long)cache_npairs(c) * c->nm * n_act);
     std::vector<unsigned long long> dg(wl.size());
     if (!wl.empty() && c->d_defer_info) (void)hipMemcpy(dg.data(), c->d_defer_info, wl.size() * 8, hipMemcpyDeviceToHost);
     for (size_t q = 0; q < wl.size(); ++q)
@@ -293,7 +302,7 @@ int fill_cached(emme_ctx* c, AssembleLaunch& L, const FillRequest& r, int n_wide
     HIP_TRY(c->d_worklist.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_defer_info.grow(need * sizeof(unsigned long long)));
     HIP_TRY(c->d_worklist_count.grow(sizeof(unsigned int)));
-    FillShape shape = shape_of(c);
+    FillShape shape = shape_of(c, L.mirror != 0);
     shape.deriv = r.d_Md != nullptr;
     const ChunkPlan plan = plan_chunks(shape, c->h_actidx, r.cost, n_wide, c->h_chunks);
     L.items_per_group = plan.items_per_group;
@@ -528,19 +537,25 @@ int fill(emme_ctx* c, const FillRequest& r) {
     const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->fb.wide.data() : nullptr, c->h_actidx);
     const int n_act = (int)c->h_actidx.size();
     if (n_act == 0) return EMME_OK;
-    AssembleLaunch L = make_launch(c, r);
     if (r.d_set) {
+        AssembleLaunch L = make_launch(c, r, false);
         EMME_TRY(launch_sets(c, L, r));
         c->acc.matrices += n_act;
         return EMME_OK;
     }
+    // no derivative kernel reads a half pair list: a cached derivative request ends a context's mirroring
+    if (c->mirror && deriv_from_cache(c, r)) EMME_TRY(drop_mirror(c));
     bool use_cache = wants_cache(c, r);
+    // the pair list is part of the tiled cache's layout: fixed when the first part of the cache is allocated
+    if (use_cache && !c->cache[0].recs && !c->cache[1].recs) c->mirror = mirror_wanted(c) && r.may_mirror;
+    AssembleLaunch L = make_launch(c, r, runs_mirrored(c, r, use_cache));
     if (use_cache) {
         const bool has_cache[2] = {(bool)c->cache[0].recs, (bool)c->cache[1].recs};
         const ClassCensus classes = plan_classes(c->h_actidx, r.host_omega, has_cache);
         if (classes.minority >= 0) return fill_by_class(c, r, classes.minority);
         for (int k = 0; k < 2 && use_cache; ++k)
             if (classes.count[k] > 0) use_cache = ensure_node_cache(c, L, k);
+        if (!use_cache && L.mirror) L = make_launch(c, r, false);  // (the cache did not fit: the uncached kernels' list)
     }
     EMME_TRY(use_cache ? grow_cache_from_deferrals(c, L) : EMME_OK);
     EMME_TRY(use_cache ? fill_cached(c, L, r, n_wide) : fill_uncached(c, L, r));

@@ -149,7 +149,8 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     auto take_pending = [&]() {  // results of the previous step's fill + retire
         std::copy(c->p_act.get(), c->p_act.get() + n, act.begin());
         // (an item an eighth of whose integrals did not fit the 64-entry level lists: 128 entries from now on)
-        fb.take(c->p_iv, c->p_overflow, c->npairs, c->p_deferred);
+        // (the dense fill is the only one that counts overflows: of the integrals it ran, half of them when mirrored)
+        fb.take(c->p_iv, c->p_overflow, cache_npairs(c), c->p_deferred);
         pending = false;
         if (std::getenv("EMME_DEBUG")) {
             unsigned long long tot = 0, mx = 0;

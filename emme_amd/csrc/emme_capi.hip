@@ -294,24 +294,33 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     std::vector<double> tab;
     dev_params_from(p, P, tab);
 
-    // pair list ordered by diagonal offset (see assemble.hip header)
-    std::vector<ushort2> pairs;
-    pairs.reserve((size_t)N * (N - 1) / 2);
-    for (int off = 1; off < N; ++off)
-        for (int i = 0; i + off < N; ++i) pairs.push_back(make_ushort2((unsigned short)i, (unsigned short)(i + off)));
+    // pair list ordered by diagonal offset (see assemble.hip header), and one pair of every mirror-image couple
+    std::vector<PairIJ> pairs, half;
+    full_pair_list(N, pairs);
+    half_pair_list(N, half);
     c->npairs = (int)pairs.size();
+    c->npairs_half = (int)half.size();
+    // Mirror-image pairs share their integral where the grid is symmetric (theta = 0): eta, g odd and b even to 1e-13
+    // of the table's largest value -- 30 times the rounding of the tables themselves (3e-15), nine orders below a real
+    // asymmetry (theta = 0.3: 3e-2).  Only the electrostatic GK15 dense fill writes mirrors (mirror_wanted: and only
+    // on the tiled layout, which emme_ctx_set_options may still change while no cache exists).
+    c->mirror_ok = c->nm == 1 && p->integration_start_points == 15 && grid_is_mirror_symmetric(tab.data(), N, 1e-13);
+    // (developer override, read once per context: EMME_MIRROR=0 is emme_ctx_set_mirror_pairs(0))
+    if (const char* v = std::getenv("EMME_MIRROR")) c->mirror_opt = std::atoi(v) != 0;
 
     auto fail = [&](int code) {
         emme_ctx_destroy(c);
         return code;
     };
     if (c->d_tab.grow(tab.size() * sizeof(double)) != hipSuccess ||
-        c->d_pairs.grow(pairs.size() * sizeof(ushort2)) != hipSuccess) {
+        c->d_pairs.grow(pairs.size() * sizeof(ushort2)) != hipSuccess ||
+        c->d_pairs_half.grow(half.size() * sizeof(ushort2)) != hipSuccess) {
         set_error("hipMalloc failed for tables");
         return fail(EMME_ENOMEM);
     }
     if (hipMemcpy(c->d_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(c->d_pairs, pairs.data(), pairs.size() * sizeof(ushort2), hipMemcpyHostToDevice) != hipSuccess) {
+        hipMemcpy(c->d_pairs, pairs.data(), pairs.size() * sizeof(ushort2), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(c->d_pairs_half, half.data(), half.size() * sizeof(ushort2), hipMemcpyHostToDevice) != hipSuccess) {
         set_error("hipMemcpy failed for tables");
         return fail(EMME_EDEVICE);
     }
@@ -371,6 +380,28 @@ int emme_ctx_set_tile_shapes(emme_ctx_t* c, int shapes) {
 }
 
 int emme_ctx_get_tile_shapes(const emme_ctx_t* c) { return c ? c->tile_shapes : EMME_EINVAL; }
+
+int emme_ctx_set_mirror_pairs(emme_ctx_t* c, int on) {
+    if (!c) {
+        set_error("emme_ctx_set_mirror_pairs: NULL context");
+        return EMME_EINVAL;
+    }
+    if (on != 0 && on != 1) {
+        set_error("emme_ctx_set_mirror_pairs: value out of range (0, 1)");
+        return EMME_EINVAL;
+    }
+    if (c->cache[0].recs || c->cache[1].recs) {
+        set_error("emme_ctx_set_mirror_pairs: the pair list fixes the layout of the node cache, which exists already");
+        return EMME_EINVAL;
+    }
+    c->mirror_opt = on;
+    return EMME_OK;
+}
+
+int emme_ctx_get_mirror_pairs(const emme_ctx_t* c) {
+    if (!c) return EMME_EINVAL;
+    return (c->cache[0].recs || c->cache[1].recs) ? (int)c->mirror : (int)mirror_wanted(c);
+}
 
 int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* c, int shapes) {
     if (!c) {

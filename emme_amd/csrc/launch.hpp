@@ -43,6 +43,8 @@ struct AssembleLaunch {
     int dense_min_cols = 3;    // dense fill: columns that must need an interval for the MFMA path
     int dense_stage = 1;       // dense fill (electrostatic GK15): operands through the LDS stage, fetched one entry ahead
     double* Md = nullptr;      // device or null: exact dM/domega beside M (Mold must be null)
+    int mirror = 0;            // pairs / npairs are one pair of every mirror-image couple (the tiled cache's dense fill and
+                               // its deferred pass, electrostatic GK15): entry (N-1-j, N-1-i) is written beside (i, j)
 };
 // What the launchers that read the node cache see of it: its geometry and, per contour class (omi = +1, -1), the
 // main records, the run-time subtrees (null if absent), the T table, the moment-factor table and the tile-poison

@@ -209,6 +209,18 @@ int emme_ctx_get_tile_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL f
 #define EMME_DERIV_CACHE_SHAPES_ALL  1 /* deriv_cached serves electromagnetic and GK31 contexts as well */
 int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range */
 int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
+/* Mirror-image pairs (additions within version 4, found by symbol lookup).  On a grid that is symmetric
+ * under i -> N-1-i (eta and g odd, b even to 1e-13 of the table's largest value: theta = 0) the integral of pair (i, j)
+ * is that of (N-1-j, N-1-i).  An electrostatic GK15 context on the tiled layout then lays its node cache out over one
+ * pair of every such couple -- half the cache, half the integrals of the dense fill and of its deferred pass -- and
+ * writes both entries, each under its own SingularityHandler weight; interval counts stay those of the full pair list.
+ * The two entries agree to the rounding noise of the reference's own mirror pairs.  On by default (EMME_MIRROR=0, read
+ * at creation, switches it off); a context created with deriv_cached = 1 never mirrors, and one whose mirrored cache a
+ * cached derivative request reaches rebuilds the cache over the full list and stays unmirrored.  A layout setting: the
+ * setter answers EMME_EINVAL once the node cache exists.  The getter says whether the cache is laid out over the half
+ * list, or before it exists whether it would be; 0 on every context that is not eligible. */
+int emme_ctx_set_mirror_pairs(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1, cache exists */
+int emme_ctx_get_mirror_pairs(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
 /* Launch everything on this hipStream_t (e.g. torch's current stream). NULL = default. */
 int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
