@@ -202,6 +202,14 @@ def load():
     lib.emme_solve_roots_sets.argtypes = [P, P, P, C.c_int, C.c_int, C.c_double, C.c_int, P, P, P, P]
     lib.emme_solve_eigenpairs.argtypes = [P, P, P, C.c_int, P, C.c_double, C.c_int, P, P, P, P, P, P]
     lib.emme_eigenpair_step_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, C.c_int, P, P, P]
+    if hasattr(lib, "emme_solve_eigenpairs_secant"):  # (an older library loaded through EMME_LIB for an A/B has none)
+        lib.emme_solve_eigenpairs_secant.argtypes = lib.emme_solve_eigenpairs.argtypes
+        lib.emme_eigenpair_secant_step_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P, C.c_int, P, P, P]
+        lib.emme_contour_eigpairs.argtypes = [C.c_int, C.c_int, P, P, C.c_double, C.c_int, P, P, P, P]
+        lib.emme_find_eigenpairs_in_contour.argtypes = [P, C.POINTER(Contour), C.c_int, C.c_double, C.c_int, C.c_int,
+                                                        P, P, P, P, P, P, P, P]
+        lib.emme_find_eigenpairs_in_contours_sets.argtypes = [P, C.c_int, P, P, C.c_int, C.c_double, C.c_int, C.c_int,
+                                                              P, P, P, P, P, P, P, P, P]
     lib.emme_run_json_lockstep.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
     lib.emme_scan_plan.argtypes = [C.c_char_p, C.c_int, P, P, P, P, C.c_int, P, P, P]
     lib.emme_null_vector.argtypes = [P, C.c_int, P]
@@ -845,11 +853,13 @@ class Context:
         return (roots, iters, info, its) if want_iterates else (roots, iters, info)
 
     # ---- Newton on the eigenpair ----
-    def solve_eigenpairs(self, guesses, set=None, v0=None, tol=None, step_limit=None, want_iterates=False):
+    def solve_eigenpairs(self, guesses, set=None, v0=None, tol=None, step_limit=None, want_iterates=False, secant=False):
         """Newton on (omega, v) from omega_0 = guesses (emme_solve_eigenpairs): one LU without right-hand sides per step,
         and the unit eigenvector and the residual |M v| / |M|_F come with the root.  set: chain b on the bound parameter
-        set set[b]; v0 [n, dim]: start vectors (default: from M(omega_0)^-1 s).  Returns (roots, vecs, resid, iters,
-        info[, iterates]); info = 0 also for a chain that used every step -- resid tells."""
+        set set[b]; v0 [n, dim]: start vectors (default: from M(omega_0)^-1 s).  secant=True: the secant reading
+        (emme_solve_eigenpairs_secant) -- bootstrapped at 0.99 g and g as solve_roots, one plain fill per step, no
+        derivative fill.  Returns (roots, vecs, resid, iters, info[, iterates]); info = 0 also for a chain that used
+        every step -- resid tells."""
         g = _c128(np.atleast_1d(guesses))
         n = g.shape[0]
         st = None
@@ -869,11 +879,41 @@ class Context:
         iters = np.zeros(n, dtype=np.int32)
         info = np.zeros(n, dtype=np.int32)
         its = np.zeros((n, step_limit + 1), dtype=np.complex128) if want_iterates else None
-        _check(self.lib.emme_solve_eigenpairs(self.h, st.ctypes.data if st is not None else None, g.ctypes.data, n,
-                                              v0.ctypes.data if v0 is not None else None, tol, step_limit,
-                                              roots.ctypes.data, vecs.ctypes.data, resid.ctypes.data, iters.ctypes.data,
-                                              info.ctypes.data, its.ctypes.data if want_iterates else None))
+        search = self.lib.emme_solve_eigenpairs_secant if secant else self.lib.emme_solve_eigenpairs
+        _check(search(self.h, st.ctypes.data if st is not None else None, g.ctypes.data, n,
+                      v0.ctypes.data if v0 is not None else None, tol, step_limit, roots.ctypes.data, vecs.ctypes.data,
+                      resid.ctypes.data, iters.ctypes.data, info.ctypes.data, its.ctypes.data if want_iterates else None))
         return (roots, vecs, resid, iters, info, its) if want_iterates else (roots, vecs, resid, iters, info)
+
+    def eigenpair_secant_step(self, M, M_old, domega, v=None):
+        """One secant eigenpair step on caller matrices (emme_eigenpair_secant_step_batch): u = M^-1 (M - M_old) v /
+        domega with the difference taken per entry, tau = v^H u (the next domega = -1/tau), resid = |M v| / |M|_F before
+        the step.  domega [nbatch]: the step between the two fills.  v None: as eigenpair_step.  Returns (u / |u|, tau,
+        resid, info)."""
+        M = _c128(M)
+        M_old = _c128(M_old)
+        if M.ndim == 2:
+            M, M_old = M[None], M_old[None]
+        M, M_old = np.ascontiguousarray(M), np.ascontiguousarray(M_old)
+        nb, n = M.shape[0], M.shape[1]
+        if M.shape != (nb, n, n) or M_old.shape != M.shape:
+            raise ValueError("M and M_old must be [nbatch, n, n]")
+        dw = np.ascontiguousarray(_c128(np.atleast_1d(domega)))
+        if dw.shape != (nb,):
+            raise ValueError("domega needs one entry per matrix")
+        if v is None:
+            vv = np.zeros((nb, n), dtype=np.complex128)
+        else:
+            vv = np.array(_c128(v), dtype=np.complex128, order="C", copy=True).reshape(-1, n)
+            if vv.shape != (nb, n):
+                raise ValueError("v must be [nbatch, n]")
+        tau = np.zeros(nb, dtype=np.complex128)
+        resid = np.zeros(nb, dtype=np.float64)
+        info = np.zeros(nb, dtype=np.int32)
+        _check(self.lib.emme_eigenpair_secant_step_batch(self.h, n, nb, M.ctypes.data, M_old.ctypes.data, dw.ctypes.data,
+                                                         vv.ctypes.data, 0 if v is None else 1, tau.ctypes.data,
+                                                         resid.ctypes.data, info.ctypes.data))
+        return vv, tau, resid, info
 
     def eigenpair_step(self, M, Mp, v=None):
         """One eigenpair step on caller matrices (emme_eigenpair_step_batch): u = M^-1 Mp v, tau = v^H u (domega = -1/tau),
@@ -1022,6 +1062,84 @@ class Context:
             m = min(int(nr[k]), max_roots)
             out.append({"roots": roots[k, :m].copy(), "iters": iters[k, :m].copy(), "info": info[k, :m].copy(),
                         "n_roots": int(nr[k]), "winding": int(w[k]), "points_used": int(pu[k]),
+                        "complete": bool(w[k] >= 0 and nr[k] == w[k]), "status": int(status[k])})
+        return out
+
+    # ---- region searches that return eigenpairs ----
+    def contour_eigpairs(self, A0, A1, rank_tol=1e-5, max_eigs=64, want_vecs=True):
+        """The Beyn step on given moments with its eigenvectors (emme_contour_eigpairs, host only): returns (mu, vecs, k,
+        sigma), vecs [min(k, max_eigs), n] with row c = U_k y_c, unit 2-norm (None with want_vecs=False)."""
+        A0 = np.ascontiguousarray(_c128(A0))
+        A1 = np.ascontiguousarray(_c128(A1))
+        n, L = A0.shape
+        if A1.shape != (n, L):
+            raise ValueError("A0 and A1 must both be n x L")
+        mu = np.zeros(max_eigs, dtype=np.complex128)
+        vecs = np.zeros((max_eigs, n), dtype=np.complex128) if want_vecs else None
+        sigma = np.zeros(L, dtype=np.float64)
+        k = C.c_int(0)
+        _check(self.lib.emme_contour_eigpairs(n, L, A0.ctypes.data, A1.ctypes.data, rank_tol, max_eigs, mu.ctypes.data,
+                                              vecs.ctypes.data if want_vecs else None, C.byref(k), sigma.ctypes.data))
+        m = min(k.value, max_eigs)
+        return mu[:m].copy(), (vecs[:m].copy() if want_vecs else None), k.value, sigma
+
+    def find_eigenpairs_in_contour(self, center, semi_axes, exact=False, tol=None, step_limit=None, max_roots=64,
+                                   **contour):
+        """find_roots_in_contour returning every root with its eigenvector (emme_find_eigenpairs_in_contour): the
+        candidates carry their Beyn vectors into an eigenpair search -- exact=False: the secant one (plain fills only),
+        exact=True: Newton on the exact derivative.  Returns find_roots_in_contour's dict plus vecs [n_roots, dim] (unit
+        2-norm) and resid (|M v| / |M|_F per root)."""
+        c = contour_default(center=complex(center), semi_axes=tuple(semi_axes), **contour)
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        roots = np.zeros(max_roots, dtype=np.complex128)
+        vecs = np.zeros((max_roots, self.dim), dtype=np.complex128)
+        resid = np.zeros(max_roots, dtype=np.float64)
+        iters = np.zeros(max_roots, dtype=np.int32)
+        info = np.zeros(max_roots, dtype=np.int32)
+        nr, w, pu = C.c_int(0), C.c_int(0), C.c_int(0)
+        _check(self.lib.emme_find_eigenpairs_in_contour(self.h, C.byref(c), int(bool(exact)), tol, step_limit, max_roots,
+                                                        roots.ctypes.data, vecs.ctypes.data, resid.ctypes.data,
+                                                        iters.ctypes.data, info.ctypes.data, C.byref(nr), C.byref(w),
+                                                        C.byref(pu)))
+        k = min(nr.value, max_roots)
+        return {"roots": roots[:k].copy(), "vecs": vecs[:k].copy(), "resid": resid[:k].copy(), "iters": iters[:k].copy(),
+                "info": info[:k].copy(), "n_roots": nr.value, "winding": w.value, "points_used": pu.value,
+                "complete": w.value >= 0 and nr.value == w.value}
+
+    def find_eigenpairs_in_contours_sets(self, set, centers, semi_axes, exact=False, tol=None, step_limit=None,
+                                         max_roots=64, contours=None):
+        """find_roots_in_contours_sets returning eigenpairs (emme_find_eigenpairs_in_contours_sets): arguments as there,
+        polish as find_eigenpairs_in_contour.  Returns a list of dicts shaped like that call's, plus status."""
+        st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+        n = st.shape[0]
+        centers = np.atleast_1d(centers)
+        semi_axes = np.asarray(semi_axes, dtype=np.float64).reshape(-1, 2)
+        contours = [{}] * n if contours is None else list(contours)
+        if len(centers) != n or len(semi_axes) != n or len(contours) != n:
+            raise ValueError("centers, semi_axes and contours need one entry per item")
+        cts = (Contour * max(n, 1))(*[contour_default(center=complex(centers[k]), semi_axes=tuple(semi_axes[k]),
+                                                      **(contours[k] or {})) for k in range(n)])
+        tol = self.params.iteration_precision if tol is None else tol
+        step_limit = self.params.iteration_step_limit if step_limit is None else step_limit
+        m1 = max(n, 1)
+        roots = np.zeros((m1, max_roots), dtype=np.complex128)
+        vecs = np.zeros((m1, max_roots, self.dim), dtype=np.complex128)
+        resid = np.zeros((m1, max_roots), dtype=np.float64)
+        iters = np.zeros((m1, max_roots), dtype=np.int32)
+        info = np.zeros((m1, max_roots), dtype=np.int32)
+        nr, w, pu, status = (np.zeros(m1, dtype=np.int32) for _ in range(4))
+        _check(self.lib.emme_find_eigenpairs_in_contours_sets(self.h, n, st.ctypes.data, C.cast(cts, C.c_void_p),
+                                                              int(bool(exact)), tol, step_limit, max_roots, roots.ctypes.data,
+                                                              vecs.ctypes.data, resid.ctypes.data, iters.ctypes.data,
+                                                              info.ctypes.data, nr.ctypes.data, w.ctypes.data,
+                                                              pu.ctypes.data, status.ctypes.data))
+        out = []
+        for k in range(n):
+            m = min(int(nr[k]), max_roots)
+            out.append({"roots": roots[k, :m].copy(), "vecs": vecs[k, :m].copy(), "resid": resid[k, :m].copy(),
+                        "iters": iters[k, :m].copy(), "info": info[k, :m].copy(), "n_roots": int(nr[k]),
+                        "winding": int(w[k]), "points_used": int(pu[k]),
                         "complete": bool(w[k] >= 0 and nr[k] == w[k]), "status": int(status[k])})
         return out
 

@@ -2,7 +2,8 @@
 // of caller matrices (emme_contour_moments_batch, emme_contour_moments_groups) and the region search (every root inside
 // an ellipse: Beyn's method, W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, seeded into the Newton search) on
 // one contour (emme_find_roots_in_contour) or on many (parameter set, contour) items at once
-// (emme_find_roots_in_contours_sets).
+// (emme_find_roots_in_contours_sets); emme_find_eigenpairs_in_contour and emme_find_eigenpairs_in_contours_sets are the
+// same searches returning every root with its eigenvector and residual.
 //
 // The nodes' matrices are factored once by the nullSpace factorisation (lu_factor_batch: P M = L U in place, row
 // order in panel snapshots) and kept for the whole call.  Three small kernels read the factors:
@@ -443,9 +444,12 @@ int caller_moments(emme_ctx* c, const char* who, int n, int nq, const double* M,
 }
 
 // where a region search puts what it found: item k's roots at roots[k max_roots ..], one of everything else per item
+// vecs / resid (both or neither): the search returns eigenpairs -- item k's unit vectors at vecs[k max_roots dim ..],
+// their residuals at resid[k max_roots ..]
 struct SearchOutputs {
     double* roots;
     int *iters, *info, *n_roots, *winding, *points_used, *status;
+    double *vecs = nullptr, *resid = nullptr;
 };
 
 // The region search on nitems (set, contour) items in lock step: the round plan of host_contour.cpp
@@ -454,6 +458,12 @@ struct SearchOutputs {
 // on the context's own parameters: its fills carry no set (so they may go through the node cache), its polish is
 // emme_solve_roots with the context's method (`exact` is not read), and an error of the item is the call's error,
 // named without an item number.
+// With out.vecs (emme_find_eigenpairs_in_contour, emme_find_eigenpairs_in_contours_sets) only the last stage differs:
+// the Beyn step of the final L pass keeps the eigenvector v_c = U_k y_c beside every mu_c (emme_contour_eigpairs: mu, k
+// and sigma are emme_contour_eigs' bit for bit, so nodes, counts and L passes are the same), the candidates carry
+// them, and the polish is an eigenpair search started from them -- exact = 0: emme_solve_eigenpairs_secant (plain
+// fills only), exact = 1: emme_solve_eigenpairs -- with or without sets; every kept root comes back with its unit
+// vector and its residual.
 int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* set, const emme_contour_t* contours,
                     int exact, double tol, int step_limit, int max_roots, const SearchOutputs& out) {
     const int n = c->dim;
@@ -530,6 +540,11 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
     std::vector<int> which, off, idx, Ls;
     std::vector<double> wz, A0, A1, mu(2 * LCAP), sig(LCAP);
     std::vector<std::vector<double>> guesses(nitems);
+    const bool pairs = out.vecs != nullptr;
+    std::vector<double> beyn;                        // (pairs) the vectors of one Beyn step, min(k, LCAP) rows of n
+    std::vector<std::vector<double>> seeds(nitems);  // ... and those of an item's candidates, in the candidates' order
+    std::vector<int> kept;
+    if (pairs) beyn.resize(2 * (size_t)n * LCAP);
     GroupBuffers G;
     const size_t ostride = (size_t)n * LCAP;
     while (plan.plan_moments(h_info.data(), which, off, idx, wz)) {
@@ -543,8 +558,10 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
             const int item = which[g];
             const emme_contour_t& ct = plan.items[item].ct;
             int k = 0, l0 = 0, nl = 0;
-            const int rc = emme_contour_eigs(n, Ls[g], &A0[2 * ostride * g], &A1[2 * ostride * g], ct.rank_tol, LCAP, mu.data(),
-                                             &k, sig.data());
+            const int rc = pairs ? emme_contour_eigpairs(n, Ls[g], &A0[2 * ostride * g], &A1[2 * ostride * g], ct.rank_tol, LCAP,
+                                                         mu.data(), beyn.data(), &k, sig.data())
+                                 : emme_contour_eigs(n, Ls[g], &A0[2 * ostride * g], &A1[2 * ostride * g], ct.rank_tol, LCAP,
+                                                     mu.data(), &k, sig.data());
             if (rc) {
                 drop(item, rc, set ? label(item) + emme_last_error() : emme_last_error());
                 continue;
@@ -557,7 +574,10 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
             }
             if (!plan.take_rank(item, k, &l0, &nl)) {
                 // the candidates (normalised radius below 1.5: the others are no eigenvalues inside)
-                contour_candidates(ct, k, mu.data(), guesses[item]);
+                kept.clear();
+                contour_candidates(ct, k, mu.data(), guesses[item], &kept);
+                if (pairs)
+                    for (int q : kept) seeds[item].insert(seeds[item].end(), &beyn[2 * (size_t)q * n], &beyn[2 * (size_t)(q + 1) * n]);
                 continue;
             }
             for (int nd : plan.items[item].nodes) {
@@ -569,19 +589,34 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
         EMME_TRY(solve_listed(c, n, probes, LCAP, list, d_list));
     }
     // ---- one search polishes the candidates of all items: items in order, an item's in the order of mu
-    std::vector<double> g_all;
+    std::vector<double> g_all, v_all;
     std::vector<int> g_set, g_first(nitems + 1, 0);
     for (int k = 0; k < nitems; ++k) {
         if (!plan.items[k].dropped) {
             g_all.insert(g_all.end(), guesses[k].begin(), guesses[k].end());
             g_set.insert(g_set.end(), guesses[k].size() / 2, plan.items[k].set);
+            v_all.insert(v_all.end(), seeds[k].begin(), seeds[k].end());
         }
         g_first[k + 1] = (int)g_set.size();
     }
     const int ng = (int)g_set.size();
     std::vector<double> r(2 * (size_t)ng), path(2 * (size_t)ng * (step_limit + 1));
     std::vector<int> its(ng), inf(ng);
-    if (ng > 0)
+    std::vector<double> vec, res;  // (pairs) the polished chains' vectors and residuals
+    if (ng > 0 && pairs) {
+        vec.resize(2 * (size_t)ng * n), res.resize(ng);
+        const int* st = set ? g_set.data() : nullptr;
+        EMME_TRY(exact ? emme_solve_eigenpairs(c, st, g_all.data(), ng, v_all.data(), tol, step_limit, r.data(), vec.data(),
+                                               res.data(), its.data(), inf.data(), path.data())
+                       : emme_solve_eigenpairs_secant(c, st, g_all.data(), ng, v_all.data(), tol, step_limit, r.data(),
+                                                      vec.data(), res.data(), its.data(), inf.data(), path.data()));
+        // The one rule this form adds: a chain can stop on its step without M being singular ("chains
+        // that stop without a root"; from a spurious candidate's vector the secant polish does, with residuals of
+        // 5e-4 .. 7e-4 where roots have 1e-11 or less).  The root form cannot see that; here the residual tells, and
+        // what is no eigenpair to sqrt(eps) is dropped like a chain that failed.
+        for (int q = 0; q < ng; ++q)
+            if (inf[q] == 0 && !(res[q] <= 1e-8)) inf[q] = EMME_ENUMERIC;
+    } else if (ng > 0)
         EMME_TRY(set ? emme_solve_roots_sets(c, g_set.data(), g_all.data(), ng, exact, tol, step_limit, r.data(), its.data(),
                                              inf.data(), path.data())
                      : emme_solve_roots(c, g_all.data(), ng, tol, step_limit, r.data(), its.data(), inf.data(), path.data()));
@@ -598,6 +633,11 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
             const size_t at = (size_t)k * max_roots + q;
             out.roots[2 * at] = found[q].re, out.roots[2 * at + 1] = found[q].im, out.iters[at] = found[q].it,
                            out.info[at] = found[q].inf;
+            if (pairs) {
+                const size_t chain = (size_t)o + found[q].chain;
+                std::copy(&vec[2 * chain * n], &vec[2 * (chain + 1) * n], out.vecs + 2 * at * n);
+                out.resid[at] = res[chain];
+            }
         }
         out.n_roots[k] = (int)found.size(), out.winding[k] = it.W, out.points_used[k] = it.N, out.status[k] = it.status;
     }
@@ -609,6 +649,51 @@ int search_contours(emme_ctx* c, const std::string& who, int nitems, const int* 
 }  // namespace emme
 
 using namespace emme;
+
+namespace {
+
+// The argument rules of the region searches, all before the device is looked for; pairs: the eigenpair forms, which
+// need vecs and resid as well
+int region_search_sets(emme_ctx* c, const std::string& who, bool pairs, int nitems, const int* set,
+                       const emme_contour_t* contours, int exact, double tol, int step_limit, int max_roots,
+                       const SearchOutputs& out) {
+    if (nitems < 1 || nitems > 65535) {
+        set_error(who + ": nitems must lie in 1 .. 65535");
+        return EMME_EINVAL;
+    }
+    if (!c || !set || !contours || !out.roots || !out.iters || !out.info || !out.n_roots || !out.winding || !out.points_used ||
+        !out.status || (pairs && (!out.vecs || !out.resid)) || max_roots < 1 || step_limit < 0 || !(tol > 0.0)) {
+        set_error(who + ": need a context, sets, contours, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
+        return EMME_EINVAL;
+    }
+    for (int k = 0; k < nitems; ++k)
+        if (const char* bad = contour_arg_error(&contours[k])) {
+            set_error(who + ": item " + std::to_string(k) + ": " + bad);
+            return EMME_EINVAL;
+        }
+    EMME_TRY(check_set_indices(c, set, nitems, who.c_str()));
+    return search_contours(c, who, nitems, set, contours, exact, tol, step_limit, max_roots, out);
+}
+
+int region_search_one(emme_ctx* c, const std::string& who, bool pairs, const emme_contour_t* ct, int exact, double tol,
+                      int step_limit, int max_roots, SearchOutputs out) {
+    if (!c || !ct || !out.roots || !out.iters || !out.info || !out.n_roots || !out.winding || !out.points_used ||
+        (pairs && (!out.vecs || !out.resid)) || max_roots < 1 || step_limit < 0 || !(tol > 0.0)) {
+        set_error(who + ": need a context, a contour, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
+        return EMME_EINVAL;
+    }
+    if (const char* bad = contour_arg_error(ct)) {
+        set_error(who + ": " + bad);
+        return EMME_EINVAL;
+    }
+    // one item on the context's own parameters; what takes the item out of the search is the call's error
+    int status = EMME_OK;
+    out.status = &status;
+    const int rc = search_contours(c, who, 1, nullptr, ct, exact, tol, step_limit, max_roots, out);
+    return rc ? rc : status;
+}
+
+}  // namespace
 
 extern "C" {
 
@@ -650,42 +735,29 @@ int emme_contour_moments_groups(emme_ctx_t* c, int n, int nq, const double* M, c
 int emme_find_roots_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, const emme_contour_t* contours, int exact,
                                      double tol, int step_limit, int max_roots, double* roots, int* iters, int* info,
                                      int* n_roots, int* winding, int* points_used, int* status) {
-    const std::string who = "emme_find_roots_in_contours_sets";
-    if (nitems < 1 || nitems > 65535) {
-        set_error(who + ": nitems must lie in 1 .. 65535");
-        return EMME_EINVAL;
-    }
-    if (!c || !set || !contours || !roots || !iters || !info || !n_roots || !winding || !points_used || !status ||
-        max_roots < 1 || step_limit < 0 || !(tol > 0.0)) {
-        set_error(who + ": need a context, sets, contours, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
-        return EMME_EINVAL;
-    }
-    for (int k = 0; k < nitems; ++k)
-        if (const char* bad = contour_arg_error(&contours[k])) {
-            set_error(who + ": item " + std::to_string(k) + ": " + bad);
-            return EMME_EINVAL;
-        }
-    EMME_TRY(check_set_indices(c, set, nitems, who.c_str()));
-    return search_contours(c, who, nitems, set, contours, exact, tol, step_limit, max_roots,
-                           {roots, iters, info, n_roots, winding, points_used, status});
+    return region_search_sets(c, "emme_find_roots_in_contours_sets", false, nitems, set, contours, exact, tol, step_limit,
+                              max_roots, {roots, iters, info, n_roots, winding, points_used, status});
 }
 
 int emme_find_roots_in_contour(emme_ctx_t* c, const emme_contour_t* ct, double tol, int step_limit, int max_roots,
                                double* roots, int* iters, int* info, int* n_roots, int* winding, int* points_used) {
-    if (!c || !ct || !roots || !iters || !info || !n_roots || !winding || !points_used || max_roots < 1 || step_limit < 0 ||
-        !(tol > 0.0)) {
-        set_error("emme_find_roots_in_contour: need a context, a contour, tol > 0, step_limit >= 0, max_roots >= 1 and every output");
-        return EMME_EINVAL;
-    }
-    if (const char* bad = contour_arg_error(ct)) {
-        set_error(std::string("emme_find_roots_in_contour: ") + bad);
-        return EMME_EINVAL;
-    }
-    // one item on the context's own parameters; what takes the item out of the search is the call's error
-    int status = EMME_OK;
-    const int rc = search_contours(c, "emme_find_roots_in_contour", 1, nullptr, ct, 0, tol, step_limit, max_roots,
-                                   {roots, iters, info, n_roots, winding, points_used, &status});
-    return rc ? rc : status;
+    return region_search_one(c, "emme_find_roots_in_contour", false, ct, 0, tol, step_limit, max_roots,
+                             {roots, iters, info, n_roots, winding, points_used, nullptr});
+}
+
+int emme_find_eigenpairs_in_contours_sets(emme_ctx_t* c, int nitems, const int* set, const emme_contour_t* contours,
+                                          int exact, double tol, int step_limit, int max_roots, double* roots, double* vecs,
+                                          double* resid, int* iters, int* info, int* n_roots, int* winding, int* points_used,
+                                          int* status) {
+    return region_search_sets(c, "emme_find_eigenpairs_in_contours_sets", true, nitems, set, contours, exact, tol, step_limit,
+                              max_roots, {roots, iters, info, n_roots, winding, points_used, status, vecs, resid});
+}
+
+int emme_find_eigenpairs_in_contour(emme_ctx_t* c, const emme_contour_t* ct, int exact, double tol, int step_limit,
+                                    int max_roots, double* roots, double* vecs, double* resid, int* iters, int* info,
+                                    int* n_roots, int* winding, int* points_used) {
+    return region_search_one(c, "emme_find_eigenpairs_in_contour", true, ct, exact, tol, step_limit, max_roots,
+                             {roots, iters, info, n_roots, winding, points_used, nullptr, vecs, resid});
 }
 
 }  // extern "C"

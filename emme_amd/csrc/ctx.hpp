@@ -149,6 +149,7 @@ struct emme_ctx {
     DeviceBuffer<double> d_M, d_Mold, d_Mp, d_work;  // matrix sets
     DeviceBuffer<double> d_iterates;
     DeviceBuffer<double> d_vecs, d_resid;  // eigenpair search: the chains' vectors [n][dim], residuals [n]
+    PinnedBuffer<int> p_live;      // ... and, in the secant loop, d_active as the step's update left it
     int last_n = 0;
     // profiling
     bool prof = false;

@@ -1,7 +1,7 @@
 // ctx_linstep.hip -- the Newton linear step and the batched LU above their kernels (linstep*.hip, nullspace.hip):
 // which kernel and how many workgroups a launch gets (linstep_plan.hpp), operands staged where the kernels can read
 // them, and the entry points emme_trace_solve_batch, emme_qr_secant_batch, emme_null_vectors_batch,
-// emme_eigenpair_step_batch.
+// emme_eigenpair_step_batch, emme_eigenpair_secant_step_batch.
 #include "ctx.hpp"
 #include "linstep_plan.hpp"
 
@@ -158,6 +158,65 @@ int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, 
 
 }  // namespace emme
 
+namespace {
+
+// What emme_eigenpair_step_batch (domega null: Mp is dM/domega) and emme_eigenpair_secant_step_batch (domega: host,
+// nbatch complex; Mp is M_old) are: one step of eigpair.hip on caller matrices, which are not modified
+int caller_eigenpair_step(emme_ctx* c, const char* who, int n, int nbatch, const double* M, const double* Mp,
+                          const double* domega, double* v, int have_v, double* tau, double* resid, int* info) {
+    if (!c || !M || !Mp || !v || !tau || !resid || !info || n < 1 || nbatch < 1) {
+        set_error(std::string(who) + ": a required pointer is NULL, n < 1 or nbatch < 1");
+        return EMME_EINVAL;
+    }
+    if (n > 2048) {
+        set_error(std::string(who) + ": order above 2048 is not supported");
+        return EMME_ECONFIG;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, nbatch));
+    const size_t bytes = batch_bytes(n, nbatch), vbytes = sizeof(double) * 2 * (size_t)n * nbatch;
+    DeviceOperands ops;
+    hipError_t staged = hipSuccess;
+    EMME_TRY(ops.stage(c, M, Mp, bytes, &staged));
+    HIP_TRY(staged);
+    // device scratch of this call: the work copy the factorisation overwrites, vectors, tau, residuals, info
+    DeviceBuffer<double> t_a, t_v, t_tau, t_res, t_dw;
+    DeviceBuffer<int> t_info;
+    HIP_TRY(t_a.grow(bytes));
+    HIP_TRY(t_v.grow(vbytes));
+    HIP_TRY(t_tau.grow(sizeof(double) * 2 * nbatch));
+    HIP_TRY(t_res.grow(sizeof(double) * nbatch));
+    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
+    HIP_TRY(hipMemcpyAsync(t_a, ops.A, bytes, hipMemcpyDeviceToDevice, c->stream));
+    if (have_v) HIP_TRY(hipMemcpyAsync(t_v, v, vbytes, hipMemcpyHostToDevice, c->stream));
+    if (domega) {
+        HIP_TRY(t_dw.grow(sizeof(double) * 2 * nbatch));
+        HIP_TRY(hipMemcpyAsync(t_dw, domega, sizeof(double) * 2 * nbatch, hipMemcpyHostToDevice, c->stream));
+    }
+    LuScratch scratch;
+    const int rc = lu_factor_batch(c, n, nbatch, t_a, scratch, who,
+                                   [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+                                       const size_t m0 = (size_t)b0 * n * n * 2;
+                                       if (domega)
+                                           return launch_eigpair_secant_step(n, ops.A + m0, ops.B + m0, t_dw + 2 * b0, t_a + m0, maps,
+                                                                             map_nb, nullptr, nb, nullptr, lu_info,
+                                                                             t_v + (size_t)b0 * n * 2, t_tau + 2 * b0, t_res + b0,
+                                                                             t_info + b0, !have_v, c->stream);
+                                       return launch_eigpair_step(n, ops.A + m0, ops.B + m0, t_a + m0, maps, map_nb, nullptr, nb,
+                                                                  nullptr, lu_info, t_v + (size_t)b0 * n * 2, t_tau + 2 * b0,
+                                                                  t_res + b0, t_info + b0, !have_v, c->stream);
+                                   });
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(v, t_v, vbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tau, t_tau, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(resid, t_res, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
+}
+
+}  // namespace
+
 extern "C" {
 
 int emme_trace_solve_batch(emme_ctx_t* c, int n, int nbatch, double* A, double* B, double* tr,
@@ -269,46 +328,18 @@ int emme_null_vectors_batch(emme_ctx_t* c, int n, int nbatch, const double* M, d
 // One eigenpair step (eigpair.hip) on caller matrices, which are not modified
 int emme_eigenpair_step_batch(emme_ctx_t* c, int n, int nbatch, const double* M, const double* Mp, double* v, int have_v,
                               double* tau, double* resid, int* info) {
-    if (!c || !M || !Mp || !v || !tau || !resid || !info || n < 1 || nbatch < 1) {
-        set_error("emme_eigenpair_step_batch: a required pointer is NULL, n < 1 or nbatch < 1");
+    return caller_eigenpair_step(c, "emme_eigenpair_step_batch", n, nbatch, M, Mp, nullptr, v, have_v, tau, resid, info);
+}
+
+// The secant reading of it: M_old = the previous fill, domega (host) the step between the two
+int emme_eigenpair_secant_step_batch(emme_ctx_t* c, int n, int nbatch, const double* M, const double* M_old,
+                                     const double* domega, double* v, int have_v, double* tau, double* resid, int* info) {
+    if (!domega) {
+        set_error("emme_eigenpair_secant_step_batch: a required pointer is NULL, n < 1 or nbatch < 1");
         return EMME_EINVAL;
     }
-    if (n > 2048) {
-        set_error("emme_eigenpair_step_batch: order above 2048 is not supported");
-        return EMME_ECONFIG;
-    }
-    HIP_TRY(hipSetDevice(c->device));
-    EMME_TRY(ensure_batch(c, nbatch));
-    const size_t bytes = batch_bytes(n, nbatch), vbytes = sizeof(double) * 2 * (size_t)n * nbatch;
-    DeviceOperands ops;
-    hipError_t staged = hipSuccess;
-    EMME_TRY(ops.stage(c, M, Mp, bytes, &staged));
-    HIP_TRY(staged);
-    // device scratch of this call: the work copy the factorisation overwrites, vectors, tau, residuals, info
-    DeviceBuffer<double> t_a, t_v, t_tau, t_res;
-    DeviceBuffer<int> t_info;
-    HIP_TRY(t_a.grow(bytes));
-    HIP_TRY(t_v.grow(vbytes));
-    HIP_TRY(t_tau.grow(sizeof(double) * 2 * nbatch));
-    HIP_TRY(t_res.grow(sizeof(double) * nbatch));
-    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
-    HIP_TRY(hipMemcpyAsync(t_a, ops.A, bytes, hipMemcpyDeviceToDevice, c->stream));
-    if (have_v) HIP_TRY(hipMemcpyAsync(t_v, v, vbytes, hipMemcpyHostToDevice, c->stream));
-    LuScratch scratch;
-    const int rc = lu_factor_batch(c, n, nbatch, t_a, scratch, "emme_eigenpair_step_batch",
-                                   [&](int b0, int nb, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
-                                       const size_t m0 = (size_t)b0 * n * n * 2;
-                                       return launch_eigpair_step(n, ops.A + m0, ops.B + m0, t_a + m0, maps, map_nb, nullptr, nb,
-                                                                  nullptr, lu_info, t_v + (size_t)b0 * n * 2, t_tau + 2 * b0,
-                                                                  t_res + b0, t_info + b0, !have_v, c->stream);
-                                   });
-    if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(v, t_v, vbytes, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(tau, t_tau, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(resid, t_res, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    return EMME_OK;
+    return caller_eigenpair_step(c, "emme_eigenpair_secant_step_batch", n, nbatch, M, M_old, domega, v, have_v, tau, resid,
+                                 info);
 }
 
 }  // extern "C"

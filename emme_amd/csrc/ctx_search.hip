@@ -2,7 +2,7 @@
 // newtonTraceSecantIteration (include/solver.h:396-415, 113-160) under the solve_once_eigen loop (src/main.cpp:19-80),
 // the Newton search on the exact derivative and, in the same loop, Newton on the eigenpair.
 // Entry points: emme_solve_roots, emme_solve_roots_newton, emme_solve_roots_sets, emme_solve_eigenpairs,
-// emme_newton_step_batch.
+// emme_solve_eigenpairs_secant, emme_newton_step_batch.
 #include "ctx.hpp"
 
 using namespace emme;
@@ -19,7 +19,8 @@ struct RootSearch {
     bool want_iterates;
     int method = 0;
     const int* set = nullptr;  // host, n ints: chain b searches on the bound parameter set set[b] (null: the context's own)
-    bool eigpair = false;      // newton_loop's linear step is the eigenpair step: `method` is not consulted
+    bool eigpair = false;      // the loop's linear step is the eigenpair step (secant_loop: its secant
+                               // reading): `method` is not consulted
     const double* v0 = nullptr;  // eigenpair search: host, n * dim complex unit start vectors (null: from M(omega_0)^-1 s)
     LuScratch lu;              // ... and what its factorisations keep between launches
     std::vector<int> act, zeros;  // host image of d_active (every chain live at the start); n zeros
@@ -51,6 +52,7 @@ int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
         const size_t vbytes = sizeof(double) * 2 * (size_t)n * c->dim;
         HIP_TRY(c->d_vecs.grow(vbytes));
         HIP_TRY(c->d_resid.grow(sizeof(double) * n));
+        HIP_TRY(c->p_live.grow(sizeof(int) * n));
         if (s.v0) HIP_TRY(hipMemcpyAsync(c->d_vecs, s.v0, vbytes, hipMemcpyHostToDevice, c->stream));
     }
     HIP_TRY(hipMemcpyAsync(c->d_active, s.act.data(), sizeof(int) * n, hipMemcpyHostToDevice, c->stream));
@@ -95,8 +97,41 @@ int search_end(emme_ctx* c, const RootSearch& s, double* roots, int* iters, int*
     return EMME_OK;
 }
 
+// One eigenpair step (eigpair.hip) for the chains still iterating, on the work copies the loop has just made:
+// factor the live ones only (lu_factor_batch with their list; its launches count as K_NULL spans), then
+// k_eigpair_step on the same list leaves tau in d_tr for launch_newton_update, the new vectors in d_vecs and the
+// residual before the step in d_resid.  A factorisation that stops leaves the column in d_info: the chain retires.
+// `live`: the chains' flags as the last launch_newton_update left them (1: iterating; 2: converged at that step and
+// retired behind its fill).  secant: k_eigpair_secant_step on (d_M, d_Mold, d_domega) instead of (d_M, d_Mp).
+int eigpair_step(emme_ctx* c, RootSearch& search, const int* live, bool first, bool secant) {
+    const int n = search.n, dim = c->dim;
+    int* slot = nullptr;
+    HIP_TRY(c->d_lu_items.grow(sizeof(int) * n));
+    HIP_TRY(c->lists.take(n, &slot));
+    int n_live = 0;
+    for (int b = 0; b < n; ++b)
+        if (live[b] == 1) slot[n_live++] = b;
+    if (n_live == 0) return EMME_OK;
+    HIP_TRY(launch_stage_ints(slot, c->d_lu_items, n_live, nullptr, 0, c->stream));
+    HIP_TRY(c->lists.read_on(c->stream));
+    return lu_factor_batch(
+        c, dim, n, c->d_work, search.lu, secant ? "emme_solve_eigenpairs_secant" : "emme_solve_eigenpairs",
+        [&](int i0, int ni, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
+            if (secant)
+                return launch_eigpair_secant_step(dim, c->d_M, c->d_Mold, c->d_domega, c->d_work, maps, map_nb,
+                                                  c->d_lu_items + i0, ni, c->d_active, lu_info, c->d_vecs, c->d_tr, c->d_resid,
+                                                  c->d_info, first, c->stream);
+            return launch_eigpair_step(dim, c->d_M, c->d_Mp, c->d_work, maps, map_nb, c->d_lu_items + i0, ni, c->d_active,
+                                       lu_info, c->d_vecs, c->d_tr, c->d_resid, c->d_info, first, c->stream);
+        },
+        c->d_lu_items, n_live);
+}
+
 // The secant search of emme_solve_roots (EigenSolver's constructor and newtonTraceSecantIteration, include/solver.h:
-// 396-415 and 113-160, under the loop of src/main.cpp:19-80), between search_begin and search_end.
+// 396-415 and 113-160, under the loop of src/main.cpp:19-80), between search_begin and search_end; with search.eigpair,
+// that of emme_solve_eigenpairs_secant: the same bootstrap, fills and feedback around the secant
+// eigenpair step, which reads M and M_old themselves -- no M' is formed, and M_old follows M by a copy of the live
+// matrices once the step has read both.
 int secant_loop(emme_ctx* c, RootSearch& search) {
     const int n = search.n, method = search.method, step_limit = search.step_limit, stride = search.stride();
     const double* guesses = search.guesses;
@@ -168,16 +203,30 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
                     j_pending, nprev, tot, mx, na);
         }
     };
+    // eigenpair search: the flags as every launch_newton_update leaves them, read at the step's one synchronisation --
+    // the list of the next factorisation is exact (it writes d_info of what it is given), where `act` is a step old
+    const bool eig = search.eigpair;
+    if (eig) std::fill(c->p_live.get(), c->p_live.get() + n, 1);
     for (int j = 0; j <= step_limit; ++j) {  // src/main.cpp:43
         const bool fused_copy = method == EMME_METHOD_TRACE_SECANT;
-        {
-            // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
-            // LU's work copy): one pass, for the chains still iterating only
+        if (eig) {
+            // the work copy of the live M, its factorisation and the secant eigenpair step on (M, M_old, domega); then
+            // this step's matrix becomes the "previous" one
+            {
+                ScopedSpan s(c, K_LIN);
+                HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_work, nullptr, c->d_active, c->stream));
+            }
+            EMME_TRY(eigpair_step(c, search, c->p_live.get(), j == 0 && !search.v0, true));
             ScopedSpan s(c, K_OTHER);
-            HIP_TRY(launch_secant_copy_sym(c->dim, n, c->d_M, c->d_Mold, fused_copy ? c->d_work : nullptr, c->d_Mp,
-                                           c->d_domega, c->d_active, c->stream));
-        }
-        {
+            HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_Mold, nullptr, c->d_active, c->stream));
+        } else {
+            {
+                // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
+                // LU's work copy): one pass, for the chains still iterating only
+                ScopedSpan s(c, K_OTHER);
+                HIP_TRY(launch_secant_copy_sym(c->dim, n, c->d_M, c->d_Mold, fused_copy ? c->d_work : nullptr, c->d_Mp,
+                                               c->d_domega, c->d_active, c->stream));
+            }
             ScopedSpan s(c, K_LIN);
             HIP_TRY(linear_step(c, method, c->dim, n, c->d_M, c->d_work, c->d_Mp, c->d_active, c->d_tr, c->d_info,
                                 act.data(), fused_copy));
@@ -188,6 +237,7 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
                                          c->d_info, tol, d_iterates, j, stride, c->stream, c->p_w,
                                          c->opt.skip_lost ? c->d_status : nullptr));
         }
+        if (eig) HIP_TRY(hipMemcpyAsync(c->p_live, c->d_active, sizeof(int) * n, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(hipStreamSynchronize(c->stream));
         std::copy(c->p_w.get(), c->p_w.get() + 2 * (size_t)n, h_w.begin());
         if (pending) {
@@ -204,31 +254,12 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
         }
         pending = true, j_pending = j;
     }
+    if (eig) {
+        // the residual of what is returned, omega and v, on the last fill's matrix, as newton_loop takes it
+        ScopedSpan s(c, K_LIN);
+        HIP_TRY(launch_eigpair_resid(c->dim, c->d_M, nullptr, n, c->d_vecs, c->d_resid, c->stream));
+    }
     return EMME_OK;
-}
-
-// One eigenpair step (eigpair.hip) for the chains still iterating, on the work copies newton_loop has just made:
-// factor the live ones only (lu_factor_batch with their list; its launches count as K_NULL spans), then
-// k_eigpair_step on the same list leaves tau in d_tr for launch_newton_update, the new vectors in d_vecs and the
-// residual before the step in d_resid.  A factorisation that stops leaves the column in d_info: the chain retires.
-int eigpair_step(emme_ctx* c, RootSearch& search, bool first) {
-    const int n = search.n, dim = c->dim;
-    int* slot = nullptr;
-    HIP_TRY(c->d_lu_items.grow(sizeof(int) * n));
-    HIP_TRY(c->lists.take(n, &slot));
-    int n_live = 0;
-    for (int b = 0; b < n; ++b)
-        if (search.act[b] == 1) slot[n_live++] = b;  // (2: converged at the last step and retired behind its fill)
-    if (n_live == 0) return EMME_OK;
-    HIP_TRY(launch_stage_ints(slot, c->d_lu_items, n_live, nullptr, 0, c->stream));
-    HIP_TRY(c->lists.read_on(c->stream));
-    return lu_factor_batch(
-        c, dim, n, c->d_work, search.lu, "emme_solve_eigenpairs",
-        [&](int i0, int ni, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
-            return launch_eigpair_step(dim, c->d_M, c->d_Mp, c->d_work, maps, map_nb, c->d_lu_items + i0, ni, c->d_active,
-                                       lu_info, c->d_vecs, c->d_tr, c->d_resid, c->d_info, first, c->stream);
-        },
-        c->d_lu_items, n_live);
 }
 
 // The Newton search of emme_solve_roots_newton, between search_begin and search_end; with
@@ -281,7 +312,7 @@ int newton_loop(emme_ctx* c, RootSearch& search) {
                                     act.data(), trace));
         }
         // the eigenpair search: d_tr <- v^H M^-1 M' v instead, and the chain's vector moves with it
-        if (search.eigpair) EMME_TRY(eigpair_step(c, search, j == 0 && !search.v0));
+        if (search.eigpair) EMME_TRY(eigpair_step(c, search, act.data(), j == 0 && !search.v0, false));
         {
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_newton_update(n, c->d_tr, c->d_omega, c->d_domega, c->d_active, c->d_iters, c->d_info, tol,
@@ -337,6 +368,51 @@ int run_search(emme_ctx* c, const double* guesses, int n, double tol, int step_l
         EMME_TRY(search_end(c, s, roots, iters, info, iterates, &repeat));
         if (!repeat) return EMME_OK;
     }
+}
+
+// What emme_solve_eigenpairs (newton_loop: exact M') and emme_solve_eigenpairs_secant (secant_loop: two plain fills)
+// are: the argument rules, the start vectors normalised, the search, the pairs read back and failed chains blanked
+int solve_eigenpairs(emme_ctx* c, const std::string& who, bool secant, const int* set, const double* guesses, int n,
+                     const double* v0, double tol, int step_limit, double* roots, double* vecs, double* resid, int* iters,
+                     int* info, double* iterates) {
+    if (!c || !guesses || !roots || !vecs || !resid || !iters || !info || n < 1 || step_limit < 0 || !(tol > 0.0)) {
+        set_error(who + ": a required pointer is NULL, n < 1, step_limit < 0 or tol <= 0");
+        return EMME_EINVAL;
+    }
+    const int dim = c->dim;
+    if (dim > 2048) {
+        set_error(who + ": matrix dimension above 2048 is not supported");
+        return EMME_ECONFIG;
+    }
+    if (set) EMME_TRY(check_set_indices(c, set, n, who.c_str()));
+    std::vector<double> vn;  // the caller's start vectors, each of unit 2-norm
+    if (v0) {
+        vn.assign(v0, v0 + 2 * (size_t)n * dim);
+        for (int b = 0; b < n; ++b) {
+            double* row = vn.data() + 2 * (size_t)b * dim;
+            double s2 = 0.0;
+            for (int i = 0; i < 2 * dim; ++i) s2 += row[i] * row[i];
+            const double nrm = std::sqrt(s2);
+            if (!(nrm > 0.0) || !std::isfinite(nrm)) {
+                set_error(who + ": v0 row " + std::to_string(b) + " is zero or not finite");
+                return EMME_EINVAL;
+            }
+            for (int i = 0; i < 2 * dim; ++i) row[i] /= nrm;
+        }
+    }
+    // (the secant search keeps M, M_old and the work copy: no M')
+    EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, secant ? 1 | 2 | 8 : 1 | 4 | 8,
+                        secant ? secant_loop : newton_loop, set, true, v0 ? vn.data() : nullptr));
+    HIP_TRY(hipMemcpyAsync(vecs, c->d_vecs, sizeof(double) * 2 * (size_t)n * dim, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(resid, c->d_resid, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    const double qnan = std::numeric_limits<double>::quiet_NaN();
+    for (int b = 0; b < n; ++b)
+        if (info[b] != 0) {  // a failed chain has no pair
+            std::fill(vecs + 2 * (size_t)b * dim, vecs + 2 * (size_t)(b + 1) * dim, qnan);
+            resid[b] = qnan;
+        }
+    return EMME_OK;
 }
 
 }  // namespace
@@ -422,43 +498,16 @@ int emme_solve_roots_sets(emme_ctx_t* c, const int* set, const double* guesses, 
 int emme_solve_eigenpairs(emme_ctx_t* c, const int* set, const double* guesses, int n, const double* v0, double tol,
                           int step_limit, double* roots, double* vecs, double* resid, int* iters, int* info,
                           double* iterates) {
-    if (!c || !guesses || !roots || !vecs || !resid || !iters || !info || n < 1 || step_limit < 0 || !(tol > 0.0)) {
-        set_error("emme_solve_eigenpairs: a required pointer is NULL, n < 1, step_limit < 0 or tol <= 0");
-        return EMME_EINVAL;
-    }
-    const int dim = c->dim;
-    if (dim > 2048) {
-        set_error("emme_solve_eigenpairs: matrix dimension above 2048 is not supported");
-        return EMME_ECONFIG;
-    }
-    if (set) EMME_TRY(check_set_indices(c, set, n, "emme_solve_eigenpairs"));
-    std::vector<double> vn;  // the caller's start vectors, each of unit 2-norm
-    if (v0) {
-        vn.assign(v0, v0 + 2 * (size_t)n * dim);
-        for (int b = 0; b < n; ++b) {
-            double* row = vn.data() + 2 * (size_t)b * dim;
-            double s2 = 0.0;
-            for (int i = 0; i < 2 * dim; ++i) s2 += row[i] * row[i];
-            const double nrm = std::sqrt(s2);
-            if (!(nrm > 0.0) || !std::isfinite(nrm)) {
-                set_error("emme_solve_eigenpairs: v0 row " + std::to_string(b) + " is zero or not finite");
-                return EMME_EINVAL;
-            }
-            for (int i = 0; i < 2 * dim; ++i) row[i] /= nrm;
-        }
-    }
-    EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, 1 | 4 | 8, newton_loop, set, true,
-                        v0 ? vn.data() : nullptr));
-    HIP_TRY(hipMemcpyAsync(vecs, c->d_vecs, sizeof(double) * 2 * (size_t)n * dim, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipMemcpyAsync(resid, c->d_resid, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(hipStreamSynchronize(c->stream));
-    const double qnan = std::numeric_limits<double>::quiet_NaN();
-    for (int b = 0; b < n; ++b)
-        if (info[b] != 0) {  // a failed chain has no pair
-            std::fill(vecs + 2 * (size_t)b * dim, vecs + 2 * (size_t)(b + 1) * dim, qnan);
-            resid[b] = qnan;
-        }
-    return EMME_OK;
+    return solve_eigenpairs(c, "emme_solve_eigenpairs", false, set, guesses, n, v0, tol, step_limit, roots, vecs, resid, iters,
+                            info, iterates);
+}
+
+// The same on two consecutive plain fills: secant_loop around k_eigpair_secant_step
+int emme_solve_eigenpairs_secant(emme_ctx_t* c, const int* set, const double* guesses, int n, const double* v0, double tol,
+                                 int step_limit, double* roots, double* vecs, double* resid, int* iters, int* info,
+                                 double* iterates) {
+    return solve_eigenpairs(c, "emme_solve_eigenpairs_secant", true, set, guesses, n, v0, tol, step_limit, roots, vecs, resid,
+                            iters, info, iterates);
 }
 
 }  // extern "C"

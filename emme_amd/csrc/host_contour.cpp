@@ -152,6 +152,70 @@ bool eigenvalues(int k, std::vector<cd>& H, std::vector<cd>& ev) {
     return true;
 }
 
+// y (k complex, unit 2-norm): the eigenvector of the k x k matrix B (row-major, kept) for its eigenvalue mu, by inverse
+// iteration on a partial-pivot LU of B - mu I.  mu comes from the QR iteration, so the shifted matrix is singular to
+// rounding and one or two solves align y; where a pivot is exactly zero the shift is moved by a few eps |B| and the
+// factorisation repeated.
+void eigenvector_of(int k, const std::vector<cd>& B, cd mu, std::vector<cd>& y) {
+    double bnorm = 0.0;
+    for (const cd& b : B) bnorm = std::max(bnorm, std::abs(b));
+    if (!(bnorm > 0.0)) bnorm = 1.0;
+    std::vector<cd> A((size_t)k * k);
+    std::vector<int> piv(k);
+    auto a = [&](int r, int c) -> cd& { return A[(size_t)r * k + c]; };
+    for (int attempt = 0; attempt < 8; ++attempt) {
+        const cd shift = mu + (attempt == 0 ? cd(0.0) : cd(1.0, 1.0) * (kEps * bnorm * std::ldexp(1.0, 2 * attempt)));
+        A = B;
+        for (int j = 0; j < k; ++j) a(j, j) -= shift;
+        bool singular = false;
+        for (int j = 0; j < k && !singular; ++j) {
+            int p = j;
+            for (int r = j + 1; r < k; ++r)
+                if (std::abs(a(r, j)) > std::abs(a(p, j))) p = r;
+            piv[j] = p;
+            if (p != j)
+                for (int c = 0; c < k; ++c) std::swap(a(j, c), a(p, c));
+            if (std::abs(a(j, j)) == 0.0 || !std::isfinite(std::abs(a(j, j)))) {
+                singular = true;
+                break;
+            }
+            for (int r = j + 1; r < k; ++r) {
+                const cd m = a(r, j) / a(j, j);
+                a(r, j) = m;
+                for (int c = j + 1; c < k; ++c) a(r, c) -= m * a(j, c);
+            }
+        }
+        if (singular) continue;
+        // a start vector with weight on every component, then three solves
+        y.resize(k);
+        for (int i = 0; i < k; ++i) y[i] = cd(1.0 + 0.37 * std::sin(1.0 + i), 0.21 * std::cos(2.0 * i));
+        bool ok = true;
+        for (int sweep = 0; sweep < 3 && ok; ++sweep) {
+            for (int j = 0; j < k; ++j) {
+                std::swap(y[j], y[piv[j]]);
+                for (int r = j + 1; r < k; ++r) y[r] -= a(r, j) * y[j];
+            }
+            for (int j = k - 1; j >= 0; --j) {
+                for (int c = j + 1; c < k; ++c) y[j] -= a(j, c) * y[c];
+                y[j] /= a(j, j);
+            }
+            // (scaled by the largest entry first: the solution of a nearly singular system may be huge)
+            double big = 0.0;
+            for (int i = 0; i < k; ++i) big = std::max(big, std::max(std::fabs(y[i].real()), std::fabs(y[i].imag())));
+            ok = big > 0.0 && std::isfinite(big);
+            if (!ok) break;
+            double nrm = 0.0;
+            for (int i = 0; i < k; ++i) y[i] /= big, nrm += std::norm(y[i]);
+            nrm = std::sqrt(nrm);
+            for (int i = 0; i < k; ++i) y[i] /= nrm;
+        }
+        if (ok) return;
+    }
+    // (not reached for a finite B: eight shifts cannot all hit an eigenvalue exactly)
+    y.assign(k, 0.0);
+    y[0] = 1.0;
+}
+
 }  // namespace
 
 namespace emme {
@@ -192,11 +256,14 @@ double norm_radius(const emme_contour_t& ct, double re, double im) {
 }
 }  // namespace
 
-void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::vector<double>& guesses) {
+void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::vector<double>& guesses,
+                        std::vector<int>* kept) {
     const double rho = std::max(ct.semi_axes[0], ct.semi_axes[1]);
     for (int q = 0; q < k; ++q) {
         const double re = ct.center[0] + rho * mu[2 * q], im = ct.center[1] + rho * mu[2 * q + 1];
-        if (std::isfinite(re) && std::isfinite(im) && norm_radius(ct, re, im) < 1.5) guesses.push_back(re), guesses.push_back(im);
+        if (!(std::isfinite(re) && std::isfinite(im) && norm_radius(ct, re, im) < 1.5)) continue;
+        guesses.push_back(re), guesses.push_back(im);
+        if (kept) kept->push_back(q);
     }
 }
 
@@ -215,7 +282,7 @@ std::vector<ContourRoot> contour_keep_roots(const emme_contour_t& ct, double tol
         bool dup = false;
         for (const ContourRoot& f : found)
             dup |= std::hypot(f.re - r[2 * q], f.im - r[2 * q + 1]) <= 10.0 * tol * std::hypot(r[2 * q], r[2 * q + 1]);
-        if (!dup) found.push_back({r[2 * q], r[2 * q + 1], its[q], inf[q]});
+        if (!dup) found.push_back({r[2 * q], r[2 * q + 1], its[q], inf[q], q});
     }
     std::stable_sort(found.begin(), found.end(), [](const ContourRoot& x, const ContourRoot& y) { return x.im > y.im; });
     return found;
@@ -316,25 +383,14 @@ bool ContourRounds::take_rank(int item, int k, int* l0, int* nl) {
 
 }  // namespace emme
 
-extern "C" {
-
-void emme_contour_default(emme_contour_t* c) {
-    if (!c) return;
-    *c = emme_contour_t{};
-    c->size = (int)sizeof(emme_contour_t);
-    // DESIGN.md §11: the count resolves at N = 8 .. 64 on the test contours; sigma(A0) levels off 3e-9 .. 8e-7 below
-    // sigma_1 once it does (the fill's own accuracy), the modes stand at >= 0.1 sigma_1
-    c->points = 32;
-    c->max_points = 512;
-    c->probes = 8;
-    c->rank_tol = 1e-5;
-}
+namespace {
 
 // The Beyn step (Beyn 2012, algorithm 1, steps 3-5) on moments A0 = sum w_j X_j, A1 = sum w_j z_j X_j
-int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double rank_tol, int max_eigs, double* mu,
-                      int* k_out, double* sigma) {
+// and, vecs given, the eigenvectors v_c = U_k y_c of M for every mu_c written (y_c: the eigenvector of B for mu_c)
+int beyn_step(const char* who, int n, int L, const double* A0, const double* A1, double rank_tol, int max_eigs, double* mu,
+              double* vecs, int* k_out, double* sigma) {
     if (n < 1 || L < 1 || L > 64 || !A0 || !A1 || !mu || !k_out || max_eigs < 1 || !(rank_tol > 0.0 && rank_tol < 1.0)) {
-        emme::set_error("emme_contour_eigs: need n >= 1, 1 <= L <= 64, A0, A1, mu, k, max_eigs >= 1 and 0 < rank_tol < 1");
+        emme::set_error(std::string(who) + ": need n >= 1, 1 <= L <= 64, A0, A1, mu, k, max_eigs >= 1 and 0 < rank_tol < 1");
         return EMME_EINVAL;
     }
     const cd* a0 = reinterpret_cast<const cd*>(A0);
@@ -375,13 +431,57 @@ int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double r
             B[(size_t)p * k + q] = t / (s[cp] * s[cq]);
         }
     }
-    std::vector<cd> ev;
+    std::vector<cd> ev, Bkept;
+    if (vecs) Bkept = B;  // (the QR iteration destroys its operand)
     if (!eigenvalues(k, B, ev)) {
-        emme::set_error("emme_contour_eigs: the QR iteration on the reduced matrix did not converge");
+        emme::set_error(std::string(who) + ": the QR iteration on the reduced matrix did not converge");
         return EMME_ENUMERIC;
     }
     for (int q = 0; q < std::min(k, max_eigs); ++q) mu[2 * q] = ev[q].real(), mu[2 * q + 1] = ev[q].imag();
+    if (!vecs) return EMME_OK;
+    std::vector<cd> y, v(n);
+    for (int q = 0; q < std::min(k, max_eigs); ++q) {
+        eigenvector_of(k, Bkept, ev[q], y);
+        // v = U_k y, U_p = G_p / s_p; U_k is orthonormal to rounding only, so the norm is taken again
+        double nrm = 0.0;
+        for (int i = 0; i < n; ++i) {
+            cd t = 0.0;
+            for (int p = 0; p < k; ++p) t += G[ord[p]][i] * (y[p] / s[ord[p]]);
+            v[i] = t, nrm += std::norm(t);
+        }
+        nrm = std::sqrt(nrm);
+        cd* row = reinterpret_cast<cd*>(vecs) + (size_t)q * n;
+        for (int i = 0; i < n; ++i) row[i] = v[i] / nrm;
+    }
     return EMME_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+void emme_contour_default(emme_contour_t* c) {
+    if (!c) return;
+    *c = emme_contour_t{};
+    c->size = (int)sizeof(emme_contour_t);
+    // DESIGN.md §11: the count resolves at N = 8 .. 64 on the test contours; sigma(A0) levels off 3e-9 .. 8e-7 below
+    // sigma_1 once it does (the fill's own accuracy), the modes stand at >= 0.1 sigma_1
+    c->points = 32;
+    c->max_points = 512;
+    c->probes = 8;
+    c->rank_tol = 1e-5;
+}
+
+// The Beyn step (Beyn 2012, algorithm 1, steps 3-5) on given moments
+int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double rank_tol, int max_eigs, double* mu,
+                      int* k_out, double* sigma) {
+    return beyn_step("emme_contour_eigs", n, L, A0, A1, rank_tol, max_eigs, mu, nullptr, k_out, sigma);
+}
+
+// ... with the eigenvectors v_c = U_k y_c that the step yields beside every mu_c
+int emme_contour_eigpairs(int n, int L, const double* A0, const double* A1, double rank_tol, int max_eigs, double* mu,
+                          double* vecs, int* k_out, double* sigma) {
+    return beyn_step("emme_contour_eigpairs", n, L, A0, A1, rank_tol, max_eigs, mu, vecs, k_out, sigma);
 }
 
 }  // extern "C"

@@ -23,6 +23,7 @@ const char* contour_arg_error(const emme_contour_t* ct);
 struct ContourRoot {
     double re, im;
     int it, inf;
+    int chain;  // which of the ng candidates it was
 };
 // The roots a region search keeps of its ng polished candidates r (chains its / inf, iterates `path` with
 // step_limit + 1 entries per chain): converged, inside the ellipse, no duplicate (10 tol |omega|) of an earlier
@@ -30,8 +31,10 @@ struct ContourRoot {
 std::vector<ContourRoot> contour_keep_roots(const emme_contour_t& ct, double tol, int step_limit, int ng, const double* r,
                                             const int* its, const int* inf, const double* path);
 // The candidates mu (k of them, normalised by rho = max(a, b) around the centre) that may be eigenvalues inside the
-// ellipse: finite, normalised radius below 1.5.  Appended to guesses as (re, im).
-void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::vector<double>& guesses);
+// ellipse: finite, normalised radius below 1.5.  Appended to guesses as (re, im); kept (nullable): their positions in
+// mu, appended likewise.
+void contour_candidates(const emme_contour_t& ct, int k, const double* mu, std::vector<double>& guesses,
+                        std::vector<int>* kept = nullptr);
 
 // The round plan of a region search over many (parameter set, contour) items that advance in lock step (DESIGN.md
 // §13.9).  No device: the caller fills, factors and solves what the plan asks for and hands the log-dets and ranks

@@ -309,6 +309,14 @@ hipError_t launch_null_iterate(int n, const double* A_lu, const int* rowmaps, in
 hipError_t launch_eigpair_step(int n, const double* M, const double* Mp, const double* A_lu, const int* rowmaps, int nb,
                                const int* items, int nitems, const int* active, const int* lu_info, double* vecs,
                                double* tau, double* resid, int* info, bool first, hipStream_t stream);
+// The secant reading (k_eigpair_secant_step): Mold = the previous plain fill M(omega_k-1), domega (device, complex per
+// batch item) = omega_k - omega_k-1, and u = M^-1 (M - Mold) v / domega with the difference taken per entry inside the
+// one pass that also gives M v and |M|_F^2; no M' exists.  Everything else as launch_eigpair_step; a zero or non-finite
+// domega gives EMME_ENUMERIC.
+hipError_t launch_eigpair_secant_step(int n, const double* M, const double* Mold, const double* domega, const double* A_lu,
+                                      const int* rowmaps, int nb, const int* items, int nitems, const int* active,
+                                      const int* lu_info, double* vecs, double* tau, double* resid, int* info, bool first,
+                                      hipStream_t stream);
 // the residual alone, in the same order of sums: no factors are read, vecs is left as it is
 hipError_t launch_eigpair_resid(int n, const double* M, const int* items, int nitems, const double* vecs, double* resid,
                                 hipStream_t stream);

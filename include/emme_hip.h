@@ -436,6 +436,33 @@ int emme_solve_eigenpairs(emme_ctx_t* ctx, const int* set /* NULL: the context's
  * same bits.  n <= 2048 (EMME_ECONFIG above); argument checks come before the device is looked for. */
 int emme_eigenpair_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* Mp,
                               double* v /* in/out, host */, int have_v, double* tau, double* resid, int* info);
+/* ---- the secant reading of it (additions within version 4: find them by symbol lookup) -------------
+ * The same iteration for a search that has no derivative fill, only two consecutive plain fills M = M(omega_k) and
+ * M_old = M(omega_k-1) -- the reference's own iteration is a secant one, and the plain fill is this library's fastest
+ * path (dense, cached, mirrored):
+ *     u = M^-1 (M - M_old) v_k / (omega_k - omega_k-1),   omega_k+1 = omega_k - 1 / (v_k^H u),   v_k+1 = u / |u|.
+ * The matrix M' is never formed: one pass over the rows of both matrices (k_eigpair_secant_step, eigpair.hip) takes the
+ * difference entry by entry and gives (M - M_old) v, M v and |M|_F together.  Convergence to a simple eigenpair is
+ * superlinear, as the secant root searches'.
+ *
+ * One step on caller matrices: M, M_old as M, Mp of emme_eigenpair_step_batch; domega: host, nbatch complex, the step
+ * omega_k - omega_k-1 between the two fills.  v, have_v, tau (domega_next = -1 / tau), resid (of M, before the step)
+ * and info as there; a zero or non-finite domega gives EMME_ENUMERIC.  Two calls give the same bits.  n <= 2048
+ * (EMME_ECONFIG above); argument checks come before the device is looked for. */
+int emme_eigenpair_secant_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* M_old,
+                                     const double* domega /* host, nbatch complex */, double* v /* in/out, host */,
+                                     int have_v, double* tau, double* resid, int* info);
+/* The search: arguments, outputs, v0 rules, stopping rule, info codes, blanked failed chains and NaN-padded iterates as
+ * emme_solve_eigenpairs, but bootstrapped as emme_solve_roots (omega_0 = 0.99 g, omega_1 = g: two plain fills; v_0 from
+ * M(omega_1)^-1 s without v0), and every step costs ONE plain fill, routed exactly as emme_solve_roots' are (node cache,
+ * mirrored pair list, cost order, skip_lost; parameter sets as emme_solve_roots_sets).  No derivative kernel runs and
+ * no option is consulted or changed: after a call on a default context emme_ctx_get_mirror_pairs and the options are
+ * what they were.  iteration_method is not consulted.  emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) work
+ * afterwards. */
+int emme_solve_eigenpairs_secant(emme_ctx_t* ctx, const int* set /* NULL: the context's own set */,
+                                 const double* guesses, int n, const double* v0 /* NULL, or n*dim complex */, double tol,
+                                 int step_limit, double* roots, double* vecs /* n*dim complex */, double* resid /* n */,
+                                 int* iters, int* info, double* iterates /* nullable */);
 
 /* ---- region search: every root inside a contour (version 4) ---------------------------------------
  * The reference only polishes guesses (src/main.cpp:19-80).  These entry points answer "which modes lie in this part of
@@ -522,6 +549,34 @@ int emme_find_roots_in_contours_sets(emme_ctx_t* ctx, int nitems, const int* set
  * sigma (nullable): the L singular values of A0, descending.  Returns EMME_OK, EMME_EINVAL on bad sizes. */
 int emme_contour_eigs(int n, int L, const double* A0, const double* A1, double rank_tol,
                       int max_eigs, double* mu, int* k, double* sigma);
+/* The same step with the eigenvectors it yields for free (an addition within version 4: find it by symbol lookup;
+ * DESIGN.md §11): vecs (nullable; host, min(k, max_eigs) rows of n complex) row c = v_c = U_k y_c, the eigenvector of
+ * M(omega) for mu_c, unit 2-norm, arbitrary phase; y_c is the eigenvector of B for mu_c, by inverse iteration on a kept
+ * copy of B (with a perturbed shift if B - mu_c I is exactly singular).  mu, k and sigma are emme_contour_eigs' bit for
+ * bit -- that function is this one with vecs = NULL. */
+int emme_contour_eigpairs(int n, int L, const double* A0, const double* A1, double rank_tol, int max_eigs, double* mu,
+                          double* vecs, int* k, double* sigma);
+
+/* Region searches that return eigenpairs (additions within version 4: find them by symbol lookup):
+ * emme_find_roots_in_contour / emme_find_roots_in_contours_sets with another last stage.  Nodes, count, L doubling,
+ * candidate radius, drop rules, duplicate rule, order, per-item failures and argument rules are theirs (one driver);
+ * the candidates carry their Beyn vectors (emme_contour_eigpairs on the moments of the final L pass), and ONE eigenpair
+ * search started from those vectors polishes the candidates of all items:
+ *   exact = 0   emme_solve_eigenpairs_secant (plain fills only: a default context keeps its mirrored cache)
+ *   exact = 1   emme_solve_eigenpairs (exact dM/domega fills, routed as there)
+ * with the items' set indices where there are sets.  Beside roots / iters / info, every kept root q of item k comes back
+ * with vecs[(k max_roots + q) dim ..] (dim complex, unit 2-norm, arbitrary phase) and resid[k max_roots + q] =
+ * |M(omega) v| / |M(omega)|_F; vecs holds max_roots*dim complex per item, resid max_roots.  The duplicate rule stays the
+ * omega-distance one; one drop rule is added: a polished chain whose residual is above 1e-8 stopped on its step without
+ * M being singular (a spurious candidate) and is dropped like a failed chain.  Afterwards emme_ctx_get_matrix and emme_null_vectors_batch(M = NULL) refer to the polish, as
+ * after the root forms.  The existing searches keep their polish and their bits. */
+int emme_find_eigenpairs_in_contour(emme_ctx_t* ctx, const emme_contour_t* c, int exact, double tol, int step_limit,
+                                    int max_roots, double* roots, double* vecs, double* resid, int* iters, int* info,
+                                    int* n_roots, int* winding, int* points_used);
+int emme_find_eigenpairs_in_contours_sets(emme_ctx_t* ctx, int nitems, const int* set, const emme_contour_t* contours,
+                                          int exact, double tol, int step_limit, int max_roots, double* roots,
+                                          double* vecs, double* resid, int* iters, int* info, int* n_roots, int* winding,
+                                          int* points_used, int* status);
 
 /* The reference's driver (src/main.cpp:182-338) on an input.json TEXT: one solve, or a
  * parameter scan over every key written {head, step, tail}, with omega continuation.
