@@ -541,6 +541,24 @@ def _c128(a, shape=None):
     return a if shape is None else a.reshape(shape)
 
 
+def _operand_pair(A, B, a_device_ptr, b_device_ptr, copy=False):
+    """The two matrix operands of a linear-algebra call as (pointer A, pointer B, nbatch, n, keep-alive): host arrays
+    [nbatch, n, n] (or one [n, n] matrix each) as they are (copy: private copies, for a call that destroys them), or
+    with a_device_ptr / b_device_ptr that operand in device memory -- then A = (nbatch, n) if both are, and the
+    argument of the device operand is not looked at otherwise."""
+    host = [None if p is not None else _c128(X) for X, p in ((A, a_device_ptr), (B, b_device_ptr))]
+    host = [None if h is None else np.ascontiguousarray(h[None] if h.ndim == 2 else h) for h in host]
+    if copy:
+        host = [None if h is None else h.copy() for h in host]
+    first = next((h for h in host if h is not None), None)
+    nb, n = (first.shape[0], first.shape[1]) if first is not None else (int(A[0]), int(A[1]))
+    for h in host:
+        if h is not None and h.shape != (nb, n, n):
+            raise ValueError("the operands must be [nbatch, n, n] of one shape")
+    ptrs = [h.ctypes.data if h is not None else C.c_void_p(p) for h, p in zip(host, (a_device_ptr, b_device_ptr))]
+    return ptrs[0], ptrs[1], nb, n, host
+
+
 class Context:
     """One (device, parameter set): owns device tables and batch scratch."""
 
@@ -714,16 +732,24 @@ class Context:
                                             C.c_void_p(out_device_ptr), iv.ctypes.data))
         return iv
 
-    def assemble_derivative(self, omegas, want_intervals=False):
+    def assemble_derivative(self, omegas, want_intervals=False, omega_device_ptr: int | None = None,
+                            out_device_ptr: int | None = None, mp_device_ptr: int | None = None):
         """M(omega) and the exact M'(omega) of the same quadrature trees, through the uncached kernels
         (option deriv_cached = 1: through the node cache where the context has the tiled one; with tile_uncached = 1
-        as well, through the table-free tile fill where there is no cache to read): returns (M, Mp[, intervals])."""
-        w = _c128(np.atleast_1d(omegas))
-        nb = w.shape[0]
+        as well, through the table-free tile fill where there is no cache to read): returns (M, Mp[, intervals]).
+        omega_device_ptr: the omegas in device memory (omegas is then the batch size); out_device_ptr / mp_device_ptr:
+        M / Mp go to device memory (the header wants both on one side) and come back as None."""
+        if omega_device_ptr is not None:
+            nb, wp = int(omegas), C.c_void_p(omega_device_ptr)
+        else:
+            w = _c128(np.atleast_1d(omegas))
+            nb, wp = w.shape[0], w.ctypes.data
         iv = np.zeros(nb, dtype=np.int64)
-        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
-        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
-        _check(self.lib.emme_assemble_derivative_batch(self.h, w.ctypes.data, nb, M.ctypes.data, Mp.ctypes.data,
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if out_device_ptr is None else None
+        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if mp_device_ptr is None else None
+        _check(self.lib.emme_assemble_derivative_batch(self.h, wp, nb,
+                                                       M.ctypes.data if M is not None else C.c_void_p(out_device_ptr),
+                                                       Mp.ctypes.data if Mp is not None else C.c_void_p(mp_device_ptr),
                                                        iv.ctypes.data))
         return (M, Mp, iv) if want_intervals else (M, Mp)
 
@@ -733,45 +759,46 @@ class Context:
         M = np.zeros((w.shape[0], self.dim, self.dim), dtype=np.complex128)
         return self.lib.emme_assemble_batch(self.h, w.ctypes.data, w.shape[0], M.ctypes.data, None)
 
-    def trace_solve(self, A, B):
-        A = _c128(A).copy()
-        B = _c128(B).copy()
-        if A.ndim == 2:
-            A, B = A[None], B[None]
-        nb, n, _ = A.shape
+    def trace_solve(self, A, B, a_device_ptr: int | None = None, b_device_ptr: int | None = None):
+        """tr(A_b^-1 B_b) and info per item (emme_trace_solve_batch) on private copies of A and B; a_device_ptr /
+        b_device_ptr: that operand in device memory, where the call destroys it (both: A = (nbatch, n))."""
+        pa, pb, nb, n, _keep = _operand_pair(A, B, a_device_ptr, b_device_ptr, copy=True)
         tr = np.zeros(nb, dtype=np.complex128)
         info = np.zeros(nb, dtype=np.int32)
-        _check(self.lib.emme_trace_solve_batch(self.h, n, nb, A.ctypes.data, B.ctypes.data,
-                                               tr.ctypes.data, info.ctypes.data))
+        _check(self.lib.emme_trace_solve_batch(self.h, n, nb, pa, pb, tr.ctypes.data, info.ctypes.data))
         return tr, info
 
     # the linear algebra of newtonQRSecantIteration (include/solver.h:244-370): q with
     # domega = -1/q, for arbitrary square A (= M) and B (= M')
-    def qr_secant(self, A, B):
-        A = _c128(A)
-        B = _c128(B)
-        if A.ndim == 2:
-            A, B = A[None], B[None]
-        A, B = np.ascontiguousarray(A), np.ascontiguousarray(B)
-        nb, n, _ = A.shape
+    def qr_secant(self, A, B, a_device_ptr: int | None = None, b_device_ptr: int | None = None):
+        """(a_device_ptr / b_device_ptr: that operand in device memory; both: A = (nbatch, n))"""
+        pa, pb, nb, n, _keep = _operand_pair(A, B, a_device_ptr, b_device_ptr)
         q = np.zeros(nb, dtype=np.complex128)
         info = np.zeros(nb, dtype=np.int32)
-        _check(self.lib.emme_qr_secant_batch(self.h, n, nb, A.ctypes.data, B.ctypes.data,
-                                             q.ctypes.data, info.ctypes.data))
+        _check(self.lib.emme_qr_secant_batch(self.h, n, nb, pa, pb, q.ctypes.data, info.ctypes.data))
         return q, info
 
     # newtonTraceSecantIteration / newtonQRSecantIteration (include/solver.h:113-160, 210-383),
     # batched; method: 0 trace-secant, 1 QR-secant
-    def newton_step(self, omegas, M, Mp, method=0):
-        w = _c128(np.atleast_1d(omegas)).copy()
-        nb = w.shape[0]
-        M = _c128(M, (nb, self.dim, self.dim)).copy()
-        Mp = _c128(Mp, (nb, self.dim, self.dim)).copy()
-        dw = np.zeros(nb, dtype=np.complex128)
-        info = np.zeros(nb, dtype=np.int32)
-        _check(self.lib.emme_newton_step_batch(self.h, w.ctypes.data, dw.ctypes.data, nb,
-                                               M.ctypes.data, Mp.ctypes.data, method,
-                                               info.ctypes.data))
+    def newton_step(self, omegas, M, Mp, method=0, omega_device_ptr: int | None = None,
+                    domega_device_ptr: int | None = None, m_device_ptr: int | None = None,
+                    mp_device_ptr: int | None = None, info_device_ptr: int | None = None):
+        """Returns (omega, domega, M, Mp, info) after the step.  *_device_ptr: that array in device memory, updated in
+        place (the header wants all five on one side) -- its argument is not looked at and it comes back as None;
+        with omega_device_ptr, omegas is the batch size."""
+        if omega_device_ptr is not None:
+            w, nb = None, int(omegas)
+        else:
+            w = _c128(np.atleast_1d(omegas)).copy()
+            nb = w.shape[0]
+        M = None if m_device_ptr is not None else _c128(M, (nb, self.dim, self.dim)).copy()
+        Mp = None if mp_device_ptr is not None else _c128(Mp, (nb, self.dim, self.dim)).copy()
+        dw = None if domega_device_ptr is not None else np.zeros(nb, dtype=np.complex128)
+        info = None if info_device_ptr is not None else np.zeros(nb, dtype=np.int32)
+        p = [a.ctypes.data if a is not None else C.c_void_p(d)
+             for a, d in ((w, omega_device_ptr), (dw, domega_device_ptr), (M, m_device_ptr), (Mp, mp_device_ptr),
+                          (info, info_device_ptr))]
+        _check(self.lib.emme_newton_step_batch(self.h, p[0], p[1], nb, p[2], p[3], method, p[4]))
         return w, dw, M, Mp, info
 
     # solve_once_eigen (src/main.cpp:19-80), batched over initial guesses
@@ -815,19 +842,30 @@ class Context:
     def param_sets(self) -> int:
         return self.lib.emme_ctx_param_sets(self.h)
 
-    def assemble_sets(self, set, omegas, want_derivative=False, want_intervals=False):
+    def assemble_sets(self, set, omegas, want_derivative=False, want_intervals=False,
+                      omega_device_ptr: int | None = None, out_device_ptr: int | None = None,
+                      mp_device_ptr: int | None = None):
         """M(omega_b) of the bound parameter set set[b], one launch for the batch: returns M[, Mp][, intervals]
-        (Mp: the exact dM/domega of the same quadrature trees)."""
-        w = _c128(np.atleast_1d(omegas))
-        nb = w.shape[0]
+        (Mp: the exact dM/domega of the same quadrature trees).  omega_device_ptr: the omegas in device memory (omegas is
+        not looked at); out_device_ptr / mp_device_ptr: M / Mp go to device memory and come back as None
+        (mp_device_ptr asks for the derivative)."""
         st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
-        if st.shape[0] != nb:
-            raise ValueError("set needs one entry per omega")
+        nb = st.shape[0]
+        if omega_device_ptr is not None:
+            wp = C.c_void_p(omega_device_ptr)
+        else:
+            w = _c128(np.atleast_1d(omegas))
+            wp = w.ctypes.data
+            if w.shape[0] != nb:
+                raise ValueError("set needs one entry per omega")
+        want_derivative = want_derivative or mp_device_ptr is not None
         iv = np.zeros(nb, dtype=np.int64)
-        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
-        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if want_derivative else None
-        _check(self.lib.emme_assemble_sets_batch(self.h, st.ctypes.data, w.ctypes.data, nb, M.ctypes.data,
-                                                 Mp.ctypes.data if want_derivative else None, iv.ctypes.data))
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if out_device_ptr is None else None
+        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128) if want_derivative and mp_device_ptr is None else None
+        mpp = C.c_void_p(mp_device_ptr) if mp_device_ptr is not None else (Mp.ctypes.data if want_derivative else None)
+        _check(self.lib.emme_assemble_sets_batch(self.h, st.ctypes.data, wp, nb,
+                                                 M.ctypes.data if M is not None else C.c_void_p(out_device_ptr), mpp,
+                                                 iv.ctypes.data))
         out = (M, Mp) if want_derivative else (M,)
         if want_intervals:
             out = out + (iv,)
@@ -885,19 +923,13 @@ class Context:
                       resid.ctypes.data, iters.ctypes.data, info.ctypes.data, its.ctypes.data if want_iterates else None))
         return (roots, vecs, resid, iters, info, its) if want_iterates else (roots, vecs, resid, iters, info)
 
-    def eigenpair_secant_step(self, M, M_old, domega, v=None):
+    def eigenpair_secant_step(self, M, M_old, domega, v=None, m_device_ptr: int | None = None,
+                              m_old_device_ptr: int | None = None):
         """One secant eigenpair step on caller matrices (emme_eigenpair_secant_step_batch): u = M^-1 (M - M_old) v /
         domega with the difference taken per entry, tau = v^H u (the next domega = -1/tau), resid = |M v| / |M|_F before
         the step.  domega [nbatch]: the step between the two fills.  v None: as eigenpair_step.  Returns (u / |u|, tau,
-        resid, info)."""
-        M = _c128(M)
-        M_old = _c128(M_old)
-        if M.ndim == 2:
-            M, M_old = M[None], M_old[None]
-        M, M_old = np.ascontiguousarray(M), np.ascontiguousarray(M_old)
-        nb, n = M.shape[0], M.shape[1]
-        if M.shape != (nb, n, n) or M_old.shape != M.shape:
-            raise ValueError("M and M_old must be [nbatch, n, n]")
+        resid, info).  m_device_ptr / m_old_device_ptr: that matrix operand in device memory (both: M = (nbatch, n))."""
+        pm, pmo, nb, n, _keep = _operand_pair(M, M_old, m_device_ptr, m_old_device_ptr)
         dw = np.ascontiguousarray(_c128(np.atleast_1d(domega)))
         if dw.shape != (nb,):
             raise ValueError("domega needs one entry per matrix")
@@ -910,23 +942,17 @@ class Context:
         tau = np.zeros(nb, dtype=np.complex128)
         resid = np.zeros(nb, dtype=np.float64)
         info = np.zeros(nb, dtype=np.int32)
-        _check(self.lib.emme_eigenpair_secant_step_batch(self.h, n, nb, M.ctypes.data, M_old.ctypes.data, dw.ctypes.data,
+        _check(self.lib.emme_eigenpair_secant_step_batch(self.h, n, nb, pm, pmo, dw.ctypes.data,
                                                          vv.ctypes.data, 0 if v is None else 1, tau.ctypes.data,
                                                          resid.ctypes.data, info.ctypes.data))
         return vv, tau, resid, info
 
-    def eigenpair_step(self, M, Mp, v=None):
+    def eigenpair_step(self, M, Mp, v=None, m_device_ptr: int | None = None, mp_device_ptr: int | None = None):
         """One eigenpair step on caller matrices (emme_eigenpair_step_batch): u = M^-1 Mp v, tau = v^H u (domega = -1/tau),
         resid = |M v| / |M|_F before the step.  v None: the step starts from M^-1 s / |M^-1 s| (include/emme_hip.h).
-        Returns (u / |u|, tau, resid, info)."""
-        M = _c128(M)
-        Mp = _c128(Mp)
-        if M.ndim == 2:
-            M, Mp = M[None], Mp[None]
-        M, Mp = np.ascontiguousarray(M), np.ascontiguousarray(Mp)
-        nb, n = M.shape[0], M.shape[1]
-        if M.shape != (nb, n, n) or Mp.shape != M.shape:
-            raise ValueError("M and Mp must be [nbatch, n, n]")
+        Returns (u / |u|, tau, resid, info).  m_device_ptr / mp_device_ptr: that matrix operand in device memory (both:
+        M = (nbatch, n))."""
+        pm, pmp, nb, n, _keep = _operand_pair(M, Mp, m_device_ptr, mp_device_ptr)
         if v is None:
             vv = np.zeros((nb, n), dtype=np.complex128)
         else:
@@ -936,16 +962,19 @@ class Context:
         tau = np.zeros(nb, dtype=np.complex128)
         resid = np.zeros(nb, dtype=np.float64)
         info = np.zeros(nb, dtype=np.int32)
-        _check(self.lib.emme_eigenpair_step_batch(self.h, n, nb, M.ctypes.data, Mp.ctypes.data, vv.ctypes.data,
+        _check(self.lib.emme_eigenpair_step_batch(self.h, n, nb, pm, pmp, vv.ctypes.data,
                                                   0 if v is None else 1, tau.ctypes.data, resid.ctypes.data,
                                                   info.ctypes.data))
         return vv, tau, resid, info
 
-    def null_vectors(self, M=None, nbatch=None):
+    def null_vectors(self, M=None, nbatch=None, device_ptr: int | None = None):
         """nullSpace (include/solver.h:58-112) on the device, batched: right singular vector of the smallest
-        singular value of every matrix.  M = None: the matrices M(omega_final) of the last solve_roots call.
+        singular value of every matrix.  M = None: the matrices M(omega_final) of the last solve_roots call;
+        device_ptr: the matrices in device memory, M = (nbatch, n).
         Returns (vectors [nbatch, n], info [nbatch])."""
-        if M is None:
+        if device_ptr is not None:
+            (nb, n), ptr = M, C.c_void_p(device_ptr)
+        elif M is None:
             n, nb, ptr = self.dim, nbatch, None
         else:
             M = _c128(M)
@@ -1006,19 +1035,25 @@ class Context:
                                                    A0.ctypes.data, A1.ctypes.data, ld.ctypes.data, info.ctypes.data))
         return A0, A1, ld, info
 
-    def contour_moments_groups(self, M, group, ngroups, z, w, L, V=None):
+    def contour_moments_groups(self, M, group, ngroups, z, w, L, V=None, device_ptr: int | None = None,
+                               v_device_ptr: int | None = None):
         """contour_moments with the matrices dealt into ngroups groups (group[j] in [0, ngroups), any order): returns
         (A0, A1, logdet, info) with A0, A1 of shape [ngroups, n, L], group g summed over its matrices in ascending j
-        (info != 0 left out, an empty group zero)."""
-        M = np.ascontiguousarray(_c128(M))
-        nq, n = M.shape[0], M.shape[1]
+        (info != 0 left out, an empty group zero).  device_ptr / v_device_ptr as in contour_moments."""
+        if device_ptr is None:
+            M = np.ascontiguousarray(_c128(M))
+            nq, n = M.shape[0], M.shape[1]
+            ptr = M.ctypes.data
+        else:
+            nq, n = M
+            ptr = C.c_void_p(device_ptr)
         g = np.ascontiguousarray(np.atleast_1d(group), dtype=np.int32)
         z = _c128(np.atleast_1d(z))
         w = _c128(np.atleast_1d(w))
         if g.shape[0] != nq or z.shape[0] != nq or w.shape[0] != nq:
             raise ValueError("group, z and w need one entry per matrix")
-        Vp = None
-        if V is not None:
+        Vp = None if v_device_ptr is None else C.c_void_p(v_device_ptr)
+        if V is not None and v_device_ptr is None:
             V = np.ascontiguousarray(_c128(V))
             if V.shape != (n, L):
                 raise ValueError("V must be n x L")
@@ -1027,7 +1062,7 @@ class Context:
         A1 = np.zeros((max(ngroups, 0), n, L), dtype=np.complex128)
         ld = np.zeros(nq, dtype=np.complex128)
         info = np.zeros(nq, dtype=np.int32)
-        _check(self.lib.emme_contour_moments_groups(self.h, n, nq, M.ctypes.data, g.ctypes.data, ngroups, z.ctypes.data,
+        _check(self.lib.emme_contour_moments_groups(self.h, n, nq, ptr, g.ctypes.data, ngroups, z.ctypes.data,
                                                     w.ctypes.data, L, Vp, A0.ctypes.data, A1.ctypes.data, ld.ctypes.data,
                                                     info.ctypes.data))
         return A0, A1, ld, info

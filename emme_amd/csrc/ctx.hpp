@@ -237,6 +237,8 @@ void dev_params_from(const emme_params_t* p, DevParams& P, std::vector<double>& 
 bool is_device_ptr(const void* p);
 // *dev <- a and b are device pointers; EMME_EINVAL ("<names> must both be ...") if only one of them is
 int same_side(const void* a, const void* b, const char* names, bool* dev);
+// the same for n arrays: EMME_EINVAL ("<names> must all be ...") unless every one is on the side of the first
+int same_side_all(const void* const* ptrs, int n, const char* names, bool* dev);
 // bytes of nbatch complex n x n matrices
 inline size_t batch_bytes(int n, int nbatch) { return (size_t)n * n * 2 * sizeof(double) * nbatch; }
 // a call over parameter sets: EMME_EINVAL unless sets are bound and every set[b] names one; the indices into c->d_set

@@ -424,9 +424,11 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
     if (!c || !omega || !domega || !M || !Mp || !info || nbatch < 1) return EMME_EINVAL;
     EMME_TRY(check_method(c, method));
     HIP_TRY(hipSetDevice(c->device));
-    EMME_TRY(ensure_batch(c, nbatch));
+    // (every copy kind below follows from this one side)
     bool dev = false;
-    EMME_TRY(same_side(M, Mp, "M and Mp", &dev));
+    const void* const arrays[5] = {omega, domega, M, Mp, info};
+    EMME_TRY(same_side_all(arrays, 5, "emme_newton_step_batch: omega, domega, M, Mp and info", &dev));
+    EMME_TRY(ensure_batch(c, nbatch));
     const size_t mbytes = batch_bytes(c->dim, nbatch);
     EMME_TRY(ensure_mats(c, nbatch, dev ? (2 | 8) : (1 | 2 | 4 | 8)));
     double *dM = M, *dMp = Mp;
@@ -435,8 +437,8 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
         HIP_TRY(hipMemcpyAsync(dM, M, mbytes, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(hipMemcpyAsync(dMp, Mp, mbytes, hipMemcpyHostToDevice, c->stream));
     }
-    const hipMemcpyKind in_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    const hipMemcpyKind out_kind = is_device_ptr(omega) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
+    const hipMemcpyKind in_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    const hipMemcpyKind out_kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost;
     EMME_TRY(upload_omega(c, omega, nbatch, in_kind));
     EMME_TRY(reset_fill_counters(c, nbatch));
     {
@@ -469,8 +471,7 @@ int emme_newton_step_batch(emme_ctx_t* c, double* omega, double* domega, int nba
     HIP_TRY(hipMemcpyAsync(domega, c->d_domega, sizeof(double) * 2 * nbatch, out_kind, c->stream));
     std::vector<unsigned long long> iv;
     EMME_TRY(queue_fill_counters(c, nbatch, iv, nullptr));  // (the status flags are not this call's to report)
-    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch,
-                           is_device_ptr(info) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch, out_kind, c->stream));
     HIP_TRY(hipStreamSynchronize(c->stream));
     (void)fold_fill_counters(c, iv, nullptr);
     return EMME_OK;

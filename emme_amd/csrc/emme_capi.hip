@@ -178,6 +178,16 @@ int same_side(const void* a, const void* b, const char* names, bool* dev) {
     return EMME_EINVAL;
 }
 
+int same_side_all(const void* const* ptrs, int n, const char* names, bool* dev) {
+    *dev = is_device_ptr(ptrs[0]);
+    for (int k = 1; k < n; ++k)
+        if (is_device_ptr(ptrs[k]) != *dev) {
+            set_error(std::string(names) + " must all be host or all be device pointers");
+            return EMME_EINVAL;
+        }
+    return EMME_OK;
+}
+
 }  // namespace emme
 
 using namespace emme;
@@ -486,6 +496,11 @@ int emme_assemble_batch(emme_ctx_t* c, const double* omega, int nbatch, double* 
                         long long* intervals) {
     if (!c || !omega || !M || nbatch < 1) return EMME_EINVAL;
     HIP_TRY(hipSetDevice(c->device));
+    // (the fill plan reads the omegas on the host: contour classes, cache policy)
+    if (is_device_ptr(omega)) {
+        set_error("emme_assemble_batch: omega must be a host pointer");
+        return EMME_EINVAL;
+    }
     EMME_TRY(ensure_batch(c, nbatch));
     const bool dev_out = is_device_ptr(M);
     double* dM = M;

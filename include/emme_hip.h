@@ -252,14 +252,16 @@ int emme_ctx_cache_state(const emme_ctx_t* ctx, int* full_depth, int* subtrees, 
 int emme_ctx_profile_enable(emme_ctx_t* ctx, int on);
 int emme_ctx_profile_read(emme_ctx_t* ctx, emme_profile_t* out, int reset);
 
-/* Fill M(omega_b) for b < nbatch.  omega: 2*nbatch doubles (host).  M: nbatch*dim*dim
- * complex, row-major, host or device.  intervals (optional, host, nbatch long long):
- * GK intervals evaluated per item. */
+/* Fill M(omega_b) for b < nbatch.  omega: 2*nbatch doubles (host; a device pointer is refused with
+ * EMME_EINVAL before anything is read or queued: the fill is planned on the host from the omegas'
+ * values).  M: nbatch*dim*dim complex, row-major, host or device.  intervals (optional, host,
+ * nbatch long long): GK intervals evaluated per item. */
 int emme_assemble_batch(emme_ctx_t* ctx, const double* omega, int nbatch, double* M,
                         long long* intervals);
 
 /* One trace-secant Newton step per item, in place (all arrays host or device, but
- * consistently one of the two):
+ * consistently one of the two: omega, domega, M, Mp and info are checked together, and a call
+ * that mixes the sides returns EMME_EINVAL before anything is copied or queued):
  *   in : omega[b], M[b] = M(omega[b]), Mp[b] = M'(omega[b])
  *   out: domega[b] = -1/tr(M^-1 M'), omega[b] += domega[b], M[b] = M(new omega),
  *        Mp[b] = (M_new - M_old)/domega, info[b] (LAPACK convention).
