@@ -210,6 +210,9 @@ def load():
                                                         P, P, P, P, P, P, P, P]
         lib.emme_find_eigenpairs_in_contours_sets.argtypes = [P, C.c_int, P, P, C.c_int, C.c_double, C.c_int, C.c_int,
                                                               P, P, P, P, P, P, P, P, P]
+    if hasattr(lib, "emme_root_sensitivities_sets"):  # (an older library loaded through EMME_LIB for an A/B has none)
+        lib.emme_sym_forms_batch.argtypes = [P, C.c_int, C.c_int, P, P, C.c_int, P, C.c_int, P, P, P, P, P, P]
+        lib.emme_root_sensitivities_sets.argtypes = [P, C.c_int, P, P, P, C.c_int, P, P, P, C.c_int, P, P, P, P, P]
     lib.emme_run_json_lockstep.argtypes = [C.c_char_p, C.c_char_p, C.POINTER(C.c_void_p)]
     lib.emme_scan_plan.argtypes = [C.c_char_p, C.c_int, P, P, P, P, C.c_int, P, P, P]
     lib.emme_null_vector.argtypes = [P, C.c_int, P]
@@ -445,6 +448,52 @@ def params_same_shape(a: Params, b: Params) -> bool:
 
 def last_error() -> str:
     return load().emme_last_error().decode()
+
+
+def neighbour_sets(bases, names, rel_step=1e-4):
+    """The parameter sets a root_sensitivities call needs (host only).  bases: one parameter dict or a list of them (all
+    of one shape); names: the parameters to differentiate by.  Returns (params, set, set_plus, set_minus, dp): params is
+    the list of Params to bind -- the bases first, then p (1 + rel_step) and p (1 - rel_step) per base and name (an
+    absolute step of rel_step where p = 0; a whole step of at least 1 for an integer) -- set [nbases] the bases' indices,
+    set_plus / set_minus [nbases, len(names)] those of the neighbours and dp [nbases, len(names)] = p+ - p- as the sets
+    hold it.  A name that changes the shape (npoints, integration_start_points, iteration_method, a beta_e step across
+    0: params_same_shape) is refused with a ValueError."""
+    bases = [bases] if isinstance(bases, dict) else list(bases)
+    names = list(names)
+    if not bases:
+        raise ValueError("neighbour_sets needs at least one base")
+    params = [params_from_dict(d) for d in bases]
+    for k, p in enumerate(params[1:]):
+        if not params_same_shape(params[0], p):
+            raise ValueError(f"base {k + 1} has another shape than base 0: {last_error()}")
+    nb, nn = len(bases), len(names)
+    set_plus = np.zeros((nb, nn), dtype=np.int32)
+    set_minus = np.zeros((nb, nn), dtype=np.int32)
+    dp = np.zeros((nb, nn), dtype=np.float64)
+    for ib, d in enumerate(bases):
+        for k, name in enumerate(names):
+            if name not in d or isinstance(d[name], (str, bool, list, tuple, dict)):
+                raise ValueError(f"{name!r} is not a numeric parameter of base {ib}")
+            p = d[name]
+            if isinstance(p, (int, np.integer)):
+                h = max(1, int(round(abs(p) * rel_step)))
+            else:
+                h = abs(p) * rel_step if p != 0 else rel_step
+            if name == "beta_e" and p != 0 and not (p - h) * (p + h) > 0:
+                raise ValueError(f"a step of 'beta_e' from {p} crosses 0, where the shape changes (base {ib})")
+            sides = []
+            for sign in (1, -1):
+                try:
+                    q = params_from_dict({**d, name: p + sign * h})
+                except EmmeError as e:
+                    raise ValueError(f"a step of {name!r} gives no valid parameter set: {e.reason}") from e
+                if not params_same_shape(params[ib], q):
+                    raise ValueError(f"a step of {name!r} changes the shape of base {ib}: {last_error()}")
+                sides.append(q)
+            set_plus[ib, k], set_minus[ib, k] = len(params), len(params) + 1
+            params += sides
+            dp[ib, k] = float(p + h) - float(p - h)
+    return params, np.arange(nb, dtype=np.int32), set_plus, set_minus, dp
 
 
 def release_pooled_memory() -> None:
@@ -966,6 +1015,82 @@ class Context:
                                                   0 if v is None else 1, tau.ctypes.data, resid.ctypes.data,
                                                   info.ctypes.data))
         return vv, tau, resid, info
+
+    # ---- root sensitivities from eigenpairs ----
+    def sym_forms(self, A, B, vecs, a, b=None, x=None, y=None, a_device_ptr: int | None = None,
+                  b_device_ptr: int | None = None):
+        """Bilinear forms on matrix differences (emme_sym_forms_batch): per item t, form[t] = x^T (A_a - B_b) y (plain
+        transpose) and fro2[t] = |A_a - B_b|_F^2, the difference taken per entry before the product.  A, B: [nmat, n, n]
+        (B None: no second matrix); vecs [nvec, n]; a, b (None, or -1 per item: none), x (None: item t takes vector t),
+        y (None: y = x): index lists.  a_device_ptr / b_device_ptr: the matrices in device memory, A = (nmat, n).
+        Returns (form [nitems] complex, fro2 [nitems])."""
+        if a_device_ptr is not None:
+            nmat, n = int(A[0]), int(A[1])
+            pa = C.c_void_p(a_device_ptr)
+            pb = C.c_void_p(b_device_ptr) if b_device_ptr is not None else None
+            keep = None
+        else:
+            Ah = _c128(A)
+            Ah = np.ascontiguousarray(Ah[None] if Ah.ndim == 2 else Ah)
+            nmat, n = Ah.shape[0], Ah.shape[1]
+            Bh = None
+            if B is not None:
+                Bh = _c128(B)
+                Bh = np.ascontiguousarray(Bh[None] if Bh.ndim == 2 else Bh)
+                if Bh.shape != Ah.shape:
+                    raise ValueError("A and B must be [nmat, n, n] of one shape")
+            pa, pb, keep = Ah.ctypes.data, (Bh.ctypes.data if Bh is not None else None), (Ah, Bh)
+        v = np.ascontiguousarray(_c128(vecs)).reshape(-1, n)
+        ia = np.ascontiguousarray(np.atleast_1d(a), dtype=np.int32)
+        nitems = ia.shape[0]
+        lists = []
+        for idx, default in ((b, None), (x, np.arange(nitems)), (y, None)):
+            idx = default if idx is None else idx
+            if idx is not None:
+                idx = np.ascontiguousarray(np.atleast_1d(idx), dtype=np.int32)
+                if idx.shape != (nitems,):
+                    raise ValueError("a, b, x and y need one entry per item")
+            lists.append(idx)
+        ib, ix, iy = lists
+        form = np.zeros(nitems, dtype=np.complex128)
+        fro2 = np.zeros(nitems, dtype=np.float64)
+        _check(self.lib.emme_sym_forms_batch(self.h, n, nmat, pa, pb, v.shape[0], v.ctypes.data, nitems, ia.ctypes.data,
+                                             ib.ctypes.data if ib is not None else None, ix.ctypes.data,
+                                             iy.ctypes.data if iy is not None else None, form.ctypes.data,
+                                             fro2.ctypes.data))
+        del keep
+        return form, fro2
+
+    def root_sensitivities(self, set, roots, vecs, set_plus, set_minus, dp, max_items=0):
+        """d omega / d p of eigenpairs over bound parameter sets (emme_root_sensitivities_sets): root r is the eigenpair
+        (roots[r], vecs[r]) of bound set set[r], as solve_eigenpairs(set=...) and find_eigenpairs_in_contours_sets return
+        it; direction k is the pair of bound sets set_plus[r, k], set_minus[r, k] at parameter distance dp[r, k]
+        (neighbour_sets builds all of it).  Returns (dwdp [nroots, ndir], denom, corr, cond, info): denom = v^T M' v,
+        corr = -v^T M v / denom (first-order distance to the root), cond = |M|_F |v|^2 / |denom|; info 0, 1 (denom at
+        its rounding level) or EMME_ENUMERIC (a NaN eigenpair or a failed base fill) per root."""
+        st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+        nr = st.shape[0]
+        w = np.ascontiguousarray(_c128(np.atleast_1d(roots)))
+        v = np.ascontiguousarray(_c128(vecs)).reshape(-1, self.dim)
+        if w.shape != (nr,) or v.shape != (nr, self.dim):
+            raise ValueError("roots must be [len(set)] and vecs [len(set), dim]")
+        sp = np.ascontiguousarray(set_plus, dtype=np.int32).reshape(nr, -1)
+        sm = np.ascontiguousarray(set_minus, dtype=np.int32).reshape(nr, -1)
+        d = np.ascontiguousarray(dp, dtype=np.float64).reshape(nr, -1)
+        ndir = sp.shape[1]
+        if sm.shape != (nr, ndir) or d.shape != (nr, ndir):
+            raise ValueError("set_plus, set_minus and dp must be [len(set), ndir]")
+        dwdp = np.zeros((nr, ndir), dtype=np.complex128)
+        denom = np.zeros(nr, dtype=np.complex128)
+        corr = np.zeros(nr, dtype=np.complex128)
+        cond = np.zeros(nr, dtype=np.float64)
+        info = np.zeros(nr, dtype=np.int32)
+        opt = (lambda arr: arr.ctypes.data) if ndir > 0 else (lambda arr: None)
+        _check(self.lib.emme_root_sensitivities_sets(self.h, nr, st.ctypes.data, w.ctypes.data, v.ctypes.data, ndir,
+                                                     opt(sp), opt(sm), opt(d), int(max_items), opt(dwdp),
+                                                     denom.ctypes.data, corr.ctypes.data, cond.ctypes.data,
+                                                     info.ctypes.data))
+        return dwdp, denom, corr, cond, info
 
     def null_vectors(self, M=None, nbatch=None, device_ptr: int | None = None):
         """nullSpace (include/solver.h:58-112) on the device, batched: right singular vector of the smallest

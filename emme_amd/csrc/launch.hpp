@@ -321,6 +321,35 @@ hipError_t launch_eigpair_secant_step(int n, const double* M, const double* Mold
 hipError_t launch_eigpair_resid(int n, const double* M, const int* items, int nitems, const double* vecs, double* resid,
                                 hipStream_t stream);
 
+// ---- bilinear forms on matrix differences (sym_forms.hip) ----------------------------------
+// Item t (a, b, x, y: device lists of nitems; b or B null: no second matrix, y null: y = x): part receives the partial
+// sums of f = x^T (A_a - B_b) y and s = |A_a - B_b|_F^2, the difference taken per entry -- 4 doubles per (item, block of
+// 64 rows), sym_forms_blocks(n, split) blocks per item; launch_sym_forms_finish adds them in index order.  The bits of
+// a result depend on n and the data alone.  split = false: one workgroup per item (one block; other bits), kept for
+// the measurement of the split.  n <= 2048 (hipErrorNotSupported above); A, B, vecs are not modified.
+int sym_forms_blocks(int n, bool split = true);
+hipError_t launch_sym_forms(int n, const double* A, const double* B, const double* vecs, const int* a, const int* b,
+                            const int* x, const int* y, int nitems, double* part, bool split, hipStream_t stream);
+// What k_sym_forms_finish makes of the partial sums (all pointers device):
+//   SYM_FORMS_PLAIN      count items: form[t] (complex), fro2[t] (nullable)
+//   SYM_FORMS_BASE       count roots, root g from the items 2g = (M, v), 2g + 1 = (M', v): with r = root[g] and
+//                        vnorm2[r] = |v|^2, denom[r] = v^T M' v, corr[r] = -v^T M v / denom, cond[r] = |M|_F |v|^2 /
+//                        |denom|, info[r] = 0, 1 (|denom| <= 64 n eps |M'|_F |v|^2: corr NaN) or EMME_ENUMERIC (a
+//                        non-finite form: everything NaN)
+//   SYM_FORMS_NEIGHBOUR  count items, item t = (M+, M-, v) of root r = root[t], output slot q = slot[t]:
+//                        dwdp[q] = -f / (dp[q] denom[r]); NaN where info[r] != 0 or f is not finite
+enum { SYM_FORMS_PLAIN = 0, SYM_FORMS_BASE = 1, SYM_FORMS_NEIGHBOUR = 2 };
+struct SymFormsFinish {
+    int mode, count, nblk, n;
+    const double* part;
+    double *form, *fro2;
+    const int *root, *slot;
+    const double *vnorm2, *dp;
+    double *denom, *corr, *cond, *dwdp;
+    int* info;
+};
+hipError_t launch_sym_forms_finish(const SymFormsFinish& F, hipStream_t stream);
+
 // QR-secant form of the step (linstep_qr.hip, reference include/solver.h:210-383): Wt holds the
 // TRANSPOSE of each matrix (destroyed), Mp the secant derivative (read only); writes
 // tr = t_n / R_nn so that domega = -1/tr = -R_nn / t_n; info = k > 0 when R11(k,k) == 0.

@@ -466,6 +466,64 @@ int emme_solve_eigenpairs_secant(emme_ctx_t* ctx, const int* set /* NULL: the co
                                  int step_limit, double* roots, double* vecs /* n*dim complex */, double* resid /* n */,
                                  int* iters, int* info, double* iterates /* nullable */);
 
+/* ---- root sensitivities from eigenpairs (additions within version 4: find them by symbol lookup) ----
+ * Every fill kernel writes an entry of M(omega; p) together with its mirror, so M = M^T bit for bit (DESIGN.md §5.0c,
+ * §5.5): the left null vector of a root is the conjugate of the right one, v, that the eigenpair searches return, and
+ * for a simple root
+ *     d omega / d p = - v^T (dM/dp) v / (v^T M' v)          (v^T: plain transpose, no conjugation)
+ * with the exact M' = dM/domega of emme_assemble_derivative_batch and dM/dp the difference of two plain fills on
+ * neighbouring parameter sets at the same omega.  No factorisation, no transposed solve, no iteration: the cost of a
+ * call is its fills -- the forms kernel is a single pass over matrices the fills just wrote.  The same forms give
+ *     corr = - v^T M v / (v^T M' v)              the Rayleigh-functional correction: a first-order estimate of the
+ *                                                distance from the returned omega to the root
+ *     cond = |M|_F |v|_2^2 / |v^T M' v|          the eigenvalue condition number: how far a perturbation of M moves omega
+ *
+ * Building block on caller matrices (sym_forms.hip): item t < nitems computes
+ *     form[t] = x^T (A_a - B_b) y   (complex; transpose, not conjugate),    fro2[t] = |A_a - B_b|_F^2
+ * with a = a[t], b = b[t] (-1, or b = NULL: no second matrix), x = x[t], y = y[t] (y = NULL: y = x) -- the difference
+ * taken per entry BEFORE the product, as in emme_eigenpair_secant_step_batch.  A, B: nmat*n*n complex, row-major, both
+ * host or both device, not modified; vecs: host, nvec*n complex; a, b, x, y: host, their ranges ([0, nmat), b also -1,
+ * [0, nvec)) checked.  form: host, nitems complex; fro2: host, nitems, nullable.  Symmetry is not assumed.  The bits of
+ * a result depend on n and the data alone -- not on which items share a call or on the device's size -- and two calls
+ * give the same bits.  n <= 2048 (EMME_ECONFIG above); all pointer and range checks (EMME_EINVAL) come before the
+ * device is looked for. */
+int emme_sym_forms_batch(emme_ctx_t* ctx, int n, int nmat, const double* A, const double* B /* nullable */,
+                         int nvec, const double* vecs /* host, nvec*n complex */, int nitems, const int* a,
+                         const int* b /* nullable: none */, const int* x, const int* y /* nullable: y = x */,
+                         double* form /* host, nitems complex */, double* fro2 /* host, nitems; nullable */);
+/* d omega / d p of nroots eigenpairs over bound parameter sets (emme_ctx_bind_param_sets).
+ *   set, roots, vecs   root r is the eigenpair (roots[r], vecs[r*dim ..]) of bound set set[r], exactly as
+ *                      emme_solve_eigenpairs / emme_solve_eigenpairs_secant (with `set`) and
+ *                      emme_find_eigenpairs_in_contours_sets return them: their outputs can be passed straight through.
+ *                      The vector need not have unit norm (the quotients do not depend on it).
+ *   ndir, set_plus, set_minus, dp
+ *                      direction k < ndir of root r is the pair of bound sets set_plus[r*ndir+k], set_minus[r*ndir+k],
+ *                      filled at omega_r, and dp[r*ndir+k] = p+ - p-, the parameter distance between them (non-zero and
+ *                      finite, else EMME_EINVAL).  The sets may differ in any continuous parameters: the direction is
+ *                      whatever the caller made of it.  One-sided differences (set_minus = set[r]) and a scan line's
+ *                      own neighbours (sets i-1 and i+1 around point i) are legal.  ndir = 0: only denom, corr, cond.
+ *   max_items          cap of the matrices held at once (0: automatic, 1 GiB of matrices, at least 2 and at most
+ *                      4096).  A cap of 1 is rounded up to one pair's two matrices, an odd cap down to whole pairs.
+ *                      The neighbour fills run in chunks of whole (root, direction) pairs under the cap; the outputs
+ *                      do not depend on it.
+ *   dwdp               host, nroots*ndir complex;   denom[r] = v^T M' v, corr[r], cond[r] as above (host)
+ *   info[r]            0;  1: |v^T M' v| <= 64 dim eps |M'|_F |v|^2, the form is at its own rounding level -- a multiple
+ *                      or defective root, or not an eigenvector: dwdp and corr NaN, denom and cond still returned;
+ *                      EMME_ENUMERIC: a NaN (non-finite) root or vector row -- the blanked output of a failed chain --
+ *                      or a base fill that failed: every output of THAT root NaN, the others untouched.
+ * A neighbour fill that fails makes only its dwdp entry NaN.  A vector that is merely not an eigenvector of a simple
+ * root is NOT caught by info (it stays 0): corr, of the size of the distance to the root, and the search's resid tell.
+ * Method: one derivative fill over sets for M, M' at (set[r], omega_r), plain fills over sets for the neighbour
+ * matrices, routed exactly as emme_assemble_sets_batch routes them; one k_sym_forms launch per chunk and
+ * k_sym_forms_finish, which forms the quotients on the device.  No option is consulted or changed beyond what
+ * emme_assemble_sets_batch does: afterwards emme_ctx_get_mirror_pairs, the options and the binding are what they were.
+ * EMME_EINVAL, all before the device is looked for: NULL ctx / set / roots / vecs / denom / corr / cond / info (with
+ * ndir > 0 also set_plus / set_minus / dp / dwdp), nroots < 1, ndir < 0, max_items < 0, a bad dp, no binding, a set
+ * index out of range, a zero vector row.  EMME_ECONFIG for dim > 2048. */
+int emme_root_sensitivities_sets(emme_ctx_t* ctx, int nroots, const int* set, const double* roots, const double* vecs,
+                                 int ndir, const int* set_plus, const int* set_minus, const double* dp, int max_items,
+                                 double* dwdp, double* denom, double* corr, double* cond, int* info);
+
 /* ---- region search: every root inside a contour (version 4) ---------------------------------------
  * The reference only polishes guesses (src/main.cpp:19-80).  These entry points answer "which modes lie in this part of
  * the omega plane": Beyn's contour-integral method (W.-J. Beyn, Linear Algebra Appl. 436 (2012) 3839-3863, algorithm 1)
