@@ -808,6 +808,43 @@ class Context:
         M = np.zeros((w.shape[0], self.dim, self.dim), dtype=np.complex128)
         return self.lib.emme_assemble_batch(self.h, w.ctypes.data, w.shape[0], M.ctypes.data, None)
 
+    def assemble_raw(self, omegas, set=None):
+        """emme_assemble_batch (set given: emme_assemble_sets_batch on the bound sets set[b]) without raising on its
+        return code: (rc, M, intervals).  The library copies every matrix and interval count out before it returns
+        EMME_ENUMERIC, so the items beside a lost one are there to be read."""
+        w = _c128(np.atleast_1d(omegas))
+        nb = w.shape[0]
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        iv = np.zeros(nb, dtype=np.int64)
+        if set is None:
+            rc = self.lib.emme_assemble_batch(self.h, w.ctypes.data, nb, M.ctypes.data, iv.ctypes.data)
+        else:
+            st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+            if st.shape[0] != nb:
+                raise ValueError("set needs one entry per omega")
+            rc = self.lib.emme_assemble_sets_batch(self.h, st.ctypes.data, w.ctypes.data, nb, M.ctypes.data, None,
+                                                   iv.ctypes.data)
+        return rc, M, iv
+
+    def assemble_derivative_raw(self, omegas, set=None):
+        """The derivative twin of assemble_raw (emme_assemble_derivative_batch, or emme_assemble_sets_batch with Mp):
+        (rc, M, Mp, intervals)."""
+        w = _c128(np.atleast_1d(omegas))
+        nb = w.shape[0]
+        M = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        Mp = np.zeros((nb, self.dim, self.dim), dtype=np.complex128)
+        iv = np.zeros(nb, dtype=np.int64)
+        if set is None:
+            rc = self.lib.emme_assemble_derivative_batch(self.h, w.ctypes.data, nb, M.ctypes.data, Mp.ctypes.data,
+                                                         iv.ctypes.data)
+        else:
+            st = np.ascontiguousarray(np.atleast_1d(set), dtype=np.int32)
+            if st.shape[0] != nb:
+                raise ValueError("set needs one entry per omega")
+            rc = self.lib.emme_assemble_sets_batch(self.h, st.ctypes.data, w.ctypes.data, nb, M.ctypes.data,
+                                                   Mp.ctypes.data, iv.ctypes.data)
+        return rc, M, Mp, iv
+
     def trace_solve(self, A, B, a_device_ptr: int | None = None, b_device_ptr: int | None = None):
         """tr(A_b^-1 B_b) and info per item (emme_trace_solve_batch) on private copies of A and B; a_device_ptr /
         b_device_ptr: that operand in device memory, where the call destroys it (both: A = (nbatch, n))."""

@@ -368,8 +368,8 @@ __global__ __launch_bounds__(256, EMME_CACHED_MIN_WAVES) void k_assemble_cached(
             ++item_intervals;
             // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
             const double dKx = K.x - G.x, dKy = K.y - G.y;
-            const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
-            double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+            const double absK = gk_modulus(K.x, K.y);
+            double err = fmax(gk_modulus(dKx, dKy), absK * (2.0 * 2.220446049250313e-16));
             const cd integral = mk(K.x * scale, K.y * scale);
             err *= scale;
             const double rel_abs = P.rel_tol * (absK * scale);
@@ -850,8 +850,8 @@ __global__ __launch_bounds__(256, 4) void k_assemble_union(AsmCachedArgs A) {
                 // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
                 const double scale = A.scale[cslot];  // (r - l)/2 of the interval: small table, L2-resident
                 const double dKx = K.x - G.x, dKy = K.y - G.y;
-                const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
-                double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+                const double absK = gk_modulus(K.x, K.y);
+                double err = fmax(gk_modulus(dKx, dKy), absK * (2.0 * 2.220446049250313e-16));
                 const cd integral = mk(K.x * scale, K.y * scale);
                 err *= scale;
                 const double rel_abs = P.rel_tol * (absK * scale);

@@ -24,12 +24,12 @@ namespace {
 // numbers in every kernel, so that the flag does not depend on which kernel served the integral.
 constexpr int EMME_MAX_DEPTH = 40;
 constexpr int EMME_MAX_INTERVALS = 1 << 18;
-// Largest modulus of an integral the device path stands for.  The accept/split rule takes |K| and |K - G| as
-// sqrt(x^2 + y^2) and the Newton step's pivot search compares |x|^2: both overflow beyond 1.3e154, so a matrix
-// with a larger entry would be walked on corrupted error estimates and could not be factored anyway.  The
+// Largest modulus of an integral the device path stands for.  The Newton step's pivot search compares |x|^2, which
+// overflows beyond 1.3e154, so a matrix with a larger entry could not be factored anyway.  The
 // reference (std::abs = hypot, LAPACK's scaled arithmetic) goes on to 1e308 -- where, on the headline lattice,
 // its own intermediates overflow first (chain 80's iterate -0.0055-0.734i: entries up to 3e202, two of them
 // inf; its zsysv then fails, include/solver.h:142-153).  Such a matrix is flagged (status -> EMME_ENUMERIC).
+// (The accept/split rule used to overflow as well, and on far smaller matrices: gk_modulus below.)
 constexpr double EMME_MAX_ENTRY = 1e150;
 __device__ __forceinline__ bool kappa_bad(cd k) { return !(fabs(k.x) < EMME_MAX_ENTRY && fabs(k.y) < EMME_MAX_ENTRY); }
 
@@ -46,6 +46,35 @@ struct SqrtExact {
 struct SqrtSeeded {
     static __device__ __forceinline__ double of(double x) { return fsqrt_pos(x); }
 };
+// |x + i y| for the rule: sqrt(x^2 + y^2), the same bits as ever wherever the squares are representable.  They are not
+// from |z| = 1.3e154 on, and the Kronrod sum of ONE interval gets there long before the finished integral reaches
+// EMME_MAX_ENTRY: far below the real axis the integrand is 1e12 times its integral (tokamak example, omega = 0.5-4.9i:
+// nodes of 1.8e156 under an integral of 3e143).  The modulus then came out infinite, `inf > inf` accepted the interval
+// whatever its error, and the integral ended decades off -- flagged only where the wrong value happened to pass
+// EMME_MAX_ENTRY.  The reference takes std::abs = hypot there; here the squares are taken on 2^-520 z (exact) instead.
+// A NaN sum goes the same way and stays NaN.
+// From 2^52 EMME_MAX_ENTRY = 4.5e165 on the modulus is reported infinite as before: an integral that sums such
+// intervals cannot come back below EMME_MAX_ENTRY with one correct bit, so its matrix is lost, and `inf > inf` ends the
+// walk at once instead of refining what nobody will read (the lost matrix of a root search costs what it used to).
+template <class Sqrt = SqrtExact>
+__device__ __forceinline__ double gk_modulus(double x, double y) {
+    const double n2 = fma(x, x, y * y);
+    if (__builtin_expect(n2 <= 1.7976931348623157e308, 1)) return Sqrt::of(n2);
+    const double xs = x * 0x1p-520, ys = y * 0x1p-520;
+    const double m = Sqrt::of(fma(xs, xs, ys * ys));
+    return m >= (EMME_MAX_ENTRY * 0x1p52) * 0x1p-520 ? __builtin_inf() : m * 0x1p520;
+}
+// The rule's two moduli, |K| and |K - G|, behind ONE test: the sum of the two sums of squares is representable exactly
+// when neither needs the rescaled form (a NaN takes it and stays NaN).
+template <class Sqrt = SqrtExact>
+__device__ __forceinline__ void gk_moduli(double kx, double ky, double dx, double dy, double& absK, double& absD) {
+    const double nk = fma(kx, kx, ky * ky), nd = fma(dx, dx, dy * dy);
+    if (__builtin_expect(nk + nd <= 1.7976931348623157e308, 1)) {
+        absK = Sqrt::of(nk), absD = Sqrt::of(nd);
+    } else {
+        absK = gk_modulus<Sqrt>(kx, ky), absD = gk_modulus<Sqrt>(dx, dy);
+    }
+}
 // Does the interval of half-width `scale` at bisection depth `depth`, with Kronrod sum K and Gauss sum G (both
 // before the factor scale), have to be split?  :203-208: err = max(|K - G|, 2 eps |K|) scale; :231-233:
 // |rel * integral|; :237-239: abs_tol is set by the first interval of the integral (the root) and is what the
@@ -55,8 +84,9 @@ template <class Sqrt = SqrtExact>
 __device__ __forceinline__ bool gk_split(cd K, cd G, double scale, double inv_scale, int depth, const DevParams& P,
                                          double& abs_tol) {
     const double dKx = K.x - G.x, dKy = K.y - G.y;
-    const double absK = Sqrt::of(fma(K.x, K.x, K.y * K.y));
-    double err = fmax(Sqrt::of(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+    double absK, absD;
+    gk_moduli<Sqrt>(K.x, K.y, dKx, dKy, absK, absD);
+    double err = fmax(absD, absK * (2.0 * 2.220446049250313e-16));
     err *= scale;
     const double rel_abs = P.rel_tol * (absK * scale);
     if (abs_tol == 0.0) abs_tol = rel_abs;

@@ -686,8 +686,9 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 const int cnt = s_count[wave][r][owner] + 1;
                 s_count[wave][r][owner] = cnt;
                 const double dKx = kx - gx, dKy = ky - gy;
-                const double absK = fsqrt_pos(fma(kx, kx, ky * ky));
-                double err = fmax(fsqrt_pos(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+                double absK, absD;
+                gk_moduli<SqrtSeeded>(kx, ky, dKx, dKy, absK, absD);
+                double err = fmax(absD, absK * (2.0 * 2.220446049250313e-16));
                 err *= scale;
                 const double rel_abs = P.rel_tol * (absK * scale);
                 double at = s_abstol[wave][r][owner];

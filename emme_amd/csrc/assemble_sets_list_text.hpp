@@ -158,8 +158,8 @@ __global__ __launch_bounds__(256, 3) void k_assemble_sets_list(SetsListArgs A) {
             ++item_intervals;
             // (gk_split of assemble_common.hpp, spelled out as in assemble_deriv_list_text.hpp)
             const double dKx = Kx - Gx, dKy = Ky - Gy;
-            const double absK = sqrt(fma(Kx, Kx, Ky * Ky));
-            double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+            const double absK = gk_modulus(Kx, Ky);
+            double err = fmax(gk_modulus(dKx, dKy), absK * (2.0 * 2.220446049250313e-16));
             const cd integral = mk(Kx * scale, Ky * scale);
             err *= scale;
             const double rel_abs = P.rel_tol * (absK * scale);

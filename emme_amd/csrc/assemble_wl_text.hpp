@@ -232,8 +232,8 @@ __global__ __launch_bounds__(256, EMME_WL_MIN_WAVES) void k_assemble_wl(AsmWlArg
 #if EMME_WL_DERIV
                 // (gk_split of assemble_common.hpp, spelled out: calling it here renames registers in this kernel)
                 const double dKx = K.x - G.x, dKy = K.y - G.y;
-                const double absK = sqrt(fma(K.x, K.x, K.y * K.y));
-                double err = fmax(sqrt(fma(dKx, dKx, dKy * dKy)), absK * (2.0 * 2.220446049250313e-16));
+                const double absK = gk_modulus(K.x, K.y);
+                double err = fmax(gk_modulus(dKx, dKy), absK * (2.0 * 2.220446049250313e-16));
                 const cd integral = mk(K.x * scale, K.y * scale);
                 err *= scale;
                 const double rel_abs = P.rel_tol * (absK * scale);
