@@ -177,6 +177,11 @@ def load():
     if hasattr(lib, "emme_ctx_set_mirror_pairs"):  # (an older library loaded through EMME_LIB for an A/B has neither)
         lib.emme_ctx_set_mirror_pairs.argtypes = [P, C.c_int]
         lib.emme_ctx_get_mirror_pairs.argtypes = [P]
+    if hasattr(lib, "emme_ctx_set_lu_fold"):  # (an older library loaded through EMME_LIB for an A/B has none)
+        lib.emme_ctx_set_lu_fold.argtypes = [P, C.c_int]
+        lib.emme_ctx_get_lu_fold.argtypes = [P]
+        lib.emme_ctx_last_folded_steps.argtypes = [P]
+        lib.emme_trace_secant_folded_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P, P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
     lib.emme_ctx_last_deferred.argtypes = [P]
@@ -612,14 +617,18 @@ class Context:
     """One (device, parameter set): owns device tables and batch scratch."""
 
     def __init__(self, params: Params, device: int = -1, **options):
-        """options: fields of emme_options_t (node_cache_gb, cache_min_batch, fill, lu_split, ...)."""
+        """options: fields of emme_options_t (node_cache_gb, cache_min_batch, fill, lu_split, ...); lu_fold (0 / 1): the
+        folded trace-secant step, which is a setter of the context (set_lu_fold)."""
         self.lib = load()
         self.params = params
         h = C.c_void_p()
+        lu_fold = options.pop("lu_fold", None)
         o = default_options(**options)
         _check(self.lib.emme_ctx_create_ex(C.byref(params), device, C.byref(o), C.byref(h)))
         self.h = h
         self.dim = self.lib.emme_ctx_dim(h)
+        if lu_fold is not None:
+            self.set_lu_fold(lu_fold)
 
     def options(self) -> Options:
         o = Options()
@@ -662,6 +671,40 @@ class Context:
         """Fill one pair of every mirror-image couple (i, j) / (N-1-j, N-1-i) on symmetric grids (DESIGN.md §5.0c;
         default on, electrostatic GK15 on the tiled cache only).  A layout setting: rejected once the node cache exists."""
         _check(self.lib.emme_ctx_set_mirror_pairs(self.h, 1 if on else 0))
+
+    def set_lu_fold(self, on) -> None:
+        """The folded trace-secant step (default on): steps of solve_roots whose two fills ran mirrored,
+        on an even order, factor the even and the odd block instead of the matrix.  0: the unfolded step bit for bit."""
+        _check(self.lib.emme_ctx_set_lu_fold(self.h, int(on)))
+
+    def lu_fold(self) -> int:
+        v = self.lib.emme_ctx_get_lu_fold(self.h)
+        if v < 0:
+            _check(v)
+        return v
+
+    def last_folded_steps(self) -> int:
+        """Steps of the last root search that ran folded."""
+        return self.lib.emme_ctx_last_folded_steps(self.h)
+
+    def trace_secant_folded(self, M, M_old, domega, device_ptrs=None):
+        """tr(M_b^-1 (M_b - M_old_b) / domega_b) and info per item by the folded step (emme_trace_secant_folded_batch)
+        for symmetric matrices that are centrosymmetric apart from their last row and column.  device_ptrs = (M, M_old,
+        domega, tr, info) device addresses: all five operands in device memory, M = (nbatch, n); returns None then."""
+        if device_ptrs is not None:
+            nb, n = int(M[0]), int(M[1])
+            _check(self.lib.emme_trace_secant_folded_batch(self.h, n, nb, *[C.c_void_p(int(p)) for p in device_ptrs]))
+            return None
+        M = _c128(M)
+        M = np.ascontiguousarray(M[None] if M.ndim == 2 else M)
+        Mo = _c128(M_old, M.shape)
+        nb, n = M.shape[0], M.shape[1]
+        dw = _c128(np.broadcast_to(np.asarray(domega, dtype=np.complex128), (nb,)))
+        tr = np.zeros(nb, dtype=np.complex128)
+        info = np.zeros(nb, dtype=np.int32)
+        _check(self.lib.emme_trace_secant_folded_batch(self.h, n, nb, M.ctypes.data, Mo.ctypes.data, dw.ctypes.data,
+                                                       tr.ctypes.data, info.ctypes.data))
+        return tr, info
 
     def mirror_pairs(self) -> int:
         """1 if the node cache is (or, before it exists, would be) laid out over the half pair list."""

@@ -128,6 +128,15 @@ struct emme_ctx {
     int n_cu = 256;                // compute units of the device
     int last_lu_nwg = 1;           // workgroups per matrix of the last LU launch
     bool lu_one_wg = false;        // a hand-over of the multi-workgroup LU timed out once: never again
+    // the folded trace-secant step (linstep_fold.hip)
+    int lu_fold = 1;               // emme_ctx_set_lu_fold (EMME_LU_FOLD read at creation)
+    bool last_fill_mirrored = false;  // the last fill() wrote every matrix it was asked for through the mirrored route
+    int last_folded_steps = 0;     // steps of the last root search that ran folded (emme_ctx_last_folded_steps)
+    struct FoldScratch {
+        DeviceBuffer<double> vecs, tr2, part;    // folds of u and u'; traces of the half problems; k_fold_solve's sums
+        DeviceBuffer<int> act2, info2, lu_info, items;
+        DeviceBuffer<> lu_scratch;               // row orders of the second factorisation (launch_lu_inplace)
+    } fold;
     PinnedBuffer<int> p_act;       // pinned host copies of d_active / d_intervals / omega / the deferred
     PinnedBuffer<unsigned long long> p_iv;  // count, WRITTEN BY KERNELS (k_retire, k_newton_update): the
     PinnedBuffer<double> p_w;      // Newton loop reads them after its one synchronisation per step
@@ -265,6 +274,14 @@ int check_method(const emme_ctx* c, int method);
 // all live; work_ready: work holds M already)
 hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double* M, double* work, double* Mp,
                        const int* active, double* tr, int* info, const int* h_active = nullptr, bool work_ready = false);
+// The trace-secant step folded into two half-size problems: whether an order qualifies (the option, an
+// even order, the blocked one-workgroup kernels for n / 2), and the step itself on symmetric matrices that are
+// centrosymmetric apart from their last row and column.  Reads the upper triangles of M and Mold, leaves tr / info of
+// the live chains; Mold_w (nullable): M_old = M there, upper triangle only.  work and Mp hold nbatch n x n matrices each
+// (the half problems' work copies and right-hand sides); h_active: host copy of `active` (null: all live).
+bool fold_applies(const emme_ctx* c, int n);
+int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* work,
+                       double* Mp, const double* domega, const int* active, double* tr, int* info, const int* h_active);
 // scratch of lu_factor_batch that the caller keeps until what it queued behind the factorisation has run
 struct LuScratch {
     DeviceBuffer<double> b;  // dummy right-hand sides of the chunked multi-workgroup factorisation

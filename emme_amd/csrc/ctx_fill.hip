@@ -524,6 +524,7 @@ int fill_by_class(emme_ctx* c, const FillRequest& r, int minority) {
     part.host_active = minor.data(), part.force_uncached = true;
     const int rc = fill(c, part);
     c->last_fill_mode = mode;
+    c->last_fill_mirrored = false;  // (the minority's matrices come from the full pair list)
     return rc;
 }
 
@@ -536,6 +537,7 @@ int fill(emme_ctx* c, const FillRequest& r) {
     const bool has_wide = r.newton_loop && !r.d_Md && !r.d_set && c->tiled && c->nm == 1 && !c->fb.wide.empty();
     const int n_wide = plan_order(r.nbatch, r.host_active, r.cost, has_wide ? c->fb.wide.data() : nullptr, c->h_actidx);
     const int n_act = (int)c->h_actidx.size();
+    c->last_fill_mirrored = false;  // (until every matrix of the request has gone down the mirrored route)
     if (n_act == 0) return EMME_OK;
     if (r.d_set) {
         AssembleLaunch L = make_launch(c, r, false);
@@ -559,6 +561,7 @@ int fill(emme_ctx* c, const FillRequest& r) {
     }
     EMME_TRY(use_cache ? grow_cache_from_deferrals(c, L) : EMME_OK);
     EMME_TRY(use_cache ? fill_cached(c, L, r, n_wide) : fill_uncached(c, L, r));
+    c->last_fill_mirrored = use_cache && L.mirror != 0;
     c->acc.matrices += n_act;
     return EMME_OK;
 }

@@ -102,6 +102,62 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
     return trace_solve(c, n, nbatch, work, Mp, active, tr, info, h_active);
 }
 
+bool fold_applies(const emme_ctx* c, int n) {
+    return c->lu_fold != 0 && n >= 2 && n % 2 == 0 && c->opt.lu_unblocked == 0 &&
+           trace_solve_blocked_lds(n / 2) <= 150 * 1024 && null_iterate_lds(n / 2) <= 150 * 1024;
+}
+
+// The folded step (linstep_fold.hip): the fold pass, then per half problem the trace kernel on [S | S'] and, for the
+// rank-2 part, a second factorisation that keeps its factors (the one-workgroup trace kernel keeps its multipliers in
+// LDS) with two full solves behind it, then the sum per chain.  The first halves of `work` and `Mp` hold what the
+// factorisations destroy, the second halves the copies that are read afterwards.
+int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* work,
+                       double* Mp, const double* domega, const int* active, double* tr, int* info, const int* h_active) {
+    const int m = n / 2, nhalf = 2 * nbatch;
+    emme_ctx::FoldScratch& f = c->fold;
+    HIP_TRY(f.vecs.grow(sizeof(double) * 2 * 4 * (size_t)m * nbatch));
+    HIP_TRY(f.tr2.grow(sizeof(double) * 2 * nhalf));
+    HIP_TRY(f.part.grow(fold_part_bytes(nbatch)));
+    HIP_TRY(f.act2.grow(sizeof(int) * nhalf));
+    HIP_TRY(f.info2.grow(sizeof(int) * nhalf));
+    HIP_TRY(f.lu_info.grow(sizeof(int) * nhalf));
+    HIP_TRY(f.lu_scratch.grow(trace_solve_blocked_scratch(m, nhalf)));
+    const size_t second = (size_t)nbatch * n * n;  // doubles: half of a set of nbatch n x n complex matrices
+    double *S1 = work, *S2 = work + second, *D1 = Mp, *D2 = Mp + second;
+    {
+        ScopedSpan s(c, K_OTHER);
+        HIP_TRY(launch_fold_edges(n, nbatch, M, Mold, domega, active, f.vecs, f.act2, c->stream));
+        HIP_TRY(launch_fold_pass(n, nbatch, M, Mold, Mold_w, S1, S2, D1, D2, domega, active, c->stream));
+    }
+    // the live half problems: host flags for the trace kernel's launch, a device list for the other two
+    std::vector<int> h2;
+    const int* d_items = nullptr;
+    int n_live = nhalf;
+    if (h_active) {
+        h2.resize(nhalf);
+        int* slot = nullptr;
+        HIP_TRY(f.items.grow(sizeof(int) * nhalf));
+        HIP_TRY(c->lists.reserve(nhalf));
+        HIP_TRY(c->lists.take(nhalf, &slot));
+        n_live = 0;
+        for (int b = 0; b < nbatch; ++b) {
+            h2[2 * b] = h2[2 * b + 1] = h_active[b] != 0;
+            if (h_active[b]) slot[n_live++] = 2 * b, slot[n_live++] = 2 * b + 1;
+        }
+        if (n_live == 0) return EMME_OK;
+        HIP_TRY(launch_stage_ints(slot, f.items, n_live, nullptr, 0, c->stream));
+        HIP_TRY(c->lists.read_on(c->stream));
+        d_items = f.items;
+    }
+    ScopedSpan s(c, K_LIN);
+    HIP_TRY(launch_lu_inplace(m, nhalf, S2, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
+    HIP_TRY(trace_solve(c, m, nhalf, S1, D1, f.act2, f.tr2, f.info2, h_active ? h2.data() : nullptr));
+    HIP_TRY(launch_fold_solve(m, S2, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
+                              f.lu_info, D2, f.vecs, f.part, c->stream));
+    HIP_TRY(launch_fold_combine(n, nbatch, active, f.tr2, f.info2, f.lu_info, f.part, tr, info, c->stream));
+    return EMME_OK;
+}
+
 // Partial-pivot LU of nbatch n x n matrices in place (P M = L U, rows never moved; n <= 2048), by the branch the
 // order allows: k_lu_inplace where the whole L21 panel fits one workgroup's LDS; above that, up to n = 1024, the chunked
 // multi-workgroup kernel of the Newton step (two workgroups per matrix, which must be resident together: slices of at
@@ -239,6 +295,55 @@ int emme_trace_solve_batch(emme_ctx_t* c, int n, int nbatch, double* A, double* 
     }
     HIP_TRY(hipMemcpyAsync(tr, c->d_tr, sizeof(double) * 2 * nbatch, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(info, c->d_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
+}
+
+// The folded trace-secant step on caller matrices, whatever the context's lu_fold says
+int emme_trace_secant_folded_batch(emme_ctx_t* c, int n, int nbatch, const double* M, const double* M_old,
+                                   const double* domega, double* tr, int* info) {
+    const char* who = "emme_trace_secant_folded_batch";
+    if (!c || !M || !M_old || !domega || !tr || !info || n < 1 || nbatch < 1) {
+        set_error(std::string(who) + ": a required pointer is NULL, n < 1 or nbatch < 1");
+        return EMME_EINVAL;
+    }
+    if (n % 2 != 0) {
+        set_error(std::string(who) + ": the order must be even");
+        return EMME_EINVAL;
+    }
+    if (trace_solve_blocked_lds(n / 2) > 150 * 1024 || null_iterate_lds(n / 2) > 150 * 1024 || c->opt.lu_unblocked != 0) {
+        set_error(std::string(who) + ": the half problems need the blocked one-workgroup kernels (order above 1050, or lu_unblocked)");
+        return EMME_ECONFIG;
+    }
+    const void* sides[5] = {M, M_old, domega, tr, info};
+    bool dev = false;
+    EMME_TRY(same_side_all(sides, 5, "M, M_old, domega, tr and info", &dev));
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, 2 * nbatch));
+    const size_t bytes = batch_bytes(n, nbatch), cb = sizeof(double) * 2 * nbatch, ib = sizeof(int) * nbatch;
+    DeviceBuffer<double> t_m, t_old, t_dw, t_work, t_mp, t_tr;
+    DeviceBuffer<int> t_info;
+    HIP_TRY(t_work.grow(bytes));
+    HIP_TRY(t_mp.grow(bytes));
+    const double *dM = M, *dOld = M_old, *dDw = domega;
+    double* dTr = tr;
+    int* dInfo = info;
+    if (!dev) {
+        HIP_TRY(t_m.grow(bytes));
+        HIP_TRY(t_old.grow(bytes));
+        HIP_TRY(t_dw.grow(cb));
+        HIP_TRY(t_tr.grow(cb));
+        HIP_TRY(t_info.grow(ib));
+        HIP_TRY(hipMemcpyAsync(t_m, M, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(t_old, M_old, bytes, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(hipMemcpyAsync(t_dw, domega, cb, hipMemcpyHostToDevice, c->stream));
+        dM = t_m, dOld = t_old, dDw = t_dw, dTr = t_tr, dInfo = t_info;
+    }
+    EMME_TRY(folded_secant_step(c, n, nbatch, dM, dOld, nullptr, t_work, t_mp, dDw, nullptr, dTr, dInfo, nullptr));
+    if (!dev) {
+        HIP_TRY(hipMemcpyAsync(tr, t_tr, cb, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(hipMemcpyAsync(info, t_info, ib, hipMemcpyDeviceToHost, c->stream));
+    }
     HIP_TRY(hipStreamSynchronize(c->stream));
     return EMME_OK;
 }

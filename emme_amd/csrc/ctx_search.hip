@@ -47,6 +47,7 @@ int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
         HIP_TRY(hipStreamSynchronize(c->stream));
     }
     s.act.assign(n, 1), s.zeros.assign(n, 0);
+    c->last_folded_steps = 0;
     if (s.set) EMME_TRY(upload_set_indices(c, s.set, n));
     if (s.eigpair) {
         const size_t vbytes = sizeof(double) * 2 * (size_t)n * c->dim;
@@ -163,6 +164,10 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     first.host_omega = w0.data(), first.newton_loop = true;
     search.to(c, first);
     EMME_TRY(fill(c, first));
+    // The folded step needs both matrices of the secant written by mirrored fills for every live
+    // chain: old_mirrored / new_mirrored say so of what d_Mold and d_M hold (a minority class that went through the
+    // omega-lane kernel, or a cache that did not fit, makes a fill unmirrored)
+    bool old_mirrored = c->last_fill_mirrored, new_mirrored = false;
     EMME_TRY(refresh_cost());  // synchronises; the first fill's interval counts order the second
     HIP_TRY(hipMemcpyAsync(c->d_omega, w1.data(), sizeof(double) * 2 * n, hipMemcpyHostToDevice, c->stream));
     // (the fills of a root search write M only: the secant M' = (M - M_old) / d, include/solver.h:157 and :412, is
@@ -171,6 +176,7 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     next.host_omega = w1.data(), next.cost = fb.cost.data(), next.newton_loop = true;
     search.to(c, next);
     EMME_TRY(fill(c, next));
+    new_mirrored = c->last_fill_mirrored;
     next.host_omega = h_w.data(), next.d_active = c->d_active, next.host_active = act.data();  // (the steps' fills)
 
     EMME_TRY(refresh_cost());
@@ -219,6 +225,11 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
             EMME_TRY(eigpair_step(c, search, c->p_live.get(), j == 0 && !search.v0, true));
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_Mold, nullptr, c->d_active, c->stream));
+        } else if (fused_copy && c->mirror && old_mirrored && new_mirrored && fold_applies(c, c->dim)) {
+            // both fills mirrored: the even and the odd block instead of the matrix; M_old follows M in the same pass
+            EMME_TRY(folded_secant_step(c, c->dim, n, c->d_M, c->d_Mold, c->d_Mold, c->d_work, c->d_Mp, c->d_domega,
+                                        c->d_active, c->d_tr, c->d_info, act.data()));
+            ++c->last_folded_steps;
         } else {
             {
                 // the secant M' of the step just taken, then this step's matrix becomes the "previous" one (and the
@@ -246,7 +257,9 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
             for (int b = 0; b < n; ++b) any |= act[b] != 0;
             if (!any) break;  // (this step's LU and update found nothing active: no-ops)
         }
+        old_mirrored = new_mirrored;  // (the step's pass has made M_old of M)
         EMME_TRY(fill(c, next));
+        new_mirrored = c->last_fill_mirrored;
         {
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_retire(n, c->d_active, c->stream, c->p_act, c->d_intervals, c->p_iv,

@@ -317,6 +317,8 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     c->mirror_ok = c->nm == 1 && p->integration_start_points == 15 && grid_is_mirror_symmetric(tab.data(), N, 1e-13);
     // (developer override, read once per context: EMME_MIRROR=0 is emme_ctx_set_mirror_pairs(0))
     if (const char* v = std::getenv("EMME_MIRROR")) c->mirror_opt = std::atoi(v) != 0;
+    // (the same for the folded trace-secant step, DESIGN.md 5.4c: EMME_LU_FOLD=0 is emme_ctx_set_lu_fold(0))
+    if (const char* v = std::getenv("EMME_LU_FOLD")) c->lu_fold = std::atoi(v) != 0;
 
     auto fail = [&](int code) {
         emme_ctx_destroy(c);
@@ -412,6 +414,23 @@ int emme_ctx_get_mirror_pairs(const emme_ctx_t* c) {
     if (!c) return EMME_EINVAL;
     return (c->cache[0].recs || c->cache[1].recs) ? (int)c->mirror : (int)mirror_wanted(c);
 }
+
+int emme_ctx_set_lu_fold(emme_ctx_t* c, int on) {
+    if (!c) {
+        set_error("emme_ctx_set_lu_fold: NULL context");
+        return EMME_EINVAL;
+    }
+    if (on != 0 && on != 1) {
+        set_error("emme_ctx_set_lu_fold: value out of range (0, 1)");
+        return EMME_EINVAL;
+    }
+    c->lu_fold = on;
+    return EMME_OK;
+}
+
+int emme_ctx_get_lu_fold(const emme_ctx_t* c) { return c ? c->lu_fold : EMME_EINVAL; }
+
+int emme_ctx_last_folded_steps(const emme_ctx_t* c) { return c ? c->last_folded_steps : EMME_EINVAL; }
 
 int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* c, int shapes) {
     if (!c) {

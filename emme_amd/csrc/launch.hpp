@@ -280,6 +280,25 @@ hipError_t launch_trace_solve_blocked(int n, int nbatch, double* A, double* B, c
                                       double* tr, int* info, int nwg, const int* items, int nitems,
                                       void* scratch, hipStream_t stream, int group_min_n = 256, int spin_limit = 0);
 
+// ---- the trace-secant step folded into two half-size problems (linstep_fold.hip) ---------
+// For symmetric matrices of even order n = 2m that are centrosymmetric apart from their last row and column.  Half
+// problem 2b is the even (+) block of chain b, 2b + 1 the odd (-) one; all pointers device memory.
+// vecs [nbatch][4][m] complex: the folds of u and u'; act2 [2 nbatch]: the half problems' live flags
+hipError_t launch_fold_edges(int n, int nbatch, const double* M, const double* Mold, const double* domega,
+                             const int* active, double* vecs, int* act2, hipStream_t stream);
+// S1 = S2 = S and D1 = D2 = S' = (S - S_old) / domega of every live chain, [2 nbatch][m][m] each, from the upper
+// triangles of M and Mold; Mold_w (nullable): M_old = M there, upper triangle only.  Runs behind launch_fold_edges.
+hipError_t launch_fold_pass(int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* S1, double* S2,
+                            double* D1, double* D2, const double* domega, const int* active, hipStream_t stream);
+// the rank-2 part of every listed half problem (items: device list of nitems, null = 0 .. nitems-1) from its factors
+// S_lu / rowmaps / nb / lu_info (launch_lu_inplace), S' (Sp) and vecs: part holds fold_part_bytes(nbatch) bytes
+size_t fold_part_bytes(int nbatch);
+hipError_t launch_fold_solve(int m, const double* S_lu, const int* rowmaps, int nb, const int* items, int nitems,
+                             const int* lu_info, const double* Sp, const double* vecs, double* part, hipStream_t stream);
+// tr[b], info[b] of the live chains from tr2 / info2 [2 nbatch] of the trace kernel on [S | S'], lu_info and part
+hipError_t launch_fold_combine(int n, int nbatch, const int* active, const double* tr2, const int* info2, const int* lu_info,
+                               const double* part, double* tr, int* info, hipStream_t stream);
+
 // ---- nullSpace (nullspace.hip): factorisation alone + inverse iteration --------------------------------
 // P A = L U in place (multipliers left of the pivots, rows never moved), no right-hand sides; for orders whose
 // panel fits one workgroup's LDS (hipErrorNotSupported otherwise).  scratch as for launch_trace_solve_blocked.

@@ -221,6 +221,18 @@ int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_E
  * list, or before it exists whether it would be; 0 on every context that is not eligible. */
 int emme_ctx_set_mirror_pairs(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1, cache exists */
 int emme_ctx_get_mirror_pairs(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
+/* The folded trace-secant step (additions within version 4, found by symbol lookup).  Where a context
+ * runs mirrored (above) its matrix is symmetric and, apart from the SingularityHandler's rule for the last row and
+ * column, centrosymmetric: a trace-secant step of emme_solve_roots whose two fills both ran mirrored for every live
+ * chain, on an even order, factors the even and the odd block of order dim / 2 instead of the matrix and adds the
+ * exact rank-2 correction of that rule.  Every other step -- odd order, theta != 0, electromagnetic and GK31 contexts,
+ * the QR method, the Newton, eigenpair, sets and region searches, the step-level entry points -- is what it was.
+ * Option lu_fold: 1 = on, 0 = the unfolded step bit for bit; EMME_LU_FOLD, read at creation, overrides the default.
+ * (emme_options_t has no room left for a field that keeps its size: the option is a setter, as mirror_pairs is.)
+ * Not a layout setting: it may change on a live context, from the next call on. */
+int emme_ctx_set_lu_fold(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1 */
+int emme_ctx_get_lu_fold(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
+int emme_ctx_last_folded_steps(const emme_ctx_t* ctx); /* steps of the last emme_solve_roots that ran folded */
 /* Launch everything on this hipStream_t (e.g. torch's current stream). NULL = default. */
 int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */
@@ -278,6 +290,20 @@ int emme_newton_step_batch(emme_ctx_t* ctx, double* omega, double* domega, int n
  * emme_solve_roots repairs that case itself, the step-level calls report it). */
 int emme_trace_solve_batch(emme_ctx_t* ctx, int n, int nbatch, double* A, double* B, double* tr,
                            int* info);
+
+/* The folded trace-secant step alone: tr[b] = tr(M_b^-1 (M_b - M_old_b) / domega_b) for b < nbatch,
+ * whatever lu_fold says.  THE CALLER PROMISES matrices of the structure the mirrored fills write: M_b and M_old_b
+ * symmetric, and centrosymmetric -- X(i, j) = X(n-1-i, n-1-j) -- apart from their last row and column.  Only the upper
+ * triangles are read, and of them only the wedge between diagonal and anti-diagonal (i <= j <= n-1-i) and the last
+ * column; what the promise says about the rest is taken for granted, not checked.  M, M_old (nbatch*n*n complex,
+ * row-major), domega (nbatch complex), tr (nbatch complex) and info (nbatch ints) are all host or all device
+ * (EMME_EINVAL otherwise); M, M_old and domega are not modified.  info[b]: 0; k > 0: the factorisation of the even
+ * (k <= n/2) or of the odd block (k - n/2) met an exactly zero pivot column; n + 1: the 2 x 2 matrix of the rank-2
+ * correction is singular or not finite; EMME_EDEVICE as emme_trace_solve_batch; tr[b] is NaN for every non-zero info.
+ * The result of an item does not depend on the other items of the call nor on lu_split.  EMME_EINVAL for an odd n;
+ * EMME_ECONFIG for n above 1050 or with lu_unblocked. */
+int emme_trace_secant_folded_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* M_old,
+                                   const double* domega, double* tr, int* info);
 
 /* The QR-secant quotient alone, for any square A_b, B_b (nbatch*n*n complex, row-major, host or
  * device, not modified; n <= 1024): with A P = Q R (Householder QR, LAPACK zgeqp3 pivoting),
