@@ -182,6 +182,12 @@ def load():
         lib.emme_ctx_get_lu_fold.argtypes = [P]
         lib.emme_ctx_last_folded_steps.argtypes = [P]
         lib.emme_trace_secant_folded_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P, P]
+    if hasattr(lib, "emme_ctx_linstep_kernel_symbol"):  # (an older library loaded through EMME_LIB for an A/B has none)
+        lib.emme_ctx_linstep_kernel_symbol.argtypes = [P]
+        lib.emme_ctx_linstep_kernel_symbol.restype = C.c_char_p
+        lib.emme_ctx_last_lu_workgroups.argtypes = [P]
+        lib.emme_ctx_last_lu_slices.argtypes = [P]
+        lib.emme_ctx_compute_units.argtypes = [P]
     lib.emme_ctx_dim.argtypes = [P]
     lib.emme_ctx_fill_mode.argtypes = [P]
     lib.emme_ctx_last_deferred.argtypes = [P]
@@ -784,6 +790,29 @@ class Context:
                 return "k_assemble_tile_shape_sets<%d, %d>" % (pts, 3 if em else 1)
             return "k_assemble_tile_sets"
         return f"k_assemble<{pts}, false>"
+
+    def linstep_kernel_symbol(self) -> str:
+        """Name of the kernel of the context's last LU launch as rocprofv3 prints it ("" before the first): after a
+        trace step k_trace_solve_blocked<false, false> (one workgroup per matrix), k_trace_solve_blocked<true, false>
+        (several), k_trace_solve_grouped, k_trace_solve_blocked<true, true> (chunked panel) or k_trace_solve (unblocked);
+        after the factorisation behind null vectors, eigenpair steps and contour moments k_lu_inplace,
+        k_trace_solve_blocked<true, true> or k_lu_unblocked_inplace.  What was launched, not what was asked for."""
+        s = self.lib.emme_ctx_linstep_kernel_symbol(self.h)
+        if s is None:
+            _check(-1)
+        return s.decode()
+
+    def last_lu_workgroups(self) -> int:
+        """Workgroups per matrix of that launch."""
+        return self.lib.emme_ctx_last_lu_workgroups(self.h)
+
+    def last_lu_slices(self) -> int:
+        """Launches the last batched factorisation was cut into (1 after a trace step)."""
+        return self.lib.emme_ctx_last_lu_slices(self.h)
+
+    def compute_units(self) -> int:
+        """Compute units of the context's device (its properties' multiProcessorCount)."""
+        return self.lib.emme_ctx_compute_units(self.h)
 
     def node_cache_gib(self) -> float:
         return self.lib.emme_ctx_node_cache_gib(self.h)

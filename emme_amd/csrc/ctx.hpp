@@ -127,6 +127,8 @@ struct emme_ctx {
     DeviceBuffer<> d_lu_scratch;   // blocked LU: diagonal of X, hand-over flags, row-map snapshots
     int n_cu = 256;                // compute units of the device
     int last_lu_nwg = 1;           // workgroups per matrix of the last LU launch
+    const char* last_lu_symbol = "";  // ... its kernel (emme_ctx_linstep_kernel_symbol; "": none yet)
+    int last_lu_slices = 0;        // ... and, for lu_factor_batch, the launches its matrices were cut into
     bool lu_one_wg = false;        // a hand-over of the multi-workgroup LU timed out once: never again
     // the folded trace-secant step (linstep_fold.hip)
     int lu_fold = 1;               // emme_ctx_set_lu_fold (EMME_LU_FOLD read at creation)

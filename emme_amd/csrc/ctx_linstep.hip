@@ -9,12 +9,18 @@ using namespace emme;
 
 namespace {
 
+// what the getters report of the context's last LU launch (emme_ctx_linstep_kernel_symbol and its two companions):
+// written together, and only where a launch was made
+void note_lu_launch(emme_ctx* c, const char* symbol, int nwg, int slices) {
+    c->last_lu_symbol = symbol, c->last_lu_nwg = nwg, c->last_lu_slices = slices;
+}
+
 // the Newton linear step: blocked kernel while its panel fits in LDS, else the unblocked one
 // `h_active`: host copy of `active` (null: all live).  With fewer live matrices than compute
 // units each gets several workgroups (lu_workgroups, linstep_plan.hpp).
 hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, const int* active,
                        double* tr, int* info, const int* h_active) {
-    // n <= ~560: the whole L21 panel fits in LDS; up to 1024 the chunked build takes over, which
+    // n <= 525: the whole L21 panel fits in LDS; up to 1024 the chunked build takes over, which
     // needs helper workgroups (>= 2 per matrix, all resident); otherwise the unblocked kernel
     const bool fits = trace_solve_blocked_lds(n) <= 150 * 1024;
     if (c->opt.lu_unblocked == 0 && (fits || n <= 1024)) {
@@ -33,7 +39,6 @@ hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, con
             if (n_live == 0) return hipSuccess;
         }
         const int nwg = lu_workgroups(n, n_live, c->n_cu, c->opt.lu_split, c->lu_one_wg, fits);
-        c->last_lu_nwg = nwg;
         const int* d_items = nullptr;
         if (nwg > 1 && h_active) {
             e = launch_stage_ints(lu_slot, c->d_lu_items, n_live, nullptr, 0, c->stream);
@@ -41,13 +46,19 @@ hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, con
             if (e != hipSuccess) return e;
             d_items = c->d_lu_items;
         }
+        LuRoute route;
         e = launch_trace_solve_blocked(n, nbatch, A, B, active, tr, info, nwg, d_items, n_live, c->d_lu_scratch, c->stream,
-                                       c->opt.lu_group_min_n, c->opt.lu_spin_limit);
-        if (e != hipErrorNotSupported) return e;
+                                       c->opt.lu_group_min_n, c->opt.lu_spin_limit, &route);
+        if (e != hipErrorNotSupported) {
+            // (the launcher itself falls back to one workgroup per matrix where a split grid cannot be resident)
+            if (route.nwg > 0) note_lu_launch(c, route.symbol, route.nwg, 1);
+            return e;
+        }
         (void)hipGetLastError();  // chunked build not possible here (one workgroup per matrix, or no room)
-        c->last_lu_nwg = 1;
     }
-    return launch_trace_solve(n, nbatch, A, B, active, tr, info, c->stream);
+    const hipError_t e = launch_trace_solve(n, nbatch, A, B, active, tr, info, c->stream);
+    if (e == hipSuccess) note_lu_launch(c, LU_SYM_UNBLOCKED, 1, 1);
+    return e;
 }
 
 // The two operands of a linear step where the kernels can read them: A and B themselves if they are device
@@ -183,6 +194,7 @@ int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, 
         const int held = d_items ? nbatch : std::min(nbatch, slice_max);
         HIP_TRY(c->d_lu_scratch.grow(trace_solve_blocked_scratch(n, held)));
         if (!one_wg) HIP_TRY(s.b.grow(mbytes * held));
+        int slices = 0;
         for (int b0 = 0; b0 < todo; b0 += slice_max) {
             const int nb = std::min(slice_max, todo - b0);
             double* a0 = d_items ? work : work + (size_t)b0 * n * n * 2;
@@ -191,15 +203,18 @@ int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, 
             ScopedSpan sp(c, K_NULL);
             if (one_wg) {
                 HIP_TRY(launch_lu_inplace(n, dimb, a0, list, nb, c->d_info, c->d_lu_scratch, c->stream));
+                note_lu_launch(c, LU_SYM_INPLACE, 1, ++slices);
             } else {
                 HIP_TRY(hipMemsetAsync(s.b, 0, mbytes * dimb, c->stream));
+                LuRoute route;
                 const hipError_t e = launch_trace_solve_blocked(n, dimb, a0, s.b, nullptr, c->d_tr, c->d_info, 2, list, nb,
-                                                                c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit);
+                                                                c->d_lu_scratch, c->stream, -1, c->opt.lu_spin_limit, &route);
                 if (e != hipSuccess) {
                     (void)hipGetLastError();
                     set_error(std::string(who) + ": the chunked factorisation could not be launched (its two workgroups per matrix must be resident together)");
                     return EMME_EDEVICE;
                 }
+                note_lu_launch(c, route.symbol, route.nwg, ++slices);
             }
             HIP_TRY(after(b0, nb, trace_solve_rowmaps(c->d_lu_scratch, n, dimb), trace_solve_nb(), c->d_info));
         }
@@ -207,6 +222,7 @@ int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, 
         HIP_TRY(s.maps.grow(sizeof(int) * (size_t)n * nbatch));
         ScopedSpan sp(c, K_NULL);
         HIP_TRY(launch_lu_unblocked_inplace(n, nbatch, work, s.maps, c->d_info, c->stream, d_items, nitems));
+        note_lu_launch(c, LU_SYM_INPLACE_UNBLOCKED, 1, 1);
         HIP_TRY(after(0, todo, s.maps, n, c->d_info));
     }
     return EMME_OK;

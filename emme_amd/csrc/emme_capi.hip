@@ -432,6 +432,14 @@ int emme_ctx_get_lu_fold(const emme_ctx_t* c) { return c ? c->lu_fold : EMME_EIN
 
 int emme_ctx_last_folded_steps(const emme_ctx_t* c) { return c ? c->last_folded_steps : EMME_EINVAL; }
 
+const char* emme_ctx_linstep_kernel_symbol(const emme_ctx_t* c) { return c ? c->last_lu_symbol : nullptr; }
+
+int emme_ctx_last_lu_workgroups(const emme_ctx_t* c) { return c ? c->last_lu_nwg : EMME_EINVAL; }
+
+int emme_ctx_last_lu_slices(const emme_ctx_t* c) { return c ? c->last_lu_slices : EMME_EINVAL; }
+
+int emme_ctx_compute_units(const emme_ctx_t* c) { return c ? c->n_cu : EMME_EINVAL; }
+
 int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* c, int shapes) {
     if (!c) {
         set_error("emme_ctx_set_deriv_cache_shapes: NULL context");

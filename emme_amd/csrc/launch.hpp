@@ -268,17 +268,33 @@ hipError_t launch_secant_copy(int n, int nbatch, const double* M, double* Mold, 
 hipError_t launch_secant_copy_sym(int n, int nbatch, const double* M, double* Mold, double* work, double* Mp,
                                   const double* domega, const int* active, hipStream_t stream);
 
-// Blocked version (linstep_blocked.hip): whole L21 panel in LDS for n <= ~560, in chunks up to 1024.
+// Blocked version (linstep_blocked.hip): whole L21 panel in LDS for n <= 525 (trace_solve_blocked_lds(n) <= 150 KB),
+// in chunks up to 1024.
 // nwg workgroups per matrix (1: one does everything; > 1: one factors A, the others carry B's
 // columns; `items` = device list of the nitems matrices to work on, null for all of them);
 // `scratch` holds trace_solve_blocked_scratch(n, nbatch) bytes.
 size_t trace_solve_blocked_lds(int n);
-size_t trace_solve_chunked_lds(int n);  // 560 < n <= 1024: panel rows in chunks (helper workgroups required;
+size_t trace_solve_chunked_lds(int n);  // 525 < n <= 1024: panel rows in chunks (helper workgroups required;
                                         // the launcher returns hipErrorNotSupported when it cannot)
 size_t trace_solve_blocked_scratch(int n, int nbatch);
+// What an LU launch turned out to be (emme_ctx_linstep_kernel_symbol): the kernel as rocprofv3 prints it and the
+// workgroups each matrix got.  The launcher below decides both itself -- one workgroup per matrix where the grid of a
+// split launch cannot be resident -- and fills it in only where it launches.
+struct LuRoute {
+    const char* symbol = "";
+    int nwg = 0;
+};
+constexpr const char* LU_SYM_BLOCKED_ONE = "k_trace_solve_blocked<false, false>";
+constexpr const char* LU_SYM_BLOCKED_SPLIT = "k_trace_solve_blocked<true, false>";
+constexpr const char* LU_SYM_BLOCKED_CHUNKED = "k_trace_solve_blocked<true, true>";
+constexpr const char* LU_SYM_GROUPED = "k_trace_solve_grouped";
+constexpr const char* LU_SYM_UNBLOCKED = "k_trace_solve";
+constexpr const char* LU_SYM_INPLACE = "k_lu_inplace";
+constexpr const char* LU_SYM_INPLACE_UNBLOCKED = "k_lu_unblocked_inplace";
 hipError_t launch_trace_solve_blocked(int n, int nbatch, double* A, double* B, const int* active,
                                       double* tr, int* info, int nwg, const int* items, int nitems,
-                                      void* scratch, hipStream_t stream, int group_min_n = 256, int spin_limit = 0);
+                                      void* scratch, hipStream_t stream, int group_min_n = 256, int spin_limit = 0,
+                                      LuRoute* route = nullptr);
 
 // ---- the trace-secant step folded into two half-size problems (linstep_fold.hip) ---------
 // For symmetric matrices of even order n = 2m that are centrosymmetric apart from their last row and column.  Half

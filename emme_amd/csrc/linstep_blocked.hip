@@ -2,7 +2,7 @@
 // for the unblocked reference version and the algorithmic notes).
 //
 // One workgroup (1024 threads) per batch item -- or several, see "several workgroups per matrix"
-// below; n <= ~560 with the whole L21 panel in LDS, up to 1024 in chunks (CHUNK) -- block size NB = 16:
+// below; n <= 525 with the whole L21 panel in LDS, up to 1024 in chunks (CHUNK) -- block size NB = 16:
 //   panel    the NB current columns of every remaining row live in REGISTERS of the row's
 //            owner thread; partial pivoting = block argmax per column, the winner publishes
 //            its row through LDS; no row is ever moved in memory (a row map keeps the pivot
@@ -526,7 +526,7 @@ __device__ __forceinline__ int spin_ge(int* p, int v, int limit) {
     return -1;
 }
 
-// CHUNK (with SPLIT only): matrices whose L21 panel does not fit in LDS (560 < n <= 1024).  The
+// CHUNK (with SPLIT only): matrices whose L21 panel does not fit in LDS (525 < n <= 1024).  The
 // multipliers then go from the panel registers straight to global memory and every trailing /
 // back-substitution update walks the rows in chunks of RC, fetching that chunk's panel rows.
 constexpr int RC = 512;
@@ -1424,7 +1424,7 @@ const int* trace_solve_rowmaps(const void* scratch, int n, int nbatch) {
     return flags + 8 * (size_t)nbatch;
 }
 
-// LDS of the chunked build (560 < n <= 1024): the panel holds RC rows at a time
+// LDS of the chunked build (525 < n <= 1024): the panel holds RC rows at a time
 size_t trace_solve_chunked_lds(int n) {
     const int rows = n < RC ? n : RC;
     return (((size_t)3 * n * sizeof(int) + 15) / 16 + NB * NB + NB + std::max((size_t)rows * LS, (size_t)2 * BW * NB)) * sizeof(double2);
@@ -1464,7 +1464,7 @@ static void lu_stamps_report(hipStream_t) {}
 
 hipError_t launch_trace_solve_blocked(int n, int nbatch, double* A, double* B, const int* active,
                                       double* tr, int* info, int nwg, const int* items, int nitems,
-                                      void* scratch, hipStream_t stream, int group_min_n, int spin_limit) {
+                                      void* scratch, hipStream_t stream, int group_min_n, int spin_limit, LuRoute* route) {
     // matrices whose whole L21 panel does not fit in LDS go through the chunked build, which
     // exists only with helper workgroups (the multipliers must be in global memory anyway)
     const bool chunk = trace_solve_blocked_lds(n) > 150 * 1024;
@@ -1555,6 +1555,7 @@ hipError_t launch_trace_solve_blocked(int n, int nbatch, double* A, double* B, c
                 hipLaunchKernelGGL(k_trace_solve_blocked<true>, dim3(ctl.nitems * nwg), dim3(BT), lds, stream,
                                    n, nbatch, (double2*)A, (double2*)B, active, (double2*)tr, info, ctl);
             lu_stamps_report(stream);
+            if (route) *route = LuRoute{chunk ? LU_SYM_BLOCKED_CHUNKED : group ? LU_SYM_GROUPED : LU_SYM_BLOCKED_SPLIT, nwg};
             return hipGetLastError();
         }
         if (chunk) return hipErrorNotSupported;
@@ -1562,6 +1563,7 @@ hipError_t launch_trace_solve_blocked(int n, int nbatch, double* A, double* B, c
     }
     hipLaunchKernelGGL(k_trace_solve_blocked<false>, dim3(nbatch), dim3(BT), lds, stream, n, nbatch,
                        (double2*)A, (double2*)B, active, (double2*)tr, info, ctl);
+    if (route) *route = LuRoute{LU_SYM_BLOCKED_ONE, 1};
     return hipGetLastError();
 }
 

@@ -233,6 +233,23 @@ int emme_ctx_get_mirror_pairs(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINV
 int emme_ctx_set_lu_fold(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1 */
 int emme_ctx_get_lu_fold(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
 int emme_ctx_last_folded_steps(const emme_ctx_t* ctx); /* steps of the last emme_solve_roots that ran folded */
+/* Which LU kernel the context launched last (additions within version 4, found by symbol lookup), as the fill mode says
+ * it for the fills.  The symbol is the kernel's name as rocprofv3 prints it, "" before the first launch, NULL for a NULL
+ * context; the string lives as long as the library.  After a trace step (emme_trace_solve_batch, the half problems of
+ * the folded step, a step of emme_solve_roots): "k_trace_solve_blocked<false, false>" (one workgroup per matrix),
+ * "k_trace_solve_blocked<true, false>" (several), "k_trace_solve_grouped" (several, grouped trailing updates),
+ * "k_trace_solve_blocked<true, true>" (chunked panel, orders whose panel does not fit one workgroup's LDS) or
+ * "k_trace_solve" (unblocked) -- what was launched, which is one workgroup per matrix or the unblocked kernel where
+ * the grid of a split or chunked launch could not be resident.  After a factorisation alone (null vectors, eigenpair
+ * steps, contour moments): "k_lu_inplace", "k_trace_solve_blocked<true, true>" or "k_lu_unblocked_inplace".
+ * emme_ctx_last_lu_workgroups: the workgroups each matrix got; emme_ctx_last_lu_slices: the launches the batch of that
+ * factorisation was cut into (1 for a trace step). */
+const char* emme_ctx_linstep_kernel_symbol(const emme_ctx_t* ctx);
+int emme_ctx_last_lu_workgroups(const emme_ctx_t* ctx); /* < 0: EMME_EINVAL for NULL */
+int emme_ctx_last_lu_slices(const emme_ctx_t* ctx);     /* < 0: EMME_EINVAL for NULL */
+/* Compute units of the context's device, from its properties: what the workgroup counts and the slices of a chunked
+ * factorisation (half of them per launch) are planned with. */
+int emme_ctx_compute_units(const emme_ctx_t* ctx);      /* < 0: EMME_EINVAL for NULL */
 /* Launch everything on this hipStream_t (e.g. torch's current stream). NULL = default. */
 int emme_ctx_set_stream(emme_ctx_t* ctx, void* hip_stream);
 int emme_ctx_dim(const emme_ctx_t* ctx); /* N if beta_e == 0 else 2N */

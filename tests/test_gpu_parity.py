@@ -258,7 +258,7 @@ def test_device_resident_buffers_and_stream(emme):
 
 @pytest.mark.parametrize("n", [5, 16, 33, 100, 256, 512, 600, 777, 1024, 1100])
 def test_trace_solve_sizes_against_lapack(emme, n):
-    """Blocked LU (NB=16) incl. ragged last block, vs numpy (LAPACK zgesv); above n = 560 the
+    """Blocked LU (NB=16) incl. ragged last block, vs numpy (LAPACK zgesv); above n = 525 the
     chunked multi-workgroup build (panel rows in chunks of 512), above 1024 the unblocked kernel."""
     rng = np.random.default_rng(n)
     nb = 3
