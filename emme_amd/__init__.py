@@ -11,7 +11,7 @@ from ._lib import (EmmeError, Params, Profile, Context, params_from_json, params
                    gather_pack, gather_unpack, Contour, contour_default, contour_eigs, elementary, integrand,
                    ELEMENTARY, FORM_F, FORM_F_DF, FORM_SPLIT, FORM_W, TILE_SHAPES_ES15, TILE_SHAPES_ALL,
                    DERIV_CACHE_SHAPES_ES15, DERIV_CACHE_SHAPES_ALL, params_same_shape, run_json_lockstep, scan_plan, last_error,
-                   neighbour_sets)
+                   neighbour_sets, vector_parity)
 
 __all__ = ["EmmeError", "Params", "Profile", "Context", "params_from_json", "params_from_dict",
            "tables", "weight", "lib_path", "load", "json_text", "null_vector", "scan_values", "run_json",
@@ -20,4 +20,4 @@ __all__ = ["EmmeError", "Params", "Profile", "Context", "params_from_json", "par
            "gather_unpack", "Contour", "contour_default", "contour_eigs", "elementary", "integrand", "ELEMENTARY",
            "FORM_F", "FORM_F_DF", "FORM_SPLIT", "FORM_W", "TILE_SHAPES_ES15", "TILE_SHAPES_ALL",
            "DERIV_CACHE_SHAPES_ES15", "DERIV_CACHE_SHAPES_ALL", "params_same_shape", "run_json_lockstep", "scan_plan", "last_error",
-           "neighbour_sets"]
+           "neighbour_sets", "vector_parity"]

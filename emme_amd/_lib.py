@@ -182,6 +182,12 @@ def load():
         lib.emme_ctx_get_lu_fold.argtypes = [P]
         lib.emme_ctx_last_folded_steps.argtypes = [P]
         lib.emme_trace_secant_folded_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P, P]
+    if hasattr(lib, "emme_ctx_set_eigpair_fold"):  # (an older library loaded through EMME_LIB for an A/B has none)
+        lib.emme_ctx_set_eigpair_fold.argtypes = [P, C.c_int]
+        lib.emme_ctx_get_eigpair_fold.argtypes = [P]
+        lib.emme_ctx_last_folded_eigpair_steps.argtypes = [P]
+        lib.emme_eigenpair_secant_folded_step_batch.argtypes = [P, C.c_int, C.c_int, P, P, P, P, P, P, P]
+        lib.emme_vector_parity.argtypes = [C.c_int, C.c_int, P, P]
     if hasattr(lib, "emme_ctx_linstep_kernel_symbol"):  # (an older library loaded through EMME_LIB for an A/B has none)
         lib.emme_ctx_linstep_kernel_symbol.argtypes = [P]
         lib.emme_ctx_linstep_kernel_symbol.restype = C.c_char_p
@@ -360,6 +366,20 @@ def null_vector(M) -> np.ndarray:
     v = np.zeros(M.shape[0], dtype=np.complex128)
     _check(load().emme_null_vector(M.ctypes.data, M.shape[0], v.ctypes.data))
     return v
+
+
+def vector_parity(vecs) -> np.ndarray:
+    """Share of every vector in the subspace that is even under the flip i -> n-1-i (emme_vector_parity, DESIGN.md
+    §14.2): |v1 + J v2|^2 / (2 |v|^2), 1 for an even mode, 0 for an odd one; NaN for a zero or non-finite vector.  vecs:
+    [nvec, n] or one vector [n], from any eigenpair entry point.  No device."""
+    v = _c128(vecs)
+    one = v.ndim == 1
+    v = np.ascontiguousarray(v[None] if one else v)
+    if v.ndim != 2 or v.shape[0] < 1 or v.shape[1] < 1:
+        raise ValueError("vecs must be [nvec, n]")
+    even = np.zeros(v.shape[0], dtype=np.float64)
+    _check(load().emme_vector_parity(v.shape[1], v.shape[0], v.ctypes.data, even.ctypes.data))
+    return even[0] if one else even
 
 
 def contour_default(**kw) -> Contour:
@@ -624,17 +644,21 @@ class Context:
 
     def __init__(self, params: Params, device: int = -1, **options):
         """options: fields of emme_options_t (node_cache_gb, cache_min_batch, fill, lu_split, ...); lu_fold (0 / 1): the
-        folded trace-secant step, which is a setter of the context (set_lu_fold)."""
+        folded trace-secant step, which is a setter of the context (set_lu_fold); eigpair_fold (0 / 1): the folded secant
+        eigenpair step, likewise (set_eigpair_fold)."""
         self.lib = load()
         self.params = params
         h = C.c_void_p()
         lu_fold = options.pop("lu_fold", None)
+        eigpair_fold = options.pop("eigpair_fold", None)
         o = default_options(**options)
         _check(self.lib.emme_ctx_create_ex(C.byref(params), device, C.byref(o), C.byref(h)))
         self.h = h
         self.dim = self.lib.emme_ctx_dim(h)
         if lu_fold is not None:
             self.set_lu_fold(lu_fold)
+        if eigpair_fold is not None:
+            self.set_eigpair_fold(eigpair_fold)
 
     def options(self) -> Options:
         o = Options()
@@ -1103,6 +1127,45 @@ class Context:
         _check(self.lib.emme_eigenpair_secant_step_batch(self.h, n, nb, pm, pmo, dw.ctypes.data,
                                                          vv.ctypes.data, 0 if v is None else 1, tau.ctypes.data,
                                                          resid.ctypes.data, info.ctypes.data))
+        return vv, tau, resid, info
+
+    def set_eigpair_fold(self, on) -> None:
+        """The folded secant eigenpair step (default off): steps of solve_eigenpairs(secant=True) and of
+        find_eigenpairs_in_contour(exact=False)'s polish whose two fills ran mirrored, on an even order, factor the even
+        and the odd block instead of the matrix.  0: every step is the unfolded one, bit for bit."""
+        _check(self.lib.emme_ctx_set_eigpair_fold(self.h, int(on)))
+
+    def eigpair_fold(self) -> int:
+        v = self.lib.emme_ctx_get_eigpair_fold(self.h)
+        if v < 0:
+            _check(v)
+        return v
+
+    def last_folded_eigpair_steps(self) -> int:
+        """Steps of the last eigenpair search that ran folded."""
+        return self.lib.emme_ctx_last_folded_eigpair_steps(self.h)
+
+    def eigenpair_secant_folded_step(self, M, M_old, domega, v, device_ptrs=None):
+        """One folded secant eigenpair step (emme_eigenpair_secant_folded_step_batch) on symmetric matrices of even order
+        that are centrosymmetric apart from their last row and column; v [nbatch, n]: the unit vectors (required).
+        Returns (u / |u|, tau, resid, info) as eigenpair_secant_step.  device_ptrs = (M, M_old) device addresses: both
+        matrix operands in device memory, M = (nbatch, n)."""
+        if device_ptrs is not None:
+            nb, n = int(M[0]), int(M[1])
+            pm, pmo = (C.c_void_p(int(p)) for p in device_ptrs)
+        else:
+            pm, pmo, nb, n, _keep = _operand_pair(M, M_old, None, None)
+        dw = np.ascontiguousarray(_c128(np.atleast_1d(domega)))
+        if dw.shape != (nb,):
+            raise ValueError("domega needs one entry per matrix")
+        vv = np.array(_c128(v), dtype=np.complex128, order="C", copy=True).reshape(-1, n)
+        if vv.shape != (nb, n):
+            raise ValueError("v must be [nbatch, n]")
+        tau = np.zeros(nb, dtype=np.complex128)
+        resid = np.zeros(nb, dtype=np.float64)
+        info = np.zeros(nb, dtype=np.int32)
+        _check(self.lib.emme_eigenpair_secant_folded_step_batch(self.h, n, nb, pm, pmo, dw.ctypes.data, vv.ctypes.data,
+                                                                tau.ctypes.data, resid.ctypes.data, info.ctypes.data))
         return vv, tau, resid, info
 
     def eigenpair_step(self, M, Mp, v=None, m_device_ptr: int | None = None, mp_device_ptr: int | None = None):

@@ -138,7 +138,11 @@ struct emme_ctx {
         DeviceBuffer<double> vecs, tr2, part;    // folds of u and u'; traces of the half problems; k_fold_solve's sums
         DeviceBuffer<int> act2, info2, lu_info, items;
         DeviceBuffer<> lu_scratch;               // row orders of the second factorisation (launch_lu_inplace)
+        DeviceBuffer<double> eig_vecs, eig_part; // the folded eigenpair step: what k_eigpair_fold_half leaves behind
     } fold;
+    // the folded secant eigenpair step (eigpair_fold.hip)
+    int eigpair_fold = 0;          // emme_ctx_set_eigpair_fold (EMME_EIGPAIR_FOLD read at creation)
+    int last_folded_eigpair_steps = 0;  // steps of the last eigenpair search that ran folded
     PinnedBuffer<int> p_act;       // pinned host copies of d_active / d_intervals / omega / the deferred
     PinnedBuffer<unsigned long long> p_iv;  // count, WRITTEN BY KERNELS (k_retire, k_newton_update): the
     PinnedBuffer<double> p_w;      // Newton loop reads them after its one synchronisation per step
@@ -284,6 +288,15 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
 bool fold_applies(const emme_ctx* c, int n);
 int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* work,
                        double* Mp, const double* domega, const int* active, double* tr, int* info, const int* h_active);
+// The secant eigenpair step folded the same way: whether an order qualifies (even, the blocked
+// one-workgroup kernels for n / 2; no option is consulted), and the step on matrices of that structure: fold edges and
+// pass, ONE k_lu_inplace per half problem, k_eigpair_fold_half, k_eigpair_fold_combine.  Reads the upper triangles of M
+// and Mold and the chains' unit vectors in `vecs`; leaves the new vectors there, tau, resid (before the step) and info
+// of the live chains.  work and Mp as above; h_live: host flags, 1 = the chain takes the step (null: every chain).
+bool eigpair_fold_applies(const emme_ctx* c, int n);
+int folded_eigpair_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* work, double* Mp,
+                               const double* domega, const int* active, const int* h_live, double* vecs, double* tau,
+                               double* resid, int* info);
 // scratch of lu_factor_batch that the caller keeps until what it queued behind the factorisation has run
 struct LuScratch {
     DeviceBuffer<double> b;  // dummy right-hand sides of the chunked multi-workgroup factorisation

@@ -169,6 +169,60 @@ int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const do
     return EMME_OK;
 }
 
+bool eigpair_fold_applies(const emme_ctx* c, int n) {
+    return n >= 2 && n % 2 == 0 && c->opt.lu_unblocked == 0 && trace_solve_blocked_lds(n / 2) <= 150 * 1024 &&
+           null_iterate_lds(n / 2) <= 150 * 1024;
+}
+
+// The folded secant eigenpair step (eigpair_fold.hip): the fold pass, ONE factorisation per half problem that keeps its
+// factors, then the half problems' solves and the chains' sums.  The first half of `work` holds what the factorisation
+// destroys, the second halves of `work` and `Mp` the copies of S and S' that are read afterwards (the first half of
+// `Mp` is the pass's other copy of S', which nothing reads here).  M_old is not written: an unfolded step that follows
+// reads whole rows of it, and the search's own copy M -> M_old stays.
+int folded_eigpair_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* work, double* Mp,
+                               const double* domega, const int* active, const int* h_live, double* vecs, double* tau,
+                               double* resid, int* info) {
+    const int m = n / 2, nhalf = 2 * nbatch;
+    emme_ctx::FoldScratch& f = c->fold;
+    HIP_TRY(f.vecs.grow(sizeof(double) * 2 * 4 * (size_t)m * nbatch));
+    HIP_TRY(f.act2.grow(sizeof(int) * nhalf));
+    HIP_TRY(f.lu_info.grow(sizeof(int) * nhalf));
+    HIP_TRY(f.lu_scratch.grow(trace_solve_blocked_scratch(m, nhalf)));
+    HIP_TRY(f.eig_vecs.grow(eigpair_fold_vec_bytes(n, nbatch)));
+    HIP_TRY(f.eig_part.grow(eigpair_fold_part_bytes(nbatch)));
+    const size_t second = (size_t)nbatch * n * n;  // doubles: half of a set of nbatch n x n complex matrices
+    double *S1 = work, *S2 = work + second, *D1 = Mp, *D2 = Mp + second;
+    // the live half problems, the two of a chain side by side
+    const int* d_items = nullptr;
+    int n_live = nhalf;
+    if (h_live) {
+        int* slot = nullptr;
+        HIP_TRY(f.items.grow(sizeof(int) * nhalf));
+        HIP_TRY(c->lists.reserve(nhalf));
+        HIP_TRY(c->lists.take(nhalf, &slot));
+        n_live = 0;
+        for (int b = 0; b < nbatch; ++b)
+            if (h_live[b] == 1) slot[n_live++] = 2 * b, slot[n_live++] = 2 * b + 1;
+        if (n_live == 0) return EMME_OK;
+        HIP_TRY(launch_stage_ints(slot, f.items, n_live, nullptr, 0, c->stream));
+        HIP_TRY(c->lists.read_on(c->stream));
+        d_items = f.items;
+    }
+    {
+        ScopedSpan s(c, K_LIN);
+        HIP_TRY(launch_fold_edges(n, nbatch, M, Mold, domega, active, f.vecs, f.act2, c->stream));
+        HIP_TRY(launch_fold_pass(n, nbatch, M, Mold, nullptr, S1, S2, D1, D2, domega, active, c->stream));
+    }
+    ScopedSpan s(c, K_NULL);
+    HIP_TRY(launch_lu_inplace(m, nhalf, S1, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
+    note_lu_launch(c, LU_SYM_INPLACE, 1, 1);
+    HIP_TRY(launch_eigpair_fold_half(n, S1, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
+                                     active, f.lu_info, S2, D2, f.vecs, vecs, f.eig_vecs, f.eig_part, c->stream));
+    HIP_TRY(launch_eigpair_fold_combine(n, d_items, n_live / 2, active, M, domega, f.vecs, f.lu_info, f.eig_vecs, f.eig_part, vecs,
+                                        tau, resid, info, c->stream));
+    return EMME_OK;
+}
+
 // Partial-pivot LU of nbatch n x n matrices in place (P M = L U, rows never moved; n <= 2048), by the branch the
 // order allows: k_lu_inplace where the whole L21 panel fits one workgroup's LDS; above that, up to n = 1024, the chunked
 // multi-workgroup kernel of the Newton step (two workgroups per matrix, which must be resident together: slices of at
@@ -461,6 +515,51 @@ int emme_eigenpair_secant_step_batch(emme_ctx_t* c, int n, int nbatch, const dou
     }
     return caller_eigenpair_step(c, "emme_eigenpair_secant_step_batch", n, nbatch, M, M_old, domega, v, have_v, tau, resid,
                                  info);
+}
+
+// The folded secant eigenpair step on caller matrices, whatever the context's eigpair_fold says
+int emme_eigenpair_secant_folded_step_batch(emme_ctx_t* c, int n, int nbatch, const double* M, const double* M_old,
+                                            const double* domega, double* v, double* tau, double* resid, int* info) {
+    const char* who = "emme_eigenpair_secant_folded_step_batch";
+    if (!c || !M || !M_old || !domega || !v || !tau || !resid || !info || n < 2 || nbatch < 1) {
+        set_error(std::string(who) + ": a required pointer is NULL, n < 2 or nbatch < 1");
+        return EMME_EINVAL;
+    }
+    if (n % 2 != 0) {
+        set_error(std::string(who) + ": the order must be even");
+        return EMME_EINVAL;
+    }
+    if (!eigpair_fold_applies(c, n)) {
+        set_error(std::string(who) + ": the half problems need the blocked one-workgroup kernels (order above 1050, or lu_unblocked)");
+        return EMME_ECONFIG;
+    }
+    HIP_TRY(hipSetDevice(c->device));
+    EMME_TRY(ensure_batch(c, 2 * nbatch));
+    const size_t bytes = batch_bytes(n, nbatch), vbytes = sizeof(double) * 2 * (size_t)n * nbatch, cb = sizeof(double) * 2 * nbatch;
+    DeviceOperands ops;
+    hipError_t staged = hipSuccess;
+    EMME_TRY(ops.stage(c, M, M_old, bytes, &staged));
+    HIP_TRY(staged);
+    // device scratch of this call: the half problems' work copies, vectors, domega, tau, residuals, info
+    DeviceBuffer<double> t_work, t_mp, t_v, t_dw, t_tau, t_res;
+    DeviceBuffer<int> t_info;
+    HIP_TRY(t_work.grow(bytes));
+    HIP_TRY(t_mp.grow(bytes));
+    HIP_TRY(t_v.grow(vbytes));
+    HIP_TRY(t_dw.grow(cb));
+    HIP_TRY(t_tau.grow(cb));
+    HIP_TRY(t_res.grow(sizeof(double) * nbatch));
+    HIP_TRY(t_info.grow(sizeof(int) * nbatch));
+    HIP_TRY(hipMemcpyAsync(t_v, v, vbytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(hipMemcpyAsync(t_dw, domega, cb, hipMemcpyHostToDevice, c->stream));
+    EMME_TRY(folded_eigpair_secant_step(c, n, nbatch, ops.A, ops.B, t_work, t_mp, t_dw, nullptr, nullptr, t_v, t_tau, t_res,
+                                        t_info));
+    HIP_TRY(hipMemcpyAsync(v, t_v, vbytes, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(tau, t_tau, cb, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(resid, t_res, sizeof(double) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipMemcpyAsync(info, t_info, sizeof(int) * nbatch, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(hipStreamSynchronize(c->stream));
+    return EMME_OK;
 }
 
 }  // extern "C"

@@ -50,6 +50,7 @@ int search_begin(emme_ctx* c, RootSearch& s, int mat_sets) {
     c->last_folded_steps = 0;
     if (s.set) EMME_TRY(upload_set_indices(c, s.set, n));
     if (s.eigpair) {
+        c->last_folded_eigpair_steps = 0;
         const size_t vbytes = sizeof(double) * 2 * (size_t)n * c->dim;
         HIP_TRY(c->d_vecs.grow(vbytes));
         HIP_TRY(c->d_resid.grow(sizeof(double) * n));
@@ -215,7 +216,23 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
     if (eig) std::fill(c->p_live.get(), c->p_live.get() + n, 1);
     for (int j = 0; j <= step_limit; ++j) {  // src/main.cpp:43
         const bool fused_copy = method == EMME_METHOD_TRACE_SECANT;
-        if (eig) {
+        // Option eigpair_fold: under the routing rule of the folded trace step -- both fills mirrored
+        // for every live chain, an even order whose halves fit -- the eigenpair step factors the even and the odd block
+        // instead.  Not the first step of a call without v0, which also makes v_0 = M^-1 s.
+        // (d_Mp holds the half problems' S': solve_eigenpairs allocates it exactly where a step can fold, and a step
+        // without it is never folded.  The list of the folded step is p_live == 1, which is d_active == 1: k_retire
+        // only turns 2 into 0 after the flags were read; the kernels check d_active as well, as the parent's does.)
+        const bool eig_folded = eig && c->eigpair_fold != 0 && c->mirror && old_mirrored && new_mirrored &&
+                                eigpair_fold_applies(c, c->dim) && !(j == 0 && !search.v0) && !search.set &&
+                                c->d_Mp.bytes() >= batch_bytes(c->dim, n);
+        if (eig_folded) {
+            EMME_TRY(folded_eigpair_secant_step(c, c->dim, n, c->d_M, c->d_Mold, c->d_work, c->d_Mp, c->d_domega, c->d_active,
+                                                c->p_live.get(), c->d_vecs, c->d_tr, c->d_resid, c->d_info));
+            ++c->last_folded_eigpair_steps;
+            // (the fold pass writes upper triangles only; an unfolded step that follows reads whole rows of M_old)
+            ScopedSpan s(c, K_OTHER);
+            HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_Mold, nullptr, c->d_active, c->stream));
+        } else if (eig) {
             // the work copy of the live M, its factorisation and the secant eigenpair step on (M, M_old, domega); then
             // this step's matrix becomes the "previous" one
             {
@@ -413,8 +430,14 @@ int solve_eigenpairs(emme_ctx* c, const std::string& who, bool secant, const int
             for (int i = 0; i < 2 * dim; ++i) row[i] /= nrm;
         }
     }
-    // (the secant search keeps M, M_old and the work copy: no M')
-    EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, secant ? 1 | 2 | 8 : 1 | 4 | 8,
+    // (the secant search keeps M, M_old and the work copy: no M' -- with the option eigpair_fold its set holds the half
+    // problems' S')
+    // -- only where a step can fold at all: no parameter sets, an order whose halves qualify, and a node cache that is,
+    // or once allocated would be, laid out over the half pair list
+    const bool may_fold = c->eigpair_fold != 0 && !set && eigpair_fold_applies(c, dim) &&
+                          ((c->cache[0].recs || c->cache[1].recs) ? c->mirror : mirror_wanted(c));
+    const int secant_sets = 1 | 2 | 8 | (may_fold ? 4 : 0);
+    EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, secant ? secant_sets : 1 | 4 | 8,
                         secant ? secant_loop : newton_loop, set, true, v0 ? vn.data() : nullptr));
     HIP_TRY(hipMemcpyAsync(vecs, c->d_vecs, sizeof(double) * 2 * (size_t)n * dim, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(hipMemcpyAsync(resid, c->d_resid, sizeof(double) * n, hipMemcpyDeviceToHost, c->stream));

@@ -319,6 +319,8 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     if (const char* v = std::getenv("EMME_MIRROR")) c->mirror_opt = std::atoi(v) != 0;
     // (the same for the folded trace-secant step, DESIGN.md 5.4c: EMME_LU_FOLD=0 is emme_ctx_set_lu_fold(0))
     if (const char* v = std::getenv("EMME_LU_FOLD")) c->lu_fold = std::atoi(v) != 0;
+    // (and for the folded secant eigenpair step, DESIGN.md 14.2: EMME_EIGPAIR_FOLD=1 is emme_ctx_set_eigpair_fold(1))
+    if (const char* v = std::getenv("EMME_EIGPAIR_FOLD")) c->eigpair_fold = std::atoi(v) != 0;
 
     auto fail = [&](int code) {
         emme_ctx_destroy(c);
@@ -431,6 +433,50 @@ int emme_ctx_set_lu_fold(emme_ctx_t* c, int on) {
 int emme_ctx_get_lu_fold(const emme_ctx_t* c) { return c ? c->lu_fold : EMME_EINVAL; }
 
 int emme_ctx_last_folded_steps(const emme_ctx_t* c) { return c ? c->last_folded_steps : EMME_EINVAL; }
+
+int emme_ctx_set_eigpair_fold(emme_ctx_t* c, int on) {
+    if (!c) {
+        set_error("emme_ctx_set_eigpair_fold: NULL context");
+        return EMME_EINVAL;
+    }
+    if (on != 0 && on != 1) {
+        set_error("emme_ctx_set_eigpair_fold: value out of range (0, 1)");
+        return EMME_EINVAL;
+    }
+    c->eigpair_fold = on;
+    return EMME_OK;
+}
+
+int emme_ctx_get_eigpair_fold(const emme_ctx_t* c) { return c ? c->eigpair_fold : EMME_EINVAL; }
+
+int emme_ctx_last_folded_eigpair_steps(const emme_ctx_t* c) { return c ? c->last_folded_eigpair_steps : EMME_EINVAL; }
+
+// Share of every vector in the even subspace of the flip J: plain host arithmetic, no device
+int emme_vector_parity(int n, int nvec, const double* vecs, double* even) {
+    if (!vecs || !even || n < 1 || nvec < 1) {
+        set_error("emme_vector_parity: a required pointer is NULL, n < 1 or nvec < 1");
+        return EMME_EINVAL;
+    }
+    for (int k = 0; k < nvec; ++k) {
+        const double* v = vecs + 2 * (size_t)k * n;
+        double ev = 0.0, all = 0.0;
+        for (int i = 0; i < n / 2; ++i) {
+            const double *p = v + 2 * i, *q = v + 2 * (size_t)(n - 1 - i);
+            const double sr = p[0] + q[0], si = p[1] + q[1];
+            ev += sr * sr + si * si;
+            // (grouped so that an exactly even or odd vector gives exactly 1 or 0)
+            all += (p[0] * p[0] + p[1] * p[1]) + (q[0] * q[0] + q[1] * q[1]);
+        }
+        if (n % 2 != 0) {  // the middle entry is its own mirror image: even
+            const double* p = v + 2 * (size_t)(n / 2);
+            const double s = p[0] * p[0] + p[1] * p[1];
+            ev += 2.0 * s, all += s;
+        }
+        const double share = ev / (2.0 * all);
+        even[k] = (all > 0.0 && std::isfinite(all) && std::isfinite(share)) ? share : std::numeric_limits<double>::quiet_NaN();
+    }
+    return EMME_OK;
+}
 
 const char* emme_ctx_linstep_kernel_symbol(const emme_ctx_t* c) { return c ? c->last_lu_symbol : nullptr; }
 

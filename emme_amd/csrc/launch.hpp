@@ -352,6 +352,26 @@ hipError_t launch_eigpair_secant_step(int n, const double* M, const double* Mold
                                       const int* rowmaps, int nb, const int* items, int nitems, const int* active,
                                       const int* lu_info, double* vecs, double* tau, double* resid, int* info, bool first,
                                       hipStream_t stream);
+// ---- the secant eigenpair step folded into two half-size problems (eigpair_fold.hip) -----
+// Behind launch_fold_edges, launch_fold_pass and launch_lu_inplace on the first copy of S (half problem 2b: the even
+// block of chain b, 2b + 1 the odd one; m = n / 2; all pointers device memory).  Per listed half problem (items: device
+// list of nitems, null = 0 .. nitems-1): the fold of the chain's vector, y = S v and z = S' v from the kept copies S and
+// Sp, the four solves on the factors S_lu / rowmaps / nb / lu_info, its dot products; active (nullable, per chain): a
+// listed half problem or chain whose flag is 0 is left alone, as in launch_eigpair_secant_step.  hv holds
+// eigpair_fold_vec_bytes(n, nbatch) bytes, part eigpair_fold_part_bytes(nbatch); null_iterate_lds(m) of LDS.
+size_t eigpair_fold_vec_bytes(int n, int nbatch);
+size_t eigpair_fold_part_bytes(int nbatch);
+hipError_t launch_eigpair_fold_half(int n, const double* S_lu, const int* rowmaps, int nb, const int* items, int nitems,
+                                    const int* active, const int* lu_info, const double* S, const double* Sp, const double* edges,
+                                    const double* vecs, double* hv, double* part, hipStream_t stream);
+// Per chain (items: the same list, both half problems of every chain side by side, nchains = nitems / 2; null = chains
+// 0 .. nchains-1): tau[b], the new unit vector in vecs[b], resid[b] = |M v| / |M|_F before the step (the edge terms of
+// |M|_F from M itself) and info[b]: 0; k > 0: the even (k <= m) or the odd block (k - m) met an exactly zero pivot
+// column; n + 1: the 2 x 2 matrix of the rank-2 correction is singular or not finite; EMME_ENUMERIC: a zero or
+// non-finite domega, tau or u.  Vector, tau and resid are NaN for every non-zero info.  Two runs are bit-identical.
+hipError_t launch_eigpair_fold_combine(int n, const int* items, int nchains, const int* active, const double* M, const double* domega,
+                                       const double* edges, const int* lu_info, const double* hv, const double* part,
+                                       double* vecs, double* tau, double* resid, int* info, hipStream_t stream);
 // the residual alone, in the same order of sums: no factors are read, vecs is left as it is
 hipError_t launch_eigpair_resid(int n, const double* M, const int* items, int nitems, const double* vecs, double* resid,
                                 hipStream_t stream);

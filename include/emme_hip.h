@@ -497,6 +497,41 @@ int emme_eigenpair_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* 
 int emme_eigenpair_secant_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* M_old,
                                      const double* domega /* host, nbatch complex */, double* v /* in/out, host */,
                                      int have_v, double* tau, double* resid, int* info);
+/* ---- that step on mirrored grids, folded; mode parity (additions within version 4: find them by symbol lookup;
+ * DESIGN.md 14.2) ----------------------------------------------------------------------------------------------------
+ * Where a context runs mirrored (emme_ctx_set_mirror_pairs) its matrix is C + u e^T + e u^T, C symmetric and
+ * centrosymmetric, and a secant eigenpair step whose two fills both ran mirrored for every live chain, on an even order,
+ * can factor the even and the odd block of order dim / 2 instead of the matrix (ONE k_lu_inplace per block, a quarter of
+ * the LU flops, four triangular solves of half the order; eigpair_fold.hip) with the exact rank-2 correction of the last
+ * row and column.  Option eigpair_fold: 0 (default) = every step is the unfolded one, bit for bit; 1 = steps of
+ * emme_solve_eigenpairs_secant (and of the region searches' polish with exact = 0) that qualify run folded -- all but
+ * the first step of a call without v0, which also makes v_0.  Fills over parameter sets, theta != 0, odd orders, GK31
+ * and electromagnetic contexts never qualify; emme_solve_eigenpairs (exact) is untouched.  EMME_EIGPAIR_FOLD, read at
+ * creation, overrides the default.  Not a layout setting: it may change on a live context, from the next call on.
+ * Cost: with the option on, a secant eigenpair search on a context where steps can fold (mirrored, even order, no
+ * parameter sets) holds one more matrix set, n*dim*dim complex, for the half problems' secants; elsewhere nothing.
+ * (emme_options_t keeps its size: the option is a setter, as lu_fold is.) */
+int emme_ctx_set_eigpair_fold(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1 */
+int emme_ctx_get_eigpair_fold(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
+int emme_ctx_last_folded_eigpair_steps(const emme_ctx_t* ctx); /* steps of the last eigenpair search that ran folded */
+/* The folded step alone, whatever eigpair_fold says.  THE CALLER PROMISES matrices of the structure the mirrored fills
+ * write, as for emme_trace_secant_folded_batch: only the wedge between diagonal and anti-diagonal (i <= j <= n-1-i) and
+ * the last column are read.  M, M_old: nbatch*n*n complex, row-major, both host or both device (EMME_EINVAL otherwise),
+ * not modified; domega (host, nbatch complex); v (host, nbatch*n complex, required): in, the unit vectors; out, u / |u|;
+ * tau, resid (of M, before the step) and info (host) as emme_eigenpair_secant_step_batch.  info[b]: 0; k > 0: the
+ * factorisation of the even (k <= n/2) or of the odd block (k - n/2) met an exactly zero pivot column; n + 1: the 2 x 2
+ * matrix of the rank-2 correction is singular or not finite; EMME_ENUMERIC: a zero or non-finite domega, tau or u;
+ * vector, tau and resid are NaN for every non-zero info.  The result of an item does not depend on the other items of
+ * the call; two calls give the same bits.  EMME_EINVAL for NULL arguments, n < 2 or an odd n; EMME_ECONFIG for n above
+ * 1050 or with lu_unblocked; both come before the device is looked for. */
+int emme_eigenpair_secant_folded_step_batch(emme_ctx_t* ctx, int n, int nbatch, const double* M, const double* M_old,
+                                            const double* domega /* host */, double* v /* in/out, host, required */,
+                                            double* tau, double* resid, int* info);
+/* Mode parity: even[k] = |v1 + J v2|^2 / (2 |v|^2) of vector k (vecs: nvec*n complex, host), the share of the vector
+ * in the subspace that is even under the flip i -> n-1-i (1: an even mode, 0: an odd one; for odd n the middle entry
+ * counts as even); NaN for a zero or non-finite vector.  Plain host arithmetic: no context, no device; works on the
+ * vectors of any eigenpair entry point.  EMME_EINVAL for NULL pointers, n < 1 or nvec < 1. */
+int emme_vector_parity(int n, int nvec, const double* vecs, double* even);
 /* The search: arguments, outputs, v0 rules, stopping rule, info codes, blanked failed chains and NaN-padded iterates as
  * emme_solve_eigenpairs, but bootstrapped as emme_solve_roots (omega_0 = 0.99 g, omega_1 = g: two plain fills; v_0 from
  * M(omega_1)^-1 s without v0), and every step costs ONE plain fill, routed exactly as emme_solve_roots' are (node cache,
