@@ -285,6 +285,8 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
 // centrosymmetric apart from their last row and column.  Reads the upper triangles of M and Mold, leaves tr / info of
 // the live chains; Mold_w (nullable): M_old = M there, upper triangle only.  work and Mp hold nbatch n x n matrices each
 // (the half problems' work copies and right-hand sides); h_active: host copy of `active` (null: all live).
+// halves_fit: the order alone -- even, and n / 2 within the blocked one-workgroup kernels (not lu_unblocked).
+bool halves_fit(const emme_ctx* c, int n);
 bool fold_applies(const emme_ctx* c, int n);
 int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* work,
                        double* Mp, const double* domega, const int* active, double* tr, int* info, const int* h_active);
@@ -305,6 +307,34 @@ struct LuScratch {
 int lu_factor_batch(emme_ctx* c, int n, int nbatch, double* work, LuScratch& s, const char* who,
                     const std::function<hipError_t(int b0, int nb, const int* maps, int map_nb, const int* lu_info)>& after,
                     const int* d_items = nullptr, int nitems = 0);
+
+// The live items of a launch as a device list, from host flags: item b with keep(flags[b]) gives `width` entries,
+// width b .. width b + width - 1 (1: the item itself; 2: the two half problems of chain b, side by side).
+// live_list_fill grows d_list, takes a pinned slot of c->lists and fills it with *count entries; live_list_send queues
+// their copy to d_list on c->stream; stage_live_list is both, and sends nothing where the list is empty -- the caller
+// returns early on *count == 0.
+template <class Keep>
+hipError_t live_list_fill(emme_ctx* c, DeviceBuffer<int>& d_list, const int* flags, int n, int width, Keep keep, int** slot,
+                          int* count) {
+    hipError_t e = d_list.grow(sizeof(int) * (size_t)n * width);
+    if (e == hipSuccess) e = c->lists.take((size_t)n * width, slot);
+    if (e != hipSuccess) return e;
+    *count = 0;
+    for (int b = 0; b < n; ++b)
+        if (keep(flags[b]))
+            for (int k = 0; k < width; ++k) (*slot)[(*count)++] = width * b + k;
+    return hipSuccess;
+}
+inline hipError_t live_list_send(emme_ctx* c, const int* slot, int* d_list, int count) {
+    const hipError_t e = emme::launch_stage_ints(slot, d_list, count, nullptr, 0, c->stream);
+    return e == hipSuccess ? c->lists.read_on(c->stream) : e;
+}
+template <class Keep>
+hipError_t stage_live_list(emme_ctx* c, DeviceBuffer<int>& d_list, const int* flags, int n, int width, Keep keep, int* count) {
+    int* slot = nullptr;
+    const hipError_t e = live_list_fill(c, d_list, flags, n, width, keep, &slot, count);
+    return e == hipSuccess && *count > 0 ? live_list_send(c, slot, d_list, *count) : e;
+}
 
 // host wall time of the cache allocations (hipMalloc of tens of GB: the cold cost of a context)
 struct AllocTimer {

@@ -30,19 +30,13 @@ hipError_t trace_solve(emme_ctx* c, int n, int nbatch, double* A, double* B, con
         int n_live = nbatch;
         int* lu_slot = nullptr;
         if (h_active) {
-            e = c->d_lu_items.grow(sizeof(int) * nbatch);
-            if (e == hipSuccess) e = c->lists.take(nbatch, &lu_slot);
-            if (e != hipSuccess) return e;
-            n_live = 0;
-            for (int b = 0; b < nbatch; ++b)
-                if (h_active[b]) lu_slot[n_live++] = b;
-            if (n_live == 0) return hipSuccess;
+            e = live_list_fill(c, c->d_lu_items, h_active, nbatch, 1, [](int f) { return f != 0; }, &lu_slot, &n_live);
+            if (e != hipSuccess || n_live == 0) return e;
         }
         const int nwg = lu_workgroups(n, n_live, c->n_cu, c->opt.lu_split, c->lu_one_wg, fits);
         const int* d_items = nullptr;
-        if (nwg > 1 && h_active) {
-            e = launch_stage_ints(lu_slot, c->d_lu_items, n_live, nullptr, 0, c->stream);
-            if (e == hipSuccess) e = c->lists.read_on(c->stream);
+        if (nwg > 1 && h_active) {  // (one workgroup per matrix reads the flags themselves)
+            e = live_list_send(c, lu_slot, c->d_lu_items, n_live);
             if (e != hipSuccess) return e;
             d_items = c->d_lu_items;
         }
@@ -113,10 +107,54 @@ hipError_t linear_step(emme_ctx* c, int method, int n, int nbatch, const double*
     return trace_solve(c, n, nbatch, work, Mp, active, tr, info, h_active);
 }
 
-bool fold_applies(const emme_ctx* c, int n) {
-    return c->lu_fold != 0 && n >= 2 && n % 2 == 0 && c->opt.lu_unblocked == 0 &&
-           trace_solve_blocked_lds(n / 2) <= 150 * 1024 && null_iterate_lds(n / 2) <= 150 * 1024;
+// an even order whose halves fit the one-workgroup kernels (k_lu_inplace, the blocked trace kernel, the solve frame)
+bool halves_fit(const emme_ctx* c, int n) {
+    return n >= 2 && n % 2 == 0 && c->opt.lu_unblocked == 0 && trace_solve_blocked_lds(n / 2) <= 150 * 1024 &&
+           null_iterate_lds(n / 2) <= 150 * 1024;
 }
+bool fold_applies(const emme_ctx* c, int n) { return c->lu_fold != 0 && halves_fit(c, n); }
+bool eigpair_fold_applies(const emme_ctx* c, int n) { return halves_fit(c, n); }
+
+namespace {
+
+// What the two folded steps share.  The four matrix areas: the first halves of `work` and `Mp` (S1, D1) and the second
+// halves (S2, D2) receive the same S and S' from the pass -- a factorisation destroys the copy it is given.
+struct FoldAreas {
+    int m, nhalf;
+    double *S1, *S2, *D1, *D2;
+    FoldAreas(int n, int nbatch, double* work, double* Mp) : m(n / 2), nhalf(2 * nbatch) {
+        const size_t second = (size_t)nbatch * n * n;  // doubles: half of a set of nbatch n x n complex matrices
+        S1 = work, S2 = work + second, D1 = Mp, D2 = Mp + second;
+    }
+};
+// the scratch both steps use: the folds of u and u', the half problems' flags, the codes and row orders of k_lu_inplace
+int fold_scratch(emme_ctx::FoldScratch& f, const FoldAreas& a) {
+    HIP_TRY(f.vecs.grow(sizeof(double) * 2 * 4 * (size_t)a.m * (a.nhalf / 2)));
+    HIP_TRY(f.act2.grow(sizeof(int) * a.nhalf));
+    HIP_TRY(f.lu_info.grow(sizeof(int) * a.nhalf));
+    HIP_TRY(f.lu_scratch.grow(trace_solve_blocked_scratch(a.m, a.nhalf)));
+    return EMME_OK;
+}
+// k_fold_edges and k_fold_pass under one profile span of the caller's kind
+int fold_edges_and_pass(emme_ctx* c, int kind, int n, int nbatch, const double* M, const double* Mold, double* Mold_w,
+                        const FoldAreas& a, const double* domega, const int* active) {
+    ScopedSpan s(c, kind);
+    HIP_TRY(launch_fold_edges(n, nbatch, M, Mold, domega, active, c->fold.vecs, c->fold.act2, c->stream));
+    HIP_TRY(launch_fold_pass(n, nbatch, M, Mold, Mold_w, a.S1, a.S2, a.D1, a.D2, domega, active, c->stream));
+    return EMME_OK;
+}
+// the live half problems, the two of a chain side by side, on their way to f.items (flags null: all of them, no list)
+template <class Keep>
+int fold_live_halves(emme_ctx* c, const int* flags, int nbatch, Keep keep, const int** d_items, int* n_live) {
+    *d_items = nullptr, *n_live = 2 * nbatch;
+    if (!flags) return EMME_OK;
+    HIP_TRY(c->lists.reserve(2 * nbatch));
+    HIP_TRY(stage_live_list(c, c->fold.items, flags, nbatch, 2, keep, n_live));
+    *d_items = c->fold.items;
+    return EMME_OK;
+}
+
+}  // namespace
 
 // The folded step (linstep_fold.hip): the fold pass, then per half problem the trace kernel on [S | S'] and, for the
 // rank-2 part, a second factorisation that keeps its factors (the one-workgroup trace kernel keeps its multipliers in
@@ -124,54 +162,31 @@ bool fold_applies(const emme_ctx* c, int n) {
 // factorisations destroy, the second halves the copies that are read afterwards.
 int folded_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* Mold_w, double* work,
                        double* Mp, const double* domega, const int* active, double* tr, int* info, const int* h_active) {
-    const int m = n / 2, nhalf = 2 * nbatch;
+    const FoldAreas a(n, nbatch, work, Mp);
+    const int m = a.m, nhalf = a.nhalf;
     emme_ctx::FoldScratch& f = c->fold;
-    HIP_TRY(f.vecs.grow(sizeof(double) * 2 * 4 * (size_t)m * nbatch));
+    EMME_TRY(fold_scratch(f, a));
     HIP_TRY(f.tr2.grow(sizeof(double) * 2 * nhalf));
     HIP_TRY(f.part.grow(fold_part_bytes(nbatch)));
-    HIP_TRY(f.act2.grow(sizeof(int) * nhalf));
     HIP_TRY(f.info2.grow(sizeof(int) * nhalf));
-    HIP_TRY(f.lu_info.grow(sizeof(int) * nhalf));
-    HIP_TRY(f.lu_scratch.grow(trace_solve_blocked_scratch(m, nhalf)));
-    const size_t second = (size_t)nbatch * n * n;  // doubles: half of a set of nbatch n x n complex matrices
-    double *S1 = work, *S2 = work + second, *D1 = Mp, *D2 = Mp + second;
-    {
-        ScopedSpan s(c, K_OTHER);
-        HIP_TRY(launch_fold_edges(n, nbatch, M, Mold, domega, active, f.vecs, f.act2, c->stream));
-        HIP_TRY(launch_fold_pass(n, nbatch, M, Mold, Mold_w, S1, S2, D1, D2, domega, active, c->stream));
-    }
+    EMME_TRY(fold_edges_and_pass(c, K_OTHER, n, nbatch, M, Mold, Mold_w, a, domega, active));
     // the live half problems: host flags for the trace kernel's launch, a device list for the other two
     std::vector<int> h2;
     const int* d_items = nullptr;
     int n_live = nhalf;
     if (h_active) {
         h2.resize(nhalf);
-        int* slot = nullptr;
-        HIP_TRY(f.items.grow(sizeof(int) * nhalf));
-        HIP_TRY(c->lists.reserve(nhalf));
-        HIP_TRY(c->lists.take(nhalf, &slot));
-        n_live = 0;
-        for (int b = 0; b < nbatch; ++b) {
-            h2[2 * b] = h2[2 * b + 1] = h_active[b] != 0;
-            if (h_active[b]) slot[n_live++] = 2 * b, slot[n_live++] = 2 * b + 1;
-        }
-        if (n_live == 0) return EMME_OK;
-        HIP_TRY(launch_stage_ints(slot, f.items, n_live, nullptr, 0, c->stream));
-        HIP_TRY(c->lists.read_on(c->stream));
-        d_items = f.items;
+        for (int b = 0; b < nbatch; ++b) h2[2 * b] = h2[2 * b + 1] = h_active[b] != 0;
     }
+    EMME_TRY(fold_live_halves(c, h_active, nbatch, [](int flag) { return flag != 0; }, &d_items, &n_live));
+    if (n_live == 0) return EMME_OK;
     ScopedSpan s(c, K_LIN);
-    HIP_TRY(launch_lu_inplace(m, nhalf, S2, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
-    HIP_TRY(trace_solve(c, m, nhalf, S1, D1, f.act2, f.tr2, f.info2, h_active ? h2.data() : nullptr));
-    HIP_TRY(launch_fold_solve(m, S2, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
-                              f.lu_info, D2, f.vecs, f.part, c->stream));
+    HIP_TRY(launch_lu_inplace(m, nhalf, a.S2, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
+    HIP_TRY(trace_solve(c, m, nhalf, a.S1, a.D1, f.act2, f.tr2, f.info2, h_active ? h2.data() : nullptr));
+    HIP_TRY(launch_fold_solve(m, a.S2, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
+                              f.lu_info, a.D2, f.vecs, f.part, c->stream));
     HIP_TRY(launch_fold_combine(n, nbatch, active, f.tr2, f.info2, f.lu_info, f.part, tr, info, c->stream));
     return EMME_OK;
-}
-
-bool eigpair_fold_applies(const emme_ctx* c, int n) {
-    return n >= 2 && n % 2 == 0 && c->opt.lu_unblocked == 0 && trace_solve_blocked_lds(n / 2) <= 150 * 1024 &&
-           null_iterate_lds(n / 2) <= 150 * 1024;
 }
 
 // The folded secant eigenpair step (eigpair_fold.hip): the fold pass, ONE factorisation per half problem that keeps its
@@ -182,42 +197,23 @@ bool eigpair_fold_applies(const emme_ctx* c, int n) {
 int folded_eigpair_secant_step(emme_ctx* c, int n, int nbatch, const double* M, const double* Mold, double* work, double* Mp,
                                const double* domega, const int* active, const int* h_live, double* vecs, double* tau,
                                double* resid, int* info) {
-    const int m = n / 2, nhalf = 2 * nbatch;
+    const FoldAreas a(n, nbatch, work, Mp);
+    const int m = a.m, nhalf = a.nhalf;
     emme_ctx::FoldScratch& f = c->fold;
-    HIP_TRY(f.vecs.grow(sizeof(double) * 2 * 4 * (size_t)m * nbatch));
-    HIP_TRY(f.act2.grow(sizeof(int) * nhalf));
-    HIP_TRY(f.lu_info.grow(sizeof(int) * nhalf));
-    HIP_TRY(f.lu_scratch.grow(trace_solve_blocked_scratch(m, nhalf)));
+    EMME_TRY(fold_scratch(f, a));
     HIP_TRY(f.eig_vecs.grow(eigpair_fold_vec_bytes(n, nbatch)));
     HIP_TRY(f.eig_part.grow(eigpair_fold_part_bytes(nbatch)));
-    const size_t second = (size_t)nbatch * n * n;  // doubles: half of a set of nbatch n x n complex matrices
-    double *S1 = work, *S2 = work + second, *D1 = Mp, *D2 = Mp + second;
-    // the live half problems, the two of a chain side by side
+    // the list goes first: an empty one launches nothing
     const int* d_items = nullptr;
     int n_live = nhalf;
-    if (h_live) {
-        int* slot = nullptr;
-        HIP_TRY(f.items.grow(sizeof(int) * nhalf));
-        HIP_TRY(c->lists.reserve(nhalf));
-        HIP_TRY(c->lists.take(nhalf, &slot));
-        n_live = 0;
-        for (int b = 0; b < nbatch; ++b)
-            if (h_live[b] == 1) slot[n_live++] = 2 * b, slot[n_live++] = 2 * b + 1;
-        if (n_live == 0) return EMME_OK;
-        HIP_TRY(launch_stage_ints(slot, f.items, n_live, nullptr, 0, c->stream));
-        HIP_TRY(c->lists.read_on(c->stream));
-        d_items = f.items;
-    }
-    {
-        ScopedSpan s(c, K_LIN);
-        HIP_TRY(launch_fold_edges(n, nbatch, M, Mold, domega, active, f.vecs, f.act2, c->stream));
-        HIP_TRY(launch_fold_pass(n, nbatch, M, Mold, nullptr, S1, S2, D1, D2, domega, active, c->stream));
-    }
+    EMME_TRY(fold_live_halves(c, h_live, nbatch, [](int flag) { return flag == 1; }, &d_items, &n_live));
+    if (n_live == 0) return EMME_OK;
+    EMME_TRY(fold_edges_and_pass(c, K_LIN, n, nbatch, M, Mold, nullptr, a, domega, active));
     ScopedSpan s(c, K_NULL);
-    HIP_TRY(launch_lu_inplace(m, nhalf, S1, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
+    HIP_TRY(launch_lu_inplace(m, nhalf, a.S1, d_items, n_live, f.lu_info, f.lu_scratch, c->stream));
     note_lu_launch(c, LU_SYM_INPLACE, 1, 1);
-    HIP_TRY(launch_eigpair_fold_half(n, S1, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
-                                     active, f.lu_info, S2, D2, f.vecs, vecs, f.eig_vecs, f.eig_part, c->stream));
+    HIP_TRY(launch_eigpair_fold_half(n, a.S1, trace_solve_rowmaps(f.lu_scratch, m, nhalf), trace_solve_nb(), d_items, n_live,
+                                     active, f.lu_info, a.S2, a.D2, f.vecs, vecs, f.eig_vecs, f.eig_part, c->stream));
     HIP_TRY(launch_eigpair_fold_combine(n, d_items, n_live / 2, active, M, domega, f.vecs, f.lu_info, f.eig_vecs, f.eig_part, vecs,
                                         tau, resid, info, c->stream));
     return EMME_OK;
@@ -381,7 +377,7 @@ int emme_trace_secant_folded_batch(emme_ctx_t* c, int n, int nbatch, const doubl
         set_error(std::string(who) + ": the order must be even");
         return EMME_EINVAL;
     }
-    if (trace_solve_blocked_lds(n / 2) > 150 * 1024 || null_iterate_lds(n / 2) > 150 * 1024 || c->opt.lu_unblocked != 0) {
+    if (!halves_fit(c, n)) {
         set_error(std::string(who) + ": the half problems need the blocked one-workgroup kernels (order above 1050, or lu_unblocked)");
         return EMME_ECONFIG;
     }

@@ -107,15 +107,9 @@ int search_end(emme_ctx* c, const RootSearch& s, double* roots, int* iters, int*
 // retired behind its fill).  secant: k_eigpair_secant_step on (d_M, d_Mold, d_domega) instead of (d_M, d_Mp).
 int eigpair_step(emme_ctx* c, RootSearch& search, const int* live, bool first, bool secant) {
     const int n = search.n, dim = c->dim;
-    int* slot = nullptr;
-    HIP_TRY(c->d_lu_items.grow(sizeof(int) * n));
-    HIP_TRY(c->lists.take(n, &slot));
     int n_live = 0;
-    for (int b = 0; b < n; ++b)
-        if (live[b] == 1) slot[n_live++] = b;
+    HIP_TRY(stage_live_list(c, c->d_lu_items, live, n, 1, [](int flag) { return flag == 1; }, &n_live));
     if (n_live == 0) return EMME_OK;
-    HIP_TRY(launch_stage_ints(slot, c->d_lu_items, n_live, nullptr, 0, c->stream));
-    HIP_TRY(c->lists.read_on(c->stream));
     return lu_factor_batch(
         c, dim, n, c->d_work, search.lu, secant ? "emme_solve_eigenpairs_secant" : "emme_solve_eigenpairs",
         [&](int i0, int ni, const int* maps, int map_nb, const int* lu_info) -> hipError_t {
@@ -222,7 +216,8 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
         // (d_Mp holds the half problems' S': solve_eigenpairs allocates it exactly where a step can fold, and a step
         // without it is never folded.  The list of the folded step is p_live == 1, which is d_active == 1: k_retire
         // only turns 2 into 0 after the flags were read; the kernels check d_active as well, as the parent's does.)
-        const bool eig_folded = eig && c->eigpair_fold != 0 && c->mirror && old_mirrored && new_mirrored &&
+        const bool pair_mirrored = c->mirror && old_mirrored && new_mirrored;  // both matrices of the secant
+        const bool eig_folded = eig && c->eigpair_fold != 0 && pair_mirrored &&
                                 eigpair_fold_applies(c, c->dim) && !(j == 0 && !search.v0) && !search.set &&
                                 c->d_Mp.bytes() >= batch_bytes(c->dim, n);
         if (eig_folded) {
@@ -242,7 +237,7 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
             EMME_TRY(eigpair_step(c, search, c->p_live.get(), j == 0 && !search.v0, true));
             ScopedSpan s(c, K_OTHER);
             HIP_TRY(launch_copy_active(c->dim, n, c->d_M, c->d_Mold, nullptr, c->d_active, c->stream));
-        } else if (fused_copy && c->mirror && old_mirrored && new_mirrored && fold_applies(c, c->dim)) {
+        } else if (fused_copy && pair_mirrored && fold_applies(c, c->dim)) {
             // both fills mirrored: the even and the odd block instead of the matrix; M_old follows M in the same pass
             EMME_TRY(folded_secant_step(c, c->dim, n, c->d_M, c->d_Mold, c->d_Mold, c->d_work, c->d_Mp, c->d_domega,
                                         c->d_active, c->d_tr, c->d_info, act.data()));

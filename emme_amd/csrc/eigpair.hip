@@ -7,14 +7,14 @@
 //
 // k_eigpair_step: one 512-thread workgroup per live matrix.  The products M v and M' v go a wave per row, rows dealt
 // to the waves in a fixed order (row r to wave r mod 8), every sum in a fixed order and nothing atomic: two runs are
-// bit-identical.  The triangular solves are k_null_iterate's (tri_solve.hpp), on the same LDS layout.
+// bit-identical.  The triangular solves and the workgroup's frame are k_null_iterate's (tri_solve.hpp).
 //
 // k_eigpair_secant_step: the same step for a search that holds two consecutive plain fills M = M(omega_k), M_old =
 // M(omega_k-1) and no derivative: M' v is replaced by (M - M_old) v / (omega_k - omega_k-1).  ONE pass over the rows of
 // both matrices takes the difference entry by entry (two separately rounded products would lose n eps / |domega / omega|
 // near convergence) and gives M v, (M - M_old) v and |M|_F^2 together: no matrix M' is formed, written or read, and
-// there is no separate residual pass.  A sibling kernel and not a template reading of k_eigpair_step, whose code object
-// stays what it was.
+// there is no separate residual pass.  Both kernels are readings of one text, eigpair_step_body<SECANT>: start vector,
+// residual, tau, normalisation and finite check exist once.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -67,90 +67,6 @@ __device__ __forceinline__ double matvec(int n, const double2* mat, const double
     return fro;
 }
 
-__global__ __launch_bounds__(NT) void k_eigpair_step(EigArgs P) {
-    extern __shared__ double2 sm[];
-    __shared__ double s_red[2 * NW];
-    const int n = P.n;
-    double2* v = sm;                  // the iterate
-    double2* w = sm + n;              // M v, then M' v
-    double2* t = sm + 2 * (size_t)n;  // the solves' work vector: u
-    int* rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)n);
-    const int b = P.items ? P.items[blockIdx.x] : blockIdx.x;
-    if (P.active && P.active[b] == 0) return;  // uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double2* out = P.vecs + (size_t)b * n;
-    const double qnan = __builtin_nan("");
-    if (!P.resid_only && P.lu_info && P.lu_info[b] != 0) {  // no factorisation (exactly singular column / time-out)
-        for (int i = tid; i < n; i += NT) out[i] = make_double2(qnan, qnan);
-        if (tid == 0) P.info[b] = P.lu_info[b], P.tau[b] = make_double2(qnan, qnan), P.resid[b] = qnan;
-        return;
-    }
-    // (total of a and of b over the workgroup, in wave order, to every thread)
-    auto block_sum2 = [&](double a, double bb, double& ta, double& tb) {
-        a = wave_sum(a), bb = wave_sum(bb);
-        if (lane == 0) s_red[wave] = a, s_red[NW + wave] = bb;
-        __syncthreads();
-        ta = 0.0, tb = 0.0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) ta += s_red[k], tb += s_red[NW + k];
-        __syncthreads();
-    };
-    Factors F;
-    F.n = n, F.a = P.A + (size_t)b * n * n, F.rowmap = rowmap;
-    F.bA = sm + 3 * (size_t)n + rowmap_slots(n);
-    F.bD = F.bA + 2 * TB * (TB + 1);
-    if (!P.resid_only) {
-        const int* maps = P.maps + (size_t)b * P.nblk * n;
-        for (int x = tid; x < n; x += NT) rowmap[x] = maps[(size_t)(x / P.nb) * n + x];
-    }
-    if (P.first && !P.resid_only) {
-        // v_0 = M^-1 s / |M^-1 s|: the start vector of k_null_iterate
-        for (int i = tid; i < n; i += NT) w[i] = make_double2(1.0 + 0.37 * sin(1.0 + i), 0.21 * cos(2.0 * i));
-        __syncthreads();
-        solve_plain(F, w, t);
-        double s = 0.0, s0, s1;
-        for (int i = tid; i < n; i += NT) s += t[i].x * t[i].x + t[i].y * t[i].y;
-        block_sum2(s, 0.0, s0, s1);
-        const double r = 1.0 / sqrt(s0);
-        for (int i = tid; i < n; i += NT) v[i] = make_double2(t[i].x * r, t[i].y * r);
-    } else {
-        for (int i = tid; i < n; i += NT) v[i] = out[i];
-    }
-    __syncthreads();
-    // ---- the residual of (omega_k, v_k) on the un-factored M ----
-    const double2* Mb = P.M + (size_t)b * n * n;
-    const double fro = matvec<true>(n, Mb, v, w);
-    __syncthreads();
-    double y2 = 0.0, ty2, tfro;
-    for (int i = tid; i < n; i += NT) y2 += w[i].x * w[i].x + w[i].y * w[i].y;
-    block_sum2(y2, fro, ty2, tfro);
-    if (tid == 0) P.resid[b] = sqrt(ty2) / sqrt(tfro);
-    if (P.resid_only) return;  // uniform
-    // ---- the step: w = M' v, u = M^-1 w, tau = v^H u, v <- u / |u| ----
-    (void)matvec<false>(n, P.Mp + (size_t)b * n * n, v, w);
-    __syncthreads();
-    solve_plain(F, w, t);
-    cd tau = mk(0.0, 0.0);
-    double u2 = 0.0;
-    for (int i = tid; i < n; i += NT) {
-        const cd u = mk(t[i].x, t[i].y);
-        tau = tau + conj_(mk(v[i].x, v[i].y)) * u;
-        u2 += u.x * u.x + u.y * u.y;
-    }
-    double tx, ty, tu2, unused;
-    block_sum2(tau.x, tau.y, tx, ty);
-    block_sum2(u2, 0.0, tu2, unused);
-    const double r = 1.0 / sqrt(tu2);
-    bool finite = isfinite(tx) && isfinite(ty) && isfinite(r);
-    for (int i = tid; i < n; i += NT) {
-        const double2 o = make_double2(t[i].x * r, t[i].y * r);
-        out[i] = o;
-        finite = finite && isfinite(o.x) && isfinite(o.y);
-    }
-    const int bad = __syncthreads_or(!finite);
-    if (tid == 0) P.tau[b] = make_double2(tx, ty), P.info[b] = bad ? -6 /* EMME_ENUMERIC */ : 0;
-}
-
 // y = Mat x and yd = (Mat - Old) x in one pass, rows, columns and sums as matvec: the difference is taken per entry
 // before it meets x.  Returns this lane's share of sum |Mat(r, c)|^2 over the wave's rows.
 __device__ __forceinline__ double matvec_diff(int n, const double2* mat, const double2* old, const double2* x, double2* y,
@@ -176,74 +92,72 @@ __device__ __forceinline__ double matvec_diff(int n, const double2* mat, const d
     return fro;
 }
 
-// The secant reading of the step.  P.Mp holds M_old = M(omega_k-1), domega[b] = omega_k - omega_k-1 (device); P.first,
-// items, active, lu_info and the outputs as in k_eigpair_step, P.resid_only is not read (launch_eigpair_resid serves).
-__global__ __launch_bounds__(NT) void k_eigpair_secant_step(EigArgs P, const double2* domega) {
+// The step, plain (SECANT = false: P.Mp is dM/domega, P.resid_only is honoured) or secant (P.Mp holds M_old =
+// M(omega_k-1), domega[b] = omega_k - omega_k-1 on the device, P.resid_only is not read: launch_eigpair_resid serves).
+// One text, two kernels: what differs is the product pass, the division by domega and one term of the finite check.
+template <bool SECANT>
+__device__ __forceinline__ void eigpair_step_body(const EigArgs& P, const double2* domega) {
     extern __shared__ double2 sm[];
-    __shared__ double s_red[2 * NW];
+    __shared__ double s_red[3 * NW];
     const int n = P.n;
-    double2* v = sm;                  // the iterate
-    double2* w = sm + n;              // (M - M_old) v, then that over domega
-    double2* t = sm + 2 * (size_t)n;  // M v until the residual is taken, then the solves' work vector: u
-    int* rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)n);
-    const int b = P.items ? P.items[blockIdx.x] : blockIdx.x;
+    const int b = pick_item(P.items);
     if (P.active && P.active[b] == 0) return;  // uniform
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool resid_only = !SECANT && P.resid_only;
+    const int tid = threadIdx.x;
     double2* out = P.vecs + (size_t)b * n;
-    const double qnan = __builtin_nan("");
-    if (P.lu_info && P.lu_info[b] != 0) {  // no factorisation (exactly singular column / time-out)
-        for (int i = tid; i < n; i += NT) out[i] = make_double2(qnan, qnan);
+    if (!resid_only && P.lu_info && P.lu_info[b] != 0) {  // no factorisation (exactly singular column / time-out)
+        const double qnan = __builtin_nan("");
+        nan_out(out, n);
         if (tid == 0) P.info[b] = P.lu_info[b], P.tau[b] = make_double2(qnan, qnan), P.resid[b] = qnan;
         return;
     }
-    // (total of a and of b over the workgroup, in wave order, to every thread)
-    auto block_sum2 = [&](double a, double bb, double& ta, double& tb) {
-        a = wave_sum(a), bb = wave_sum(bb);
-        if (lane == 0) s_red[wave] = a, s_red[NW + wave] = bb;
-        __syncthreads();
-        ta = 0.0, tb = 0.0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) ta += s_red[k], tb += s_red[NW + k];
-        __syncthreads();
-    };
-    Factors F;
-    F.n = n, F.a = P.A + (size_t)b * n * n, F.rowmap = rowmap;
-    F.bA = sm + 3 * (size_t)n + rowmap_slots(n);
-    F.bD = F.bA + 2 * TB * (TB + 1);
-    const int* maps = P.maps + (size_t)b * P.nblk * n;
-    for (int x = tid; x < n; x += NT) rowmap[x] = maps[(size_t)(x / P.nb) * n + x];
-    if (P.first) {
+    const Frame fr(sm, n, P.A + (size_t)b * n * n);
+    const Factors& F = fr.F;
+    double2* v = fr.x0;  // the iterate
+    double2* w = fr.x1;  // plain: M v, then M' v; secant: (M - M_old) v, then that over domega
+    double2* t = fr.x2;  // the solves' work vector: u (secant: M v until the residual is taken)
+    double one[1], tot[2];
+    if (!resid_only) fr.load_rowmap(P.maps + (size_t)b * P.nblk * n, P.nb);
+    if (P.first && !resid_only) {
         // v_0 = M^-1 s / |M^-1 s|: the start vector of k_null_iterate
-        for (int i = tid; i < n; i += NT) w[i] = make_double2(1.0 + 0.37 * sin(1.0 + i), 0.21 * cos(2.0 * i));
+        for (int i = tid; i < n; i += NT) w[i] = start_vector(i);
         __syncthreads();
         solve_plain(F, w, t);
-        double s = 0.0, s0, s1;
+        double s = 0.0;
         for (int i = tid; i < n; i += NT) s += t[i].x * t[i].x + t[i].y * t[i].y;
-        block_sum2(s, 0.0, s0, s1);
-        const double r = 1.0 / sqrt(s0);
+        const double ws[1] = {wave_sum(s)};
+        block_sum(s_red, ws, one);
+        const double r = 1.0 / sqrt(one[0]);
         for (int i = tid; i < n; i += NT) v[i] = make_double2(t[i].x * r, t[i].y * r);
     } else {
         for (int i = tid; i < n; i += NT) v[i] = out[i];
     }
     __syncthreads();
-    // ---- one pass over M and M_old: M v (the residual of (omega_k, v_k)), (M - M_old) v and |M|_F^2 ----
-    const double fro = matvec_diff(n, P.M + (size_t)b * n * n, P.Mp + (size_t)b * n * n, v, t, w);
+    // ---- the residual of (omega_k, v_k) on the un-factored M; secant: the same pass over M and M_old also gives
+    // (M - M_old) v ----
+    const double2* Mb = P.M + (size_t)b * n * n;
+    const double2* mv = SECANT ? t : w;
+    const double fro = SECANT ? matvec_diff(n, Mb, P.Mp + (size_t)b * n * n, v, t, w) : matvec<true>(n, Mb, v, w);
     __syncthreads();
-    double y2 = 0.0, ty2, tfro;
-    for (int i = tid; i < n; i += NT) y2 += t[i].x * t[i].x + t[i].y * t[i].y;
-    block_sum2(y2, fro, ty2, tfro);
-    if (tid == 0) P.resid[b] = sqrt(ty2) / sqrt(tfro);
-    // ---- the step: w = (M - M_old) v / domega, u = M^-1 w, tau = v^H u, v <- u / |u| ----
-    // (a zero or non-finite domega has no reciprocal: EMME_ENUMERIC below)
-    const double2 dw = domega[b];
-    const double dw2 = dw.x * dw.x + dw.y * dw.y;
-    const cd inv = mk(dw.x / dw2, -dw.y / dw2);
-    for (int i = tid; i < n; i += NT) {
-        const cd q = mk(w[i].x, w[i].y) * inv;
-        w[i] = make_double2(q.x, q.y);
+    double y2 = 0.0;
+    for (int i = tid; i < n; i += NT) y2 += mv[i].x * mv[i].x + mv[i].y * mv[i].y;
+    const double wr[2] = {wave_sum(y2), wave_sum(fro)};
+    block_sum(s_red, wr, tot);
+    if (tid == 0) P.resid[b] = sqrt(tot[0]) / sqrt(tot[1]);
+    if (resid_only) return;  // uniform
+    // ---- the step: w = M' v (secant: (M - M_old) v / domega), u = M^-1 w, tau = v^H u, v <- u / |u| ----
+    cd inv = mk(0.0, 0.0);
+    if (SECANT) {
+        // (a zero or non-finite domega has no reciprocal: EMME_ENUMERIC below)
+        const double2 dw = domega[b];
+        const double dw2 = dw.x * dw.x + dw.y * dw.y;
+        inv = mk(dw.x / dw2, -dw.y / dw2);
+        for (int i = tid; i < n; i += NT) w[i] = d2(mk(w[i].x, w[i].y) * inv);
+    } else {
+        (void)matvec<false>(n, P.Mp + (size_t)b * n * n, v, w);
     }
     __syncthreads();
-    solve_plain(F, w, t);
+    solve_plain(F, w, t);  // (its barriers stand between the sum above and the one below)
     cd tau = mk(0.0, 0.0);
     double u2 = 0.0;
     for (int i = tid; i < n; i += NT) {
@@ -251,10 +165,10 @@ __global__ __launch_bounds__(NT) void k_eigpair_secant_step(EigArgs P, const dou
         tau = tau + conj_(mk(v[i].x, v[i].y)) * u;
         u2 += u.x * u.x + u.y * u.y;
     }
-    double tx, ty, tu2, unused;
-    block_sum2(tau.x, tau.y, tx, ty);
-    block_sum2(u2, 0.0, tu2, unused);
-    const double r = 1.0 / sqrt(tu2);
+    const double wt[3] = {wave_sum(tau.x), wave_sum(tau.y), wave_sum(u2)};
+    double tt[3];
+    block_sum(s_red, wt, tt);
+    const double tx = tt[0], ty = tt[1], r = 1.0 / sqrt(tt[2]);
     bool finite = isfinite(inv.x) && isfinite(inv.y) && isfinite(tx) && isfinite(ty) && isfinite(r);
     for (int i = tid; i < n; i += NT) {
         const double2 o = make_double2(t[i].x * r, t[i].y * r);
@@ -265,20 +179,21 @@ __global__ __launch_bounds__(NT) void k_eigpair_secant_step(EigArgs P, const dou
     if (tid == 0) P.tau[b] = make_double2(tx, ty), P.info[b] = bad ? -6 /* EMME_ENUMERIC */ : 0;
 }
 
-// domega null: k_eigpair_step, else k_eigpair_secant_step
-hipError_t launch(const EigArgs& P, int nitems, hipStream_t stream, const double2* domega = nullptr) {
-    const size_t lds = null_iterate_lds(P.n);
-    if (lds > 150 * 1024) return hipErrorNotSupported;
-    if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
-        const void* kernel = domega ? (const void*)k_eigpair_secant_step : (const void*)k_eigpair_step;
-        const hipError_t ea = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    if (domega)
-        hipLaunchKernelGGL(k_eigpair_secant_step, dim3(nitems), dim3(NT), lds, stream, P, domega);
-    else
-        hipLaunchKernelGGL(k_eigpair_step, dim3(nitems), dim3(NT), lds, stream, P);
-    return hipGetLastError();
+__global__ __launch_bounds__(NT) void k_eigpair_step(EigArgs P) { eigpair_step_body<false>(P, nullptr); }
+__global__ __launch_bounds__(NT) void k_eigpair_secant_step(EigArgs P, const double2* domega) { eigpair_step_body<true>(P, domega); }
+
+// what the three launchers hand a kernel (resid_only: launch_eigpair_resid, which has no factors, flags or outputs
+// beside resid)
+EigArgs eig_args(int n, const double* M, const double* Mp, const double* A_lu, const int* rowmaps, int nb, const int* items,
+                 const int* active, const int* lu_info, double* vecs, double* tau, double* resid, int* info, bool first,
+                 bool resid_only) {
+    EigArgs P{};
+    P.n = n, P.nb = nb, P.nblk = (n + nb - 1) / nb;
+    P.M = (const double2*)M, P.Mp = (const double2*)Mp, P.A = (const double2*)A_lu;
+    P.maps = rowmaps, P.items = items, P.active = active, P.lu_info = lu_info;
+    P.vecs = (double2*)vecs, P.tau = (double2*)tau, P.resid = resid, P.info = info;
+    P.first = first ? 1 : 0, P.resid_only = resid_only ? 1 : 0;
+    return P;
 }
 
 }  // namespace
@@ -288,37 +203,25 @@ hipError_t launch_eigpair_secant_step(int n, const double* M, const double* Mold
                                       const int* lu_info, double* vecs, double* tau, double* resid, int* info, bool first,
                                       hipStream_t stream) {
     if (nitems < 1) return hipSuccess;
-    EigArgs P{};
-    P.n = n, P.nb = nb, P.nblk = (n + nb - 1) / nb;
-    P.M = (const double2*)M, P.Mp = (const double2*)Mold, P.A = (const double2*)A_lu;
-    P.maps = rowmaps, P.items = items, P.active = active, P.lu_info = lu_info;
-    P.vecs = (double2*)vecs, P.tau = (double2*)tau, P.resid = resid, P.info = info;
-    P.first = first ? 1 : 0, P.resid_only = 0;
-    return launch(P, nitems, stream, (const double2*)domega);
+    return launch_dyn_lds(k_eigpair_secant_step, nitems, frame_lds(n), stream,
+                          eig_args(n, M, Mold, A_lu, rowmaps, nb, items, active, lu_info, vecs, tau, resid, info, first, false),
+                          (const double2*)domega);
 }
 
 hipError_t launch_eigpair_step(int n, const double* M, const double* Mp, const double* A_lu, const int* rowmaps, int nb,
                                const int* items, int nitems, const int* active, const int* lu_info, double* vecs,
                                double* tau, double* resid, int* info, bool first, hipStream_t stream) {
     if (nitems < 1) return hipSuccess;
-    EigArgs P{};
-    P.n = n, P.nb = nb, P.nblk = (n + nb - 1) / nb;
-    P.M = (const double2*)M, P.Mp = (const double2*)Mp, P.A = (const double2*)A_lu;
-    P.maps = rowmaps, P.items = items, P.active = active, P.lu_info = lu_info;
-    P.vecs = (double2*)vecs, P.tau = (double2*)tau, P.resid = resid, P.info = info;
-    P.first = first ? 1 : 0, P.resid_only = 0;
-    return launch(P, nitems, stream);
+    return launch_dyn_lds(k_eigpair_step, nitems, frame_lds(n), stream,
+                          eig_args(n, M, Mp, A_lu, rowmaps, nb, items, active, lu_info, vecs, tau, resid, info, first, false));
 }
 
 hipError_t launch_eigpair_resid(int n, const double* M, const int* items, int nitems, const double* vecs, double* resid,
                                 hipStream_t stream) {
     if (nitems < 1) return hipSuccess;
-    EigArgs P{};
-    P.n = n, P.nb = n, P.nblk = 1;
-    P.M = (const double2*)M, P.items = items;
-    P.vecs = (double2*)const_cast<double*>(vecs), P.resid = resid;
-    P.resid_only = 1;
-    return launch(P, nitems, stream);
+    return launch_dyn_lds(k_eigpair_step, nitems, frame_lds(n), stream,
+                          eig_args(n, M, nullptr, nullptr, nullptr, n, items, nullptr, nullptr, const_cast<double*>(vecs), nullptr,
+                                   resid, nullptr, false, true));
 }
 
 }  // namespace emme

@@ -14,6 +14,7 @@
 //                           and S'_s (rows to waves, columns to lanes, as k_eigpair_secant_step), the four solves
 //                           (tri_solve.hpp), this half's dot products
 //   k_eigpair_fold_combine  one workgroup per live chain: K, g, u^, tau, the new vector, the residual, info
+// (which half a workgroup has, the merge of the halves' codes and K: fold_combine.hpp, shared with linstep_fold.hip)
 // Every sum is taken in a fixed order (xor shuffles, then the waves in order), nothing is atomic, and a chain reads
 // nothing of another chain: two runs give the same bits, alone or in a batch.
 #include <hip/hip_runtime.h>
@@ -21,19 +22,18 @@
 #include <cmath>
 
 #include "emme_device.hpp"
+#include "fold_combine.hpp"
 #include "launch.hpp"
-#include "tri_solve.hpp"
 
 namespace emme {
 
 namespace {
 
 using namespace trisolve;
+using namespace fold;
 
 constexpr int NHV = 5;    // vectors a half problem leaves behind: c, a, a', b, y
 constexpr int NHP = 8;    // ... and its sums: u.a, u.b, u.c, u.a', u'.v, u.v, (|S|_F^2, |v_s|^2), unused
-
-__device__ __forceinline__ double2 d2(cd v) { return make_double2(v.x, v.y); }
 
 struct EigFoldHalfArgs {
     int n, m, nb, nblk;   // order of the chain's matrix and of a half problem; rows per panel snapshot and snapshots per
@@ -51,52 +51,27 @@ struct EigFoldHalfArgs {
     double2* part;        // [2 nbatch][NHP]
 };
 
-// (total of six numbers over the workgroup, in wave order, to every thread; v: what every lane of a wave holds of it)
-__device__ __forceinline__ void block_sum6(double* s_red, const double (&v)[6], double (&t)[6]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __syncthreads();
-    if (lane == 0)
-        for (int q = 0; q < 6; ++q) s_red[q * NW + wave] = v[q];
-    __syncthreads();
-    for (int q = 0; q < 6; ++q) {
-        t[q] = 0.0;
-        for (int k = 0; k < NW; ++k) t[q] += s_red[q * NW + k];
-    }
-}
-
 __global__ __launch_bounds__(NT) void k_eigpair_fold_half(EigFoldHalfArgs P) {
     extern __shared__ double2 sm[];
     __shared__ double s_red[6 * NW];
     const int n = P.n, m = P.m;
-    double2* vs = sm;                   // v_s
-    double2* rhs = sm + m;              // the right-hand side of the solve at hand
-    double2* sol = sm + 2 * (size_t)m;  // its solution
-    int* rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)m);
-    const int h = P.items ? P.items[blockIdx.x] : blockIdx.x;
+    const int h = pick_item(P.items);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     if (P.active && P.active[h >> 1] == 0) return;  // uniform
     double2* out = P.part + (size_t)h * NHP;
-    if (P.lu_info[h] != 0) {  // no factorisation: the chain's step fails (k_eigpair_fold_combine)
-        const double qnan = __builtin_nan("");
-        if (tid < NHP) out[tid] = make_double2(qnan, qnan);
-        return;
-    }
-    const int b = h >> 1;
-    const double sgn = (h & 1) ? -1.0 : 1.0;
-    const double2* u = P.edges + ((size_t)b * 4 + (h & 1)) * m;
-    const double2* ud = u + 2 * (size_t)m;
-    const double2* v = P.vecs + (size_t)b * n;
+    if (P.lu_info[h] != 0) return nan_out(out, NHP);  // no factorisation: the chain's step fails (k_eigpair_fold_combine)
+    const Half H(h, P.edges, m);
+    const double sgn = H.sgn;
+    const double2 *u = H.u, *ud = H.ud;
+    const double2* v = P.vecs + (size_t)H.b * n;
     double2* hv = P.hv + (size_t)h * NHV * m;
-    Factors F;
-    F.n = m, F.a = P.A + (size_t)h * m * m, F.rowmap = rowmap;
-    F.bA = sm + 3 * (size_t)m + rowmap_slots(m);
-    F.bD = F.bA + 2 * TB * (TB + 1);
-    const int* maps = P.maps + (size_t)h * P.nblk * m;
-    for (int x = tid; x < m; x += NT) {
-        rowmap[x] = maps[(size_t)(x / P.nb) * m + x];
-        const cd v1 = ld2(&v[x]), v2 = ld2(&v[n - 1 - x]);
-        vs[x] = d2(v1 + sgn * v2);
-    }
+    const Frame fr(sm, m, P.A + (size_t)h * m * m);
+    const Factors& F = fr.F;
+    double2* vs = fr.x0;   // v_s
+    double2* rhs = fr.x1;  // the right-hand side of the solve at hand
+    double2* sol = fr.x2;  // its solution
+    fr.load_rowmap(P.maps + (size_t)h * P.nblk * m, P.nb);
+    for (int x = tid; x < m; x += NT) vs[x] = d2(ld2(&v[x]) + sgn * ld2(&v[n - 1 - x]));
     __syncthreads();
     // ---- one pass over S_s and S'_s: y = S v_s (left behind), z = S' v_s (the first right-hand side), |S|_F^2 ----
     const double2* S = P.S + (size_t)h * m * m;
@@ -148,23 +123,26 @@ __global__ __launch_bounds__(NT) void k_eigpair_fold_half(EigFoldHalfArgs P) {
         uv = uv + ld2(&u[x]) * vx, dv = dv + ld2(&ud[x]) * vx;
         v2 += norm2(vx);
     }
-    double t[6];
+    // (s_red: the solves' barriers stand before the first sum, one of the kernel's own before each of the others)
+    double t[6], t2[2];
     {
         const double w[6] = {wave_sum(dot_a.x), wave_sum(dot_a.y), wave_sum(dot_b.x), wave_sum(dot_b.y),
                              wave_sum(dot_c.x), wave_sum(dot_c.y)};
-        block_sum6(s_red, w, t);
+        block_sum(s_red, w, t);
     }
     if (tid == 0) out[0] = make_double2(t[0], t[1]), out[1] = make_double2(t[2], t[3]), out[2] = make_double2(t[4], t[5]);
+    __syncthreads();
     {
-        const double w[6] = {wave_sum(dot_ap.x), wave_sum(dot_ap.y),wave_sum(dv.x), wave_sum(dv.y), wave_sum(uv.x), wave_sum(uv.y)};
-        block_sum6(s_red, w, t);
+        const double w[6] = {wave_sum(dot_ap.x), wave_sum(dot_ap.y), wave_sum(dv.x), wave_sum(dv.y), wave_sum(uv.x), wave_sum(uv.y)};
+        block_sum(s_red, w, t);
     }
     if (tid == 0) out[3] = make_double2(t[0], t[1]), out[4] = make_double2(t[2], t[3]), out[5] = make_double2(t[4], t[5]);
+    __syncthreads();
     {
-        const double w[6] = {wave_sum(fro), wave_sum(v2), 0.0, 0.0, 0.0, 0.0};
-        block_sum6(s_red, w, t);
+        const double w[2] = {wave_sum(fro), wave_sum(v2)};
+        block_sum(s_red, w, t2);
     }
-    if (tid == 0) out[6] = make_double2(t[0], t[1]), out[7] = make_double2(0.0, 0.0);
+    if (tid == 0) out[6] = make_double2(t2[0], t2[1]), out[7] = make_double2(0.0, 0.0);
 }
 
 struct EigFoldCombineArgs {
@@ -187,7 +165,7 @@ struct EigFoldCombineArgs {
 // EMME_ENUMERIC for a zero or non-finite domega, tau or u^; the vector, tau and resid are NaN for every non-zero info
 __global__ __launch_bounds__(NT) void k_eigpair_fold_combine(EigFoldCombineArgs P) {
     extern __shared__ double2 sm[];
-    __shared__ double s_red[6 * NW];
+    __shared__ double s_red[5 * NW];
     const int n = P.n, m = P.m;
     double2* up = sm;      // u^+
     double2* um = sm + m;  // u^-
@@ -197,14 +175,10 @@ __global__ __launch_bounds__(NT) void k_eigpair_fold_combine(EigFoldCombineArgs 
     double2* out = P.vecs + (size_t)b * n;
     const double qnan = __builtin_nan("");
     auto fail = [&](int code) {
-        for (int i = tid; i < n; i += NT) out[i] = make_double2(qnan, qnan);
+        nan_out(out, n);
         if (tid == 0) P.info[b] = code, P.tau[b] = make_double2(qnan, qnan), P.resid[b] = qnan;
     };
-    int inf = 0;
-    for (int s = 1; s >= 0; --s) {
-        const int i2 = P.lu_info[2 * b + s];
-        if (i2 != 0) inf = i2 > 0 ? i2 + s * m : i2;
-    }
+    const int inf = merge_half_info(P.lu_info[2 * b], P.lu_info[2 * b + 1], m);
     if (inf != 0) return fail(inf);  // uniform
     const double2* pp = P.part + (size_t)(2 * b) * NHP;
     const double2* pm = pp + NHP;
@@ -212,17 +186,16 @@ __global__ __launch_bounds__(NT) void k_eigpair_fold_combine(EigFoldCombineArgs 
     const double2* hm = hp + (size_t)NHV * m;              // ... of the odd block
     const double2* ue = P.edges + (size_t)b * 4 * m;       // u+, then u-
     // (a form of two unnormalised folds is twice the form of the vectors; e+ = e_0, e- = -e_0)
-    auto both = [&](int q) { return 0.5 * (mk(pp[q].x, pp[q].y) + mk(pm[q].x, pm[q].y)); };
     auto first = [&](int k) { return 0.5 * (ld2(&hp[(size_t)k * m]) - ld2(&hm[(size_t)k * m])); };
-    const cd ua = both(0), ub = both(1), uc = both(2), uap = both(3), upv = both(4), uv = both(5);
+    const cd ua = both(pp, pm, 0), ub = both(pp, pm, 1), uc = both(pp, pm, 2), uap = both(pp, pm, 3), upv = both(pp, pm, 4);
+    const cd uv = both(pp, pm, 5);
     const cd ec = first(0), ea = first(1), eap = first(2), eb = first(3);
     const cd vlast = ld2(&out[n - 1]);
     const cd ex = ec + vlast * eap + upv * eb, ux = uc + vlast * uap + upv * ub;
-    const cd k11 = mk(1.0, 0.0) + ea, k12 = eb, k21 = ua, k22 = mk(1.0, 0.0) + ub;
-    const cd det = k11 * k22 - k12 * k21;
-    if (!((det.x != 0.0 || det.y != 0.0) && isfinite(det.x) && isfinite(det.y))) return fail(n + 1);  // uniform
-    const cd rdet = rcp(det);
-    const cd g1 = (k22 * ex - k12 * ux) * rdet, g2 = (k11 * ux - k21 * ex) * rdet;
+    const WoodburyK K(ea, eb, ua, ub);
+    if (!K.ok) return fail(n + 1);  // uniform
+    const cd rdet = rcp(K.det);
+    const cd g1 = (K.k22 * ex - K.k12 * ux) * rdet, g2 = (K.k11 * ux - K.k21 * ex) * rdet;
     // ---- u^+-, tau, |u^|^2, |M v|^2 and the edge terms of |M|_F^2 ----
     const double2* Mb = P.M + (size_t)b * n * n;
     cd tau = mk(0.0, 0.0);
@@ -243,10 +216,10 @@ __global__ __launch_bounds__(NT) void k_eigpair_fold_combine(EigFoldCombineArgs 
         mv2 += norm2(yp) + norm2(ym);
     }
     for (int i = 1 + tid; i < n - 1; i += NT) edge += norm2(ld2(&Mb[(size_t)i * n + n - 1])) - norm2(ld2(&Mb[n - 1 - i]));
-    double t[6];
+    double t[5];
     {
-        const double w[6] = {wave_sum(tau.x), wave_sum(tau.y), wave_sum(u2), wave_sum(mv2), wave_sum(edge), 0.0};
-        block_sum6(s_red, w, t);
+        const double w[5] = {wave_sum(tau.x), wave_sum(tau.y), wave_sum(u2), wave_sum(mv2), wave_sum(edge)};
+        block_sum(s_red, w, t);
     }
     const double tx = 0.5 * t[0], ty = 0.5 * t[1];
     const double r = 1.0 / sqrt(0.5 * t[2]);
@@ -255,7 +228,7 @@ __global__ __launch_bounds__(NT) void k_eigpair_fold_combine(EigFoldCombineArgs 
     const double2 dw = P.domega[b];
     bool finite = isfinite(dw.x) && isfinite(dw.y) && (dw.x != 0.0 || dw.y != 0.0) && isfinite(tx) && isfinite(ty) &&
                   (tx != 0.0 || ty != 0.0) && isfinite(r);
-    // (every read of v_k lies before block_sum6's barriers)
+    // (every read of v_k lies before block_sum's barrier)
     const double hr = 0.5 * r;
     for (int i = tid; i < m; i += NT) {
         const cd wp = mk(up[i].x, up[i].y), wm = mk(um[i].x, um[i].y);
@@ -283,14 +256,7 @@ hipError_t launch_eigpair_fold_half(int n, const double* S_lu, const int* rowmap
     P.A = (const double2*)S_lu, P.maps = rowmaps, P.items = items, P.active = active, P.lu_info = lu_info;
     P.S = (const double2*)S, P.D = (const double2*)Sp, P.edges = (const double2*)edges, P.vecs = (const double2*)vecs;
     P.hv = (double2*)hv, P.part = (double2*)part;
-    const size_t lds = null_iterate_lds(m);
-    if (lds > 150 * 1024) return hipErrorNotSupported;
-    if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
-        const hipError_t ea = hipFuncSetAttribute((const void*)k_eigpair_fold_half, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_eigpair_fold_half, dim3(nitems), dim3(NT), lds, stream, P);
-    return hipGetLastError();
+    return launch_dyn_lds(k_eigpair_fold_half, nitems, frame_lds(m), stream, P);
 }
 
 hipError_t launch_eigpair_fold_combine(int n, const int* items, int nchains, const int* active, const double* M, const double* domega,

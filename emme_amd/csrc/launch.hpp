@@ -328,7 +328,7 @@ const int* trace_solve_rowmaps(const void* scratch, int n, int nbatch);
 // (device list of nitems batch indices, null = all nbatch): the matrices to factor
 hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream,
                                        const int* items = nullptr, int nitems = 0);
-size_t null_iterate_lds(int n);
+size_t null_iterate_lds(int n);  // dynamic LDS of a solve workgroup: trisolve::frame_lds(n) of tri_solve.hpp, for host code
 // right singular vector of the smallest singular value of every matrix, from its in-place LU: vecs [nbatch][n]
 // complex, info 0 / lu_info's code / EMME_ENUMERIC for a non-finite result
 hipError_t launch_null_iterate(int n, const double* A_lu, const int* rowmaps, int nb, const int* items, int nitems,

@@ -15,33 +15,29 @@
 //   k_fold_solve    per half problem: a+- and b+- from the factors of k_lu_inplace (tri_solve.hpp), the three forms
 //                   with S' and the six dot products
 //   k_fold_combine  per chain: K, G, the sum, info
+// (which half a workgroup has, the merge of the halves' codes and K: fold_combine.hpp, shared with eigpair_fold.hip)
 // C is defined from what the pass reads -- for i <= j < m the entries (i, j) and (i, n-1-j) of the upper triangle, the
 // wedge between the diagonal and the anti-diagonal, each once -- so it is centrosymmetric by construction; E is M - C on
 // the last row and column: u_i = M(i, n-1) - M(0, n-1-i), u_{n-1} = (M(n-1, n-1) - M(0, 0)) / 2.
 #include <hip/hip_runtime.h>
 
 #include "emme_device.hpp"
+#include "fold_combine.hpp"
 #include "launch.hpp"
-#include "tri_solve.hpp"
 
 namespace emme {
 
 namespace {
 
 using namespace trisolve;
+using namespace fold;
 
 constexpr int FT = 32;  // tile edge of the fold pass
 
-__device__ __forceinline__ cd ldc(const double2* p) {
-    const double2 v = *p;
-    return mk(v.x, v.y);
-}
-__device__ __forceinline__ double2 d2(cd v) { return make_double2(v.x, v.y); }
-
 // u(k) of one matrix X (upper triangle): the part of column n-1 that the mirror image of row 0 does not explain
 __device__ __forceinline__ cd edge_u(const double2* X, int n, int k) {
-    if (k == n - 1) return 0.5 * (ldc(&X[(size_t)(n - 1) * n + n - 1]) - ldc(&X[0]));
-    return ldc(&X[(size_t)k * n + n - 1]) - ldc(&X[n - 1 - k]);
+    if (k == n - 1) return 0.5 * (ld2(&X[(size_t)(n - 1) * n + n - 1]) - ld2(&X[0]));
+    return ld2(&X[(size_t)k * n + n - 1]) - ld2(&X[n - 1 - k]);
 }
 
 // vecs[b][4][m]: u+, u-, u'+, u'- (unnormalised folds); act2[2b], act2[2b + 1]: the half problems' live flags
@@ -103,7 +99,7 @@ __global__ __launch_bounds__(256) void k_fold_pass(int n, int nfold, const doubl
             const size_t ip = base + (size_t)i * n + j, iq = base + (size_t)i * n + (n - 1 - j);
             const double2 vp = M[ip], vq = M[iq];
             const cd P = mk(vp.x, vp.y), Q = mk(vq.x, vq.y);
-            const cd Pd = (P - ldc(&Mold[ip])) * rdw, Qd = (Q - ldc(&Mold[iq])) * rdw;
+            const cd Pd = (P - ld2(&Mold[ip])) * rdw, Qd = (Q - ld2(&Mold[iq])) * rdw;
             if (Mold_w) Mold_w[ip] = vp, Mold_w[iq] = vq;
             sp = P + Q, sm = P - Q;
             dp[q] = Pd + Qd, dm[q] = Pd - Qd;
@@ -163,32 +159,24 @@ __global__ __launch_bounds__(NT) void k_fold_solve(FoldSolveArgs P) {
     extern __shared__ double2 sm[];
     __shared__ double s_red[6 * NW];
     const int m = P.m;
-    double2* x0 = sm;                  // the right-hand side
-    double2* xa = sm + m;              // a
-    double2* xb = sm + 2 * (size_t)m;  // b
-    int* rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)m);
-    const int h = P.items ? P.items[blockIdx.x] : blockIdx.x;
+    const int h = pick_item(P.items);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     double2* out = P.part + (size_t)h * NPART;
-    if (P.lu_info[h] != 0) {  // no factorisation: the chain's step fails (k_fold_combine)
-        const double qnan = __builtin_nan("");
-        if (tid < NPART) out[tid] = make_double2(qnan, qnan);
-        return;
-    }
-    const double sgn = (h & 1) ? -1.0 : 1.0;
-    const double2* u = P.vecs + ((size_t)(h >> 1) * 4 + (h & 1)) * m;
-    const double2* ud = u + 2 * (size_t)m;
-    Factors F;
-    F.n = m, F.a = P.A + (size_t)h * m * m, F.rowmap = rowmap;
-    F.bA = sm + 3 * (size_t)m + rowmap_slots(m);
-    F.bD = F.bA + 2 * TB * (TB + 1);
-    const int* maps = P.maps + (size_t)h * P.nblk * m;
-    for (int x = tid; x < m; x += NT) rowmap[x] = maps[(size_t)(x / P.nb) * m + x], x0[x] = u[x];
+    if (P.lu_info[h] != 0) return nan_out(out, NPART);  // no factorisation: the chain's step fails (k_fold_combine)
+    const Half H(h, P.vecs, m);
+    const double sgn = H.sgn;
+    const double2 *u = H.u, *ud = H.ud;
+    const Frame fr(sm, m, P.A + (size_t)h * m * m);
+    double2* x0 = fr.x0;  // the right-hand side
+    double2* xa = fr.x1;  // a
+    double2* xb = fr.x2;  // b
+    fr.load_rowmap(P.maps + (size_t)h * P.nblk * m, P.nb);
+    for (int x = tid; x < m; x += NT) x0[x] = u[x];
     __syncthreads();
-    solve_plain(F, x0, xa);
+    solve_plain(fr.F, x0, xa);
     for (int x = tid; x < m; x += NT) x0[x] = make_double2(x == 0 ? sgn : 0.0, 0.0);
     __syncthreads();
-    solve_plain(F, x0, xb);
+    solve_plain(fr.F, x0, xb);
     // the three forms with S': row r by wave r mod NW, the lanes' partial sums by xor shuffles
     const double2* D = P.D + (size_t)h * m * m;
     cd fba = mk(0.0, 0.0), faa = fba, fbb = fba;
@@ -196,7 +184,7 @@ __global__ __launch_bounds__(NT) void k_fold_solve(FoldSolveArgs P) {
         const double2* row = D + (size_t)r * m;
         cd ya = mk(0.0, 0.0), yb = ya;
         for (int c = lane; c < m; c += 64) {
-            const cd d = ldc(&row[c]);
+            const cd d = ld2(&row[c]);
             ya = ya + d * mk(xa[c].x, xa[c].y);
             yb = yb + d * mk(xb[c].x, xb[c].y);
         }
@@ -204,21 +192,10 @@ __global__ __launch_bounds__(NT) void k_fold_solve(FoldSolveArgs P) {
         const cd ar = mk(xa[r].x, xa[r].y), br = mk(xb[r].x, xb[r].y);
         fba = fba + br * ya, faa = faa + ar * ya, fbb = fbb + br * yb;
     }
-    // (total of six numbers over the workgroup, in wave order)
-    auto block_sum6 = [&](const double (&v)[6], double (&t)[6]) {
-        __syncthreads();
-        if (lane == 0)
-            for (int q = 0; q < 6; ++q) s_red[q * NW + wave] = v[q];
-        __syncthreads();
-        for (int q = 0; q < 6; ++q) {
-            t[q] = 0.0;
-            for (int k = 0; k < NW; ++k) t[q] += s_red[q * NW + k];
-        }
-    };
-    double t[6];
+    double t[6], t2[2];
     {
         const double v[6] = {fba.x, fba.y, faa.x, faa.y, fbb.x, fbb.y};  // (every lane of a wave holds the wave's sums)
-        block_sum6(v, t);
+        block_sum(s_red, v, t);
     }
     if (tid == 0) {
         out[6] = make_double2(t[0], t[1]), out[7] = make_double2(t[2], t[3]), out[8] = make_double2(t[4], t[5]);
@@ -227,19 +204,21 @@ __global__ __launch_bounds__(NT) void k_fold_solve(FoldSolveArgs P) {
     // the dot products with u and u'
     cd ua = mk(0.0, 0.0), ub = ua, da = ua, db = ua;
     for (int x = tid; x < m; x += NT) {
-        const cd a = mk(xa[x].x, xa[x].y), bb = mk(xb[x].x, xb[x].y), uu = ldc(&u[x]), dd = ldc(&ud[x]);
+        const cd a = mk(xa[x].x, xa[x].y), bb = mk(xb[x].x, xb[x].y), uu = ld2(&u[x]), dd = ld2(&ud[x]);
         ua = ua + uu * a, ub = ub + uu * bb, da = da + dd * a, db = db + dd * bb;
     }
+    __syncthreads();  // (s_red is read no more)
     {
         const double v[6] = {wave_sum(ua.x), wave_sum(ua.y), wave_sum(ub.x), wave_sum(ub.y), wave_sum(da.x), wave_sum(da.y)};
-        block_sum6(v, t);
+        block_sum(s_red, v, t);
     }
     if (tid == 0) out[2] = make_double2(t[0], t[1]), out[3] = make_double2(t[2], t[3]), out[4] = make_double2(t[4], t[5]);
+    __syncthreads();
     {
-        const double v[6] = {wave_sum(db.x), wave_sum(db.y), 0.0, 0.0, 0.0, 0.0};
-        block_sum6(v, t);
+        const double v[2] = {wave_sum(db.x), wave_sum(db.y)};
+        block_sum(s_red, v, t2);
     }
-    if (tid == 0) out[5] = make_double2(t[0], t[1]);
+    if (tid == 0) out[5] = make_double2(t2[0], t2[1]);
 }
 
 // tr[b] and info[b] of every live chain from its two half problems: tr2 / info2 of the trace kernel, lu_info of the
@@ -250,28 +229,21 @@ __global__ void k_fold_combine(int n, int nbatch, const int* active, const doubl
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= nbatch) return;
     if (active && active[b] == 0) return;
-    const int m = n / 2;
-    int inf = 0;
-    for (int s = 1; s >= 0; --s) {
-        const int i2 = info2[2 * b + s] != 0 ? info2[2 * b + s] : lu_info[2 * b + s];
-        if (i2 != 0) inf = i2 > 0 ? i2 + s * m : i2;
-    }
+    auto half_info = [&](int s) { return info2[2 * b + s] != 0 ? info2[2 * b + s] : lu_info[2 * b + s]; };
+    int inf = merge_half_info(half_info(0), half_info(1), n / 2);
     const double2* pp = part + (size_t)(2 * b) * NPART;
     const double2* pm = pp + NPART;
-    // (a bilinear form of two unnormalised folds is twice the form of the vectors)
-    auto both = [&](int q) { return 0.5 * (mk(pp[q].x, pp[q].y) + mk(pm[q].x, pm[q].y)); };
-    const cd ea = both(0), eb = both(1), ua = both(2), ub = both(3), au = both(4), bu = both(5);
-    const cd fba = both(6), faa = both(7), fbb = both(8);
+    const cd ea = both(pp, pm, 0), eb = both(pp, pm, 1), ua = both(pp, pm, 2), ub = both(pp, pm, 3);
+    const cd au = both(pp, pm, 4), bu = both(pp, pm, 5), fba = both(pp, pm, 6), faa = both(pp, pm, 7), fbb = both(pp, pm, 8);
     const cd g11 = fba + bu * ea + eb * au;  // b^T M' a = b^T C' a + (b.u')(e.a) + (b.e)(u'.a)
     const cd g12 = fbb + 2.0 * (bu * eb);    // b^T M' b
     const cd g21 = faa + 2.0 * (au * ea);    // a^T M' a
-    const cd k11 = mk(1.0, 0.0) + ea, k12 = eb, k21 = ua, k22 = mk(1.0, 0.0) + ub;
-    const cd det = k11 * k22 - k12 * k21;
-    if (inf == 0 && !((det.x != 0.0 || det.y != 0.0) && isfinite(det.x) && isfinite(det.y))) inf = n + 1;
-    const cd trkg = (k22 * g11 - k12 * g21 - k21 * g12 + k11 * g11) * rcp(det);
-    const cd t = mk(tr2[2 * b].x, tr2[2 * b].y) + mk(tr2[2 * b + 1].x, tr2[2 * b + 1].y) + 2.0 * bu - trkg;
+    const WoodburyK K(ea, eb, ua, ub);
+    if (inf == 0 && !K.ok) inf = n + 1;
+    const cd trkg = (K.k22 * g11 - K.k12 * g21 - K.k21 * g12 + K.k11 * g11) * rcp(K.det);
+    const cd t = ld2(&tr2[2 * b]) + ld2(&tr2[2 * b + 1]) + 2.0 * bu - trkg;
     const double qnan = __builtin_nan("");
-    tr[b] = inf != 0 ? make_double2(qnan, qnan) : make_double2(t.x, t.y);
+    tr[b] = inf != 0 ? make_double2(qnan, qnan) : d2(t);
     info[b] = inf;
 }
 
@@ -303,14 +275,7 @@ hipError_t launch_fold_solve(int m, const double* S_lu, const int* rowmaps, int 
     P.m = m, P.nb = nb, P.nblk = (m + nb - 1) / nb;
     P.A = (const double2*)S_lu, P.maps = rowmaps, P.items = items, P.lu_info = lu_info;
     P.D = (const double2*)Sp, P.vecs = (const double2*)vecs, P.part = (double2*)part;
-    const size_t lds = null_iterate_lds(m);
-    if (lds > 150 * 1024) return hipErrorNotSupported;
-    if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
-        const hipError_t ea = hipFuncSetAttribute((const void*)k_fold_solve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_fold_solve, dim3(nitems), dim3(NT), lds, stream, P);
-    return hipGetLastError();
+    return launch_dyn_lds(k_fold_solve, nitems, frame_lds(m), stream, P);
 }
 
 hipError_t launch_fold_combine(int n, int nbatch, const int* active, const double* tr2, const int* info2, const int* lu_info,

@@ -15,7 +15,8 @@
 // 1024-thread workgroup per matrix: the non-transposed ones in dot form (a wave per row of a 16-row block,
 // rows are contiguous), the transposed ones in axpy form (a thread per column, the 16 rows of the block are
 // contiguous across threads), the 16 x 16 triangles by one wave with the block's entries in registers.  The solves
-// themselves live in tri_solve.hpp, which k_eigpair_step (eigpair.hip) reads too.
+// and the workgroup's frame (LDS layout, row map, start vector, sums) live in tri_solve.hpp, which the eigenpair step
+// kernels (eigpair.hip) and the folded steps' solve kernels (linstep_fold.hip, eigpair_fold.hip) read too.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -28,7 +29,7 @@ namespace emme {
 
 namespace {
 
-using namespace trisolve;  // NT, NW, TB, ld2, conj_, wave_sum and the triangular solves (tri_solve.hpp)
+using namespace trisolve;  // the frame of a solve workgroup and the triangular solves (tri_solve.hpp)
 
 struct NullArgs {
     int n, nb, nblk;       // order; rows per panel snapshot and snapshots per matrix of the factorisation
@@ -43,46 +44,37 @@ struct NullArgs {
 
 __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
     extern __shared__ double2 sm[];
-    __shared__ double s_red[2 * NW + 2];
+    __shared__ double s_red[2 * NW];
     const int n = P.n;
-    double2* v = sm;       // the iterate / right-hand side
-    double2* t = sm + n;   // work vector
-    double2* o = sm + 2 * (size_t)n;  // the direction before the sweep
-    int* rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)n);
-    const int b = P.items ? P.items[blockIdx.x] : blockIdx.x;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = pick_item(P.items);
+    const int tid = threadIdx.x;
     double2* out = P.vecs + (size_t)b * n;
     if (P.lu_info && P.lu_info[b] != 0) {  // no factorisation (exactly singular column / time-out): no vector
-        for (int i = tid; i < n; i += NT) out[i] = make_double2(__builtin_nan(""), __builtin_nan(""));
+        nan_out(out, n);
         if (tid == 0) P.info[b] = P.lu_info[b];
         return;
     }
-    const double2* a = P.A + (size_t)b * n * n;
-    const int* maps = P.maps + (size_t)b * P.nblk * n;
-    for (int x = tid; x < n; x += NT) rowmap[x] = maps[(size_t)(x / P.nb) * n + x];
-    // the start vector of the host version (host_driver.cpp): no symmetry that M's null vector could be orthogonal to
-    for (int i = tid; i < n; i += NT) v[i] = make_double2(1.0 + 0.37 * sin(1.0 + i), 0.21 * cos(2.0 * i));
+    const Frame fr(sm, n, P.A + (size_t)b * n * n);
+    const Factors& F = fr.F;
+    double2* v = fr.x0;  // the iterate / right-hand side
+    double2* t = fr.x1;  // work vector
+    double2* o = fr.x2;  // the direction before the sweep
+    const int* rowmap = fr.rowmap;
+    fr.load_rowmap(P.maps + (size_t)b * P.nblk * n, P.nb);
+    for (int i = tid; i < n; i += NT) v[i] = start_vector(i);
     __syncthreads();
 
-    // v <- v / |v|; returns |<old, v>| for the caller's `old` (per-thread elements i = tid + k NT)
+    // v <- v / |v|; ends on a barrier (which is also the one block_sum's next call is owed)
     auto normalise = [&]() {
         double s = 0.0;
         for (int i = tid; i < n; i += NT) s += v[i].x * v[i].x + v[i].y * v[i].y;
-        s = wave_sum(s);
-        if (lane == 0) s_red[wave] = s;
-        __syncthreads();
-        double tot = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) tot += s_red[w];
-        const double r = 1.0 / sqrt(tot);
+        const double w[1] = {wave_sum(s)};
+        double tot[1];
+        block_sum(s_red, w, tot);
+        const double r = 1.0 / sqrt(tot[0]);
         for (int i = tid; i < n; i += NT) v[i] = make_double2(v[i].x * r, v[i].y * r);
         __syncthreads();
     };
-    // the triangular solves, pipelined over blocks of TB = 16 unknowns: tri_solve.hpp
-    Factors F;
-    F.n = n, F.a = a, F.rowmap = rowmap;
-    F.bA = sm + 3 * (size_t)n + rowmap_slots(n);  // [2][TB][TB + 1] coupling with the previous block
-    F.bD = F.bA + 2 * TB * (TB + 1);              // [2][TB][TB + 1] the block's own triangle
     // z = M^-H b:  U^H w = b, L^H z' = w, z = P^T z'
     auto solve_h = [&]() {
         solve_tri<true, false>(F, v);
@@ -100,25 +92,19 @@ __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
     };
 
     normalise();
-    int sweeps = 0;
     for (int it = 0; it < P.max_sweeps; ++it) {
         for (int i = tid; i < n; i += NT) o[i] = v[i];  // (each thread reads back only what it wrote)
         solve_h();
         normalise();
         solve_n();
         normalise();
-        ++sweeps;
         // |<old, v>| -> 1 when the direction has stopped moving
         cd ov = mk(0.0, 0.0);
         for (int i = tid; i < n; i += NT) ov = ov + conj_(mk(o[i].x, o[i].y)) * mk(v[i].x, v[i].y);
-        ov.x = wave_sum(ov.x), ov.y = wave_sum(ov.y);
-        if (lane == 0) s_red[wave] = ov.x, s_red[NW + wave] = ov.y;
-        __syncthreads();
-        double ox = 0.0, oy = 0.0;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) ox += s_red[w], oy += s_red[NW + w];
-        __syncthreads();
-        const double overlap = sqrt(ox * ox + oy * oy);
+        const double w[2] = {wave_sum(ov.x), wave_sum(ov.y)};
+        double tot[2];
+        block_sum(s_red, w, tot);  // (the next one stands behind the barriers of solve_h)
+        const double overlap = sqrt(tot[0] * tot[0] + tot[1] * tot[1]);
         if (it >= 1 && !(fabs(1.0 - overlap) > 1e-14)) break;  // uniform (a NaN ends the loop too)
     }
     bool finite = true;
@@ -128,7 +114,6 @@ __global__ __launch_bounds__(NT) void k_null_iterate(NullArgs P) {
     }
     const int bad = __syncthreads_or(!finite);
     if (tid == 0) P.info[b] = bad ? -6 /* EMME_ENUMERIC */ : 0;
-    (void)sweeps;
 }
 
 // Orders above the blocked factorisations' reach (n > 1024): plain right-looking partial-pivot LU in place, one
@@ -201,21 +186,12 @@ __global__ __launch_bounds__(NT) void k_lu_unblocked_inplace(int n, double2* A, 
 
 }  // namespace
 
-size_t null_iterate_lds(int n) {
-    return (size_t)3 * n * sizeof(double2) + (((size_t)n * sizeof(int) + 15) / 16) * 16 + (size_t)4 * TB * (TB + 1) * sizeof(double2);
-}
+size_t null_iterate_lds(int n) { return frame_lds(n); }
 
 hipError_t launch_lu_unblocked_inplace(int n, int nbatch, double* A, int* maps, int* info, hipStream_t stream,
                                        const int* items, int nitems) {
     const size_t lds = (size_t)n * sizeof(double2) + (size_t)n * sizeof(int);
-    if (lds > 150 * 1024) return hipErrorNotSupported;
-    if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
-        const hipError_t ea = hipFuncSetAttribute((const void*)k_lu_unblocked_inplace, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_lu_unblocked_inplace, dim3(items ? nitems : nbatch), dim3(NT), lds, stream, n, (double2*)A, maps,
-                       info, items);
-    return hipGetLastError();
+    return launch_dyn_lds(k_lu_unblocked_inplace, items ? nitems : nbatch, lds, stream, n, (double2*)A, maps, info, items);
 }
 
 hipError_t launch_null_iterate(int n, const double* A_lu, const int* rowmaps, int nb, const int* items, int nitems,
@@ -229,14 +205,7 @@ hipError_t launch_null_iterate(int n, const double* A_lu, const int* rowmaps, in
     P.vecs = (double2*)vecs;
     P.info = info;
     P.max_sweeps = max_sweeps;
-    const size_t lds = null_iterate_lds(n);
-    if (lds > 150 * 1024) return hipErrorNotSupported;
-    if (lds > 48 * 1024) {  // (beyond the default dynamic-LDS limit only)
-        const hipError_t ea = hipFuncSetAttribute((const void*)k_null_iterate, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (ea != hipSuccess) return ea;
-    }
-    hipLaunchKernelGGL(k_null_iterate, dim3(nitems), dim3(NT), lds, stream, P);
-    return hipGetLastError();
+    return launch_dyn_lds(k_null_iterate, nitems, null_iterate_lds(n), stream, P);
 }
 
 }  // namespace emme

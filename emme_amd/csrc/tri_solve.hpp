@@ -1,7 +1,9 @@
-// tri_solve.hpp -- the pipelined one-vector triangular solves on an in-place partial-pivot LU (P M = L U, rows never
-// moved), shared by k_null_iterate (nullspace.hip) and k_eigpair_step (eigpair.hip).  Device code, one 512-thread
-// workgroup per matrix; both kernels carve their LDS as null_iterate_lds(n) lays it out: three vectors of n complex,
-// the row map, then the four staged 16 x 16 coefficient blocks.
+// tri_solve.hpp -- the frame of a workgroup that solves on an in-place partial-pivot LU (P M = L U, rows never moved):
+// k_null_iterate (nullspace.hip), the two step kernels of eigpair.hip, k_fold_solve (linstep_fold.hip) and
+// k_eigpair_fold_half (eigpair_fold.hip).  Device code, one 512-thread workgroup per matrix.  What the five share stands
+// here once: the LDS layout and its size (Frame, frame_lds), the item pick, the row-map load, the start vector, the NaN
+// fill, the workgroup sum (block_sum), the host launch with dynamic LDS (launch_dyn_lds), and below them the pipelined
+// one-vector triangular solves.
 //
 // One right-hand side is a chain of n dependent steps whatever one does; what can be taken OFF that chain is
 // everything else.  Per stage (one block of 16 unknowns) the workgroup splits into
@@ -30,6 +32,7 @@ __device__ __forceinline__ cd ld2(const double2* p) {
     const double2 v = *p;
     return mk(v.x, v.y);
 }
+__device__ __forceinline__ double2 d2(cd v) { return make_double2(v.x, v.y); }
 __device__ __forceinline__ cd conj_(cd a) { return mk(a.x, -a.y); }
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll
@@ -56,6 +59,74 @@ struct Factors {
     double2* bA;        // LDS [2][TB][TB + 1] coupling with the previous block
     double2* bD;        // LDS [2][TB][TB + 1] the block's own triangle
 };
+
+// ---- the frame ------------------------------------------------------------------------------------------------------
+// The dynamic LDS of a solve workgroup on a matrix of order n: three vectors of n complex, the row map, the four staged
+// 16 x 16 coefficient blocks.  frame_lds(n) is its size in bytes (null_iterate_lds(n) of launch.hpp, for host code).
+__host__ __device__ constexpr size_t frame_lds(int n) {
+    return (3 * (size_t)n + rowmap_slots(n) + 4 * TB * (TB + 1)) * sizeof(double2);
+}
+struct Frame {
+    double2 *x0, *x1, *x2;  // the three vectors
+    int* rowmap;
+    Factors F;  // on `a`, this row map and the staging blocks
+    __device__ __forceinline__ Frame(double2* sm, int n, const double2* a) {
+        x0 = sm, x1 = sm + n, x2 = sm + 2 * (size_t)n;
+        rowmap = reinterpret_cast<int*>(sm + 3 * (size_t)n);
+        F.n = n, F.a = a, F.rowmap = rowmap;
+        F.bA = sm + 3 * (size_t)n + rowmap_slots(n);
+        F.bD = F.bA + 2 * TB * (TB + 1);
+    }
+    // the row order of a finished factorisation from its panel snapshots (maps_of_item: [ceil(n / nb)][n], nb rows per
+    // snapshot): logical row x is where the snapshot of its own panel has it.  No barrier.  (Runs once, at most four
+    // trips: not worth the unrolled copies of the integer division.)
+    __device__ __forceinline__ void load_rowmap(const int* maps_of_item, int nb) const {
+#pragma unroll 1
+        for (int x = threadIdx.x; x < F.n; x += NT) rowmap[x] = maps_of_item[(size_t)(x / nb) * F.n + x];
+    }
+};
+
+// the batch item of this workgroup: the launch's list, or the workgroup's own index
+__device__ __forceinline__ int pick_item(const int* items) { return items ? items[blockIdx.x] : blockIdx.x; }
+// s of include/emme_hip.h (the start vector of the host version, host_driver.cpp): no symmetry that a null vector of M
+// could be orthogonal to
+__device__ __forceinline__ double2 start_vector(int i) { return make_double2(1.0 + 0.37 * sin(1.0 + i), 0.21 * cos(2.0 * i)); }
+// out[0 .. count) = NaN: what an item without a factorisation leaves behind
+__device__ __forceinline__ void nan_out(double2* out, int count) {
+    const double qnan = __builtin_nan("");
+    for (int i = threadIdx.x; i < count; i += NT) out[i] = make_double2(qnan, qnan);
+}
+
+// t[q] = the total of v[q] over the waves of the workgroup, q < K, added in wave order, to every thread.  v: this
+// wave's numbers (lane 0's are taken: the caller has summed over the lanes, wave_sum).  s_red: K * NW doubles of LDS.
+// Barriers: ONE, between the waves' writes and everybody's reads.  Before the call the caller owes s_red a barrier that
+// every thread has passed since the previous block_sum on it returned (any __syncthreads(), a solve's included); after
+// it the totals are in registers and no barrier has been passed since the reads -- LDS written before the call is
+// visible to every thread, what a thread writes after it is not until the caller's next barrier.
+template <int K>
+__device__ __forceinline__ void block_sum(double* s_red, const double (&v)[K], double (&t)[K]) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0)
+        for (int q = 0; q < K; ++q) s_red[q * NW + wave] = v[q];
+    __syncthreads();
+    for (int q = 0; q < K; ++q) {
+        t[q] = 0.0;
+        for (int k = 0; k < NW; ++k) t[q] += s_red[q * NW + k];
+    }
+}
+
+// Host: launch `kernel` on `grid` workgroups of NT threads with `lds` bytes of dynamic LDS -- not above 150 KiB
+// (hipErrorNotSupported), the attribute set beyond the default limit of 48 KiB only.
+template <class... Params, class... Args>
+hipError_t launch_dyn_lds(void (*kernel)(Params...), int grid, size_t lds, hipStream_t stream, Args... args) {
+    if (lds > 150 * 1024) return hipErrorNotSupported;
+    if (lds > 48 * 1024) {
+        const hipError_t ea = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (ea != hipSuccess) return ea;
+    }
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(NT), lds, stream, args...);
+    return hipGetLastError();
+}
 
 // x: right-hand side on entry, solution on exit (LDS, indexed by equation = unknown).  Called by all NT threads; ends
 // on a barrier.
