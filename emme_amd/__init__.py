@@ -10,7 +10,7 @@ from ._lib import (EmmeError, Params, Profile, Context, params_from_json, params
                    set_default_options, FILL_AUTO, FILL_UNION, FILL_LANES, comm_available,
                    gather_pack, gather_unpack, Contour, contour_default, contour_eigs, elementary, integrand,
                    ELEMENTARY, FORM_F, FORM_F_DF, FORM_SPLIT, FORM_W, TILE_SHAPES_ES15, TILE_SHAPES_ALL,
-                   DERIV_CACHE_SHAPES_ES15, DERIV_CACHE_SHAPES_ALL, params_same_shape, run_json_lockstep, scan_plan, last_error,
+                   DERIV_CACHE_SHAPES_ES15, DERIV_CACHE_SHAPES_ALL, MIRROR_SHAPES_ES15, MIRROR_SHAPES_ALL, params_same_shape, run_json_lockstep, scan_plan, last_error,
                    neighbour_sets, vector_parity)
 
 __all__ = ["EmmeError", "Params", "Profile", "Context", "params_from_json", "params_from_dict",
@@ -19,5 +19,5 @@ __all__ = ["EmmeError", "Params", "Profile", "Context", "params_from_json", "par
            "set_default_options", "FILL_AUTO", "FILL_UNION", "FILL_LANES", "comm_available", "gather_pack",
            "gather_unpack", "Contour", "contour_default", "contour_eigs", "elementary", "integrand", "ELEMENTARY",
            "FORM_F", "FORM_F_DF", "FORM_SPLIT", "FORM_W", "TILE_SHAPES_ES15", "TILE_SHAPES_ALL",
-           "DERIV_CACHE_SHAPES_ES15", "DERIV_CACHE_SHAPES_ALL", "params_same_shape", "run_json_lockstep", "scan_plan", "last_error",
+           "DERIV_CACHE_SHAPES_ES15", "DERIV_CACHE_SHAPES_ALL", "MIRROR_SHAPES_ES15", "MIRROR_SHAPES_ALL", "params_same_shape", "run_json_lockstep", "scan_plan", "last_error",
            "neighbour_sets", "vector_parity"]

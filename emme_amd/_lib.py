@@ -177,6 +177,9 @@ def load():
     if hasattr(lib, "emme_ctx_set_mirror_pairs"):  # (an older library loaded through EMME_LIB for an A/B has neither)
         lib.emme_ctx_set_mirror_pairs.argtypes = [P, C.c_int]
         lib.emme_ctx_get_mirror_pairs.argtypes = [P]
+    if hasattr(lib, "emme_ctx_set_mirror_shapes"):  # (an older library loaded through EMME_LIB for an A/B has neither)
+        lib.emme_ctx_set_mirror_shapes.argtypes = [P, C.c_int]
+        lib.emme_ctx_get_mirror_shapes.argtypes = [P]
     if hasattr(lib, "emme_ctx_set_lu_fold"):  # (an older library loaded through EMME_LIB for an A/B has none)
         lib.emme_ctx_set_lu_fold.argtypes = [P, C.c_int]
         lib.emme_ctx_get_lu_fold.argtypes = [P]
@@ -540,6 +543,9 @@ TILE_SHAPES_ALL = 1
 # emme_ctx_set_deriv_cache_shapes (include/emme_hip.h)
 DERIV_CACHE_SHAPES_ES15 = 0
 DERIV_CACHE_SHAPES_ALL = 1
+# emme_ctx_set_mirror_shapes (include/emme_hip.h)
+MIRROR_SHAPES_ES15 = 0
+MIRROR_SHAPES_ALL = 1
 
 
 def comm_available() -> bool:
@@ -645,12 +651,14 @@ class Context:
     def __init__(self, params: Params, device: int = -1, **options):
         """options: fields of emme_options_t (node_cache_gb, cache_min_batch, fill, lu_split, ...); lu_fold (0 / 1): the
         folded trace-secant step, which is a setter of the context (set_lu_fold); eigpair_fold (0 / 1): the folded secant
-        eigenpair step, likewise (set_eigpair_fold)."""
+        eigenpair step, likewise (set_eigpair_fold); mirror_shapes (MIRROR_SHAPES_ES15 / MIRROR_SHAPES_ALL): which shapes
+        mirror on a symmetric grid, likewise (set_mirror_shapes)."""
         self.lib = load()
         self.params = params
         h = C.c_void_p()
         lu_fold = options.pop("lu_fold", None)
         eigpair_fold = options.pop("eigpair_fold", None)
+        mirror_shapes = options.pop("mirror_shapes", None)
         o = default_options(**options)
         _check(self.lib.emme_ctx_create_ex(C.byref(params), device, C.byref(o), C.byref(h)))
         self.h = h
@@ -659,6 +667,8 @@ class Context:
             self.set_lu_fold(lu_fold)
         if eigpair_fold is not None:
             self.set_eigpair_fold(eigpair_fold)
+        if mirror_shapes is not None:
+            self.set_mirror_shapes(mirror_shapes)
 
     def options(self) -> Options:
         o = Options()
@@ -699,8 +709,20 @@ class Context:
 
     def set_mirror_pairs(self, on: bool) -> None:
         """Fill one pair of every mirror-image couple (i, j) / (N-1-j, N-1-i) on symmetric grids (DESIGN.md §5.0c;
-        default on, electrostatic GK15 on the tiled cache only).  A layout setting: rejected once the node cache exists."""
+        default on; electrostatic GK15 on the tiled cache, other shapes under set_mirror_shapes).  A layout setting: rejected once the node cache exists."""
         _check(self.lib.emme_ctx_set_mirror_pairs(self.h, 1 if on else 0))
+
+    def set_mirror_shapes(self, shapes: int) -> None:
+        """Which shapes mirror on a symmetric grid: MIRROR_SHAPES_ES15 (default: electrostatic GK15 only) or
+        MIRROR_SHAPES_ALL (electromagnetic and GK31 contexts on the tiled cache as well).  A layout
+        setting: rejected once the node cache exists."""
+        _check(self.lib.emme_ctx_set_mirror_shapes(self.h, int(shapes)))
+
+    def mirror_shapes(self) -> int:
+        v = self.lib.emme_ctx_get_mirror_shapes(self.h)
+        if v < 0:
+            _check(v)
+        return v
 
     def set_lu_fold(self, on) -> None:
         """The folded trace-secant step (default on): steps of solve_roots whose two fills ran mirrored,

@@ -54,8 +54,8 @@ struct AsmArgs {
     unsigned int count_lo, count_hi;  // k_assemble_coop: run only if count_lo <= list length < count_hi
     int skip_lost;  // LIST mode: integrals of a matrix whose status flag is already set are skipped
     const unsigned char* tile_poison[2];  // tiled cache: tiles that hold a poisoned (pair, interval) block, per class
-    int mirror;  // LIST mode, electrostatic: `pairs` holds one pair of every mirror-image couple -- an
-                 // integral is scattered to (N-1-j, N-1-i) too and its intervals count twice
+    int mirror;  // LIST mode: `pairs` holds one pair of every mirror-image couple -- an integral
+                 // is scattered to (N-1-j, N-1-i) too, in the block of its moment, and its intervals count twice
 };
 
 // Value of the integrand at one quadrature node when a node-record cache may hold the
@@ -315,10 +315,24 @@ __global__ __launch_bounds__(256, EMME_ASM_MIN_WAVES) void k_assemble(AsmArgs A)
                         store(j, i + N, -v);
                         store(i + N, j, -v);
                         store(j + N, i, v);
+                        if (LIST && A.mirror && i + j != N - 1) {  // (the mirror image keeps i < j: the same signs)
+                            const int i2 = N - 1 - j, j2 = N - 1 - i;
+                            store(i2, j2 + N, v);
+                            store(j2, i2 + N, -v);
+                            store(i2 + N, j2, -v);
+                            store(j2 + N, i2, v);
+                            item_intervals *= 2;
+                        }
                     } else {
                         const cd v = P.dx * kap;
                         store(i + N, j + N, v);
                         store(j + N, i + N, v);
+                        if (LIST && A.mirror && i + j != N - 1) {
+                            const int i2 = N - 1 - j, j2 = N - 1 - i;
+                            store(i2 + N, j2 + N, v);
+                            store(j2 + N, i2 + N, v);
+                            item_intervals *= 2;
+                        }
                     }
                 }
                 if (LIST && lane_in_group == 0) {  // the batch index changes with the item
@@ -543,10 +557,24 @@ __global__ __launch_bounds__(BT) void k_assemble_coop(AsmArgs A) {
                 store(j, i + N, -v);
                 store(i + N, j, -v);
                 store(j + N, i, v);
+                if (A.mirror && i + j != N - 1) {  // (the mirror image keeps i < j: the same signs)
+                    const int i2 = N - 1 - j, j2 = N - 1 - i;
+                    store(i2, j2 + N, v);
+                    store(j2, i2 + N, -v);
+                    store(i2 + N, j2, -v);
+                    store(j2 + N, i2, v);
+                    n_intervals *= 2;
+                }
             } else {
                 const cd v = P.dx * kap;
                 store(i + N, j + N, v);
                 store(j + N, i + N, v);
+                if (A.mirror && i + j != N - 1) {
+                    const int i2 = N - 1 - j, j2 = N - 1 - i;
+                    store(i2 + N, j2 + N, v);
+                    store(j2 + N, i2 + N, v);
+                    n_intervals *= 2;
+                }
             }
             if (A.intervals) atomicAdd(&A.intervals[b], (unsigned long long)n_intervals);
             if (isbad) A.status[b] = 1;
@@ -626,8 +654,7 @@ hipError_t launch_assemble_list(const AssembleLaunch& L, const unsigned long lon
     A.intervals = L.intervals;
     A.status = L.status;
     A.skip_lost = L.skip_lost;
-    if (L.mirror && L.P.nm != 1) return hipErrorInvalidValue;  // (only electrostatic integrals have mirror entries)
-    A.mirror = L.mirror;
+    A.mirror = L.mirror;  // (all three moments have mirror entries: DESIGN.md 5.0d)
     A.worklist = worklist;
     A.worklist_count = count;
     A.folded = folded ? 1 : 0;

@@ -226,7 +226,7 @@ struct DenseArgs {
     int nch_launch;             // chunks this launch serves (chunk0 .. chunk0 + nch_launch - 1)
     int tile_major;             // task order: the chunks of a tile group back to back on one XCD (else chunk-major)
     unsigned int* overflow;     // [nbatch] integrals handed over because a level list was full (null: not counted)
-    int mirror;                 // electrostatic GK15: `pairs` holds one pair of every mirror-image couple
+    int mirror;                 // `pairs` holds one pair of every mirror-image couple
 };
 
 // ---- the fill: level by level ----------------------------------------------------------------------
@@ -932,7 +932,7 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 const cd v = (-(pair_weight(i, j, N) * P.dx)) * kap;
                 store(i, j, v, rdw);
                 store(j, i, v, rdw);
-                if (PTS == 15 && A.mirror && i + j != N - 1) {
+                if (A.mirror && i + j != N - 1) {
                     // the mirror-image pair (N-1-j, N-1-i) of a symmetric grid has this integral: the same kappa
                     // under its own weight, and the intervals the reference would have spent on it
                     const int i2 = N - 1 - j, j2 = N - 1 - i;
@@ -945,21 +945,31 @@ __global__ __launch_bounds__(256, EMME_DENSE_MIN_WAVES) void k_assemble_dense(De
                 // blocks A (m = 0), B and its mirrors (m = 1), D (m = 2): include/solver.h:472-509
                 const double de = A.tab[i] - A.tab[j], dg = A.tab[N + i] - A.tab[N + j];
                 kap = kap + kappa_e(mom, P, de, dg, mk(omw.x, omw.y));
-                if (mom == 0) {
-                    const cd v = (-(pair_weight(i, j, N) * P.dx)) * kap;
-                    store(i, j, v, rdw);
-                    store(j, i, v, rdw);
-                } else if (mom == 1) {
-                    const cd v = P.dx * kap;
-                    store(i, j + N, v, rdw);
-                    store(j, i + N, -v, rdw);
-                    store(i + N, j, -v, rdw);
-                    store(j + N, i, v, rdw);
-                } else {
-                    const cd v = P.dx * kap;
-                    store(i + N, j + N, v, rdw);
-                    store(j + N, i + N, v, rdw);
+                // On a mirrored list the pair (N-1-j, N-1-i) has this kappa in all three blocks (kappa_e reads the pair
+                // through eta_i - eta_j and g_i - g_j, which the mirror image keeps, and it keeps i < j: block B's signs
+                // carry over): a second trip of the same stores, and the intervals once more
+                const int images = (A.mirror && i + j != N - 1) ? 2 : 1;
+                int ii = i, jj = j;
+#pragma unroll 1
+                for (int im = 0; im < images; ++im) {
+                    if (mom == 0) {
+                        const cd v = (-(pair_weight(ii, jj, N) * P.dx)) * kap;
+                        store(ii, jj, v, rdw);
+                        store(jj, ii, v, rdw);
+                    } else if (mom == 1) {
+                        const cd v = P.dx * kap;
+                        store(ii, jj + N, v, rdw);
+                        store(jj, ii + N, -v, rdw);
+                        store(ii + N, jj, -v, rdw);
+                        store(jj + N, ii, v, rdw);
+                    } else {
+                        const cd v = P.dx * kap;
+                        store(ii + N, jj + N, v, rdw);
+                        store(jj + N, ii + N, v, rdw);
+                    }
+                    ii = N - 1 - j, jj = N - 1 - i;
                 }
+                if (images == 2) my_intervals += (unsigned long long)s_count[wave][r][lane];
             }
         }
     }
@@ -1110,8 +1120,7 @@ hipError_t launch_assemble_dense(const AssembleLaunch& L, const NodeCacheView& c
     const int ntiles = (L.npairs + TILE_PAIRS - 1) / TILE_PAIRS;
     const int ntg = (ntiles + 3) / 4;
     const int nm = L.P.dim == L.P.N ? 1 : 3;
-    if (L.mirror && (nm != 1 || L.gk_points != 15)) return hipErrorInvalidValue;  // (only electrostatic GK15 writes mirrors)
-    A.mirror = L.mirror;
+    A.mirror = L.mirror;  // (every instantiation writes mirrors: DESIGN.md 5.0c, 5.0d)
     if (nm == 3) {  // electromagnetic (64-entry level lists only; tile-major, XCD-aware order)
         const dim3 grid((unsigned)((long)((ntg + 7) / 8) * 8 * A.nchunks));
         if (L.gk_points == 31)

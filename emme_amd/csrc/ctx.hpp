@@ -83,7 +83,9 @@ struct emme_ctx {
     // order as d_pairs) and the result section writes both.  Every other kernel family keeps d_pairs.
     int npairs_half = 0;
     DeviceBuffer<ushort2> d_pairs_half;
-    bool mirror_ok = false;    // electrostatic GK15 on a symmetric grid: decided at creation (mirror_wanted)
+    bool mirror_ok = false;    // the grid is symmetric under i -> N-1-i: decided at creation (mirror_wanted)
+    int mirror_shapes = EMME_MIRROR_SHAPES_ES15;  // shapes that mirror on such a grid (emme_ctx_set_mirror_shapes;
+                               // EMME_MIRROR_SHAPES read at creation); fixed once a cache exists
     int mirror_opt = 1;        // emme_ctx_set_mirror_pairs (EMME_MIRROR read at creation); fixed once a cache exists
     bool mirror = false;       // the tiled cache is laid out over d_pairs_half: fixed when it is first allocated
     // parameter sets bound to the context (emme_ctx_bind_param_sets): each has the shape of `p`
@@ -202,10 +204,14 @@ namespace emme {
 
 // ---- ctx_cache.hip: buffer pool (pool_alloc / pool_free / malloc_retry: buffers.hpp) and node cache ------------
 void pool_release_all();
-// what a tiled cache allocated now would be laid out over: the half list on a symmetric electrostatic GK15 grid, unless
-// switched off or the context serves cached derivative fills (their kernels read the full list)
+// what a tiled cache allocated now would be laid out over: the half list on a symmetric grid -- electrostatic GK15, or
+// any shape under EMME_MIRROR_SHAPES_ALL -- unless switched off or the context serves cached
+// derivative fills (their kernels read the full list)
+inline bool mirror_shape_ok(const emme_ctx* c) {
+    return (c->nm == 1 && c->p.integration_start_points == 15) || c->mirror_shapes == EMME_MIRROR_SHAPES_ALL;
+}
 inline bool mirror_wanted(const emme_ctx* c) {
-    return c->mirror_ok && c->mirror_opt != 0 && c->tiled && c->opt.deriv_cached == 0;
+    return c->mirror_ok && mirror_shape_ok(c) && c->mirror_opt != 0 && c->tiled && c->opt.deriv_cached == 0;
 }
 // pairs the tiled cache is laid out over, and with it its builder, the dense fill and the deferred pass
 inline int cache_npairs(const emme_ctx* c) { return c->mirror ? c->npairs_half : c->npairs; }

@@ -216,7 +216,9 @@ int secant_loop(emme_ctx* c, RootSearch& search) {
         // (d_Mp holds the half problems' S': solve_eigenpairs allocates it exactly where a step can fold, and a step
         // without it is never folded.  The list of the folded step is p_live == 1, which is d_active == 1: k_retire
         // only turns 2 into 0 after the flags were read; the kernels check d_active as well, as the parent's does.)
-        const bool pair_mirrored = c->mirror && old_mirrored && new_mirrored;  // both matrices of the secant
+        // (electrostatic only: the matrix of a mirrored electromagnetic context is a 2 x 2 block matrix of
+        // centrosymmetric blocks, not centrosymmetric itself -- its even order dim = 2 N must not route it here)
+        const bool pair_mirrored = c->mirror && c->nm == 1 && old_mirrored && new_mirrored;  // both matrices of the secant
         const bool eig_folded = eig && c->eigpair_fold != 0 && pair_mirrored &&
                                 eigpair_fold_applies(c, c->dim) && !(j == 0 && !search.v0) && !search.set &&
                                 c->d_Mp.bytes() >= batch_bytes(c->dim, n);
@@ -429,7 +431,8 @@ int solve_eigenpairs(emme_ctx* c, const std::string& who, bool secant, const int
     // problems' S')
     // -- only where a step can fold at all: no parameter sets, an order whose halves qualify, and a node cache that is,
     // or once allocated would be, laid out over the half pair list
-    const bool may_fold = c->eigpair_fold != 0 && !set && eigpair_fold_applies(c, dim) &&
+    // (and an electrostatic context: see pair_mirrored in secant_loop)
+    const bool may_fold = c->eigpair_fold != 0 && !set && c->nm == 1 && eigpair_fold_applies(c, dim) &&
                           ((c->cache[0].recs || c->cache[1].recs) ? c->mirror : mirror_wanted(c));
     const int secant_sets = 1 | 2 | 8 | (may_fold ? 4 : 0);
     EMME_TRY(run_search(c, guesses, n, tol, step_limit, roots, iters, info, iterates, secant ? secant_sets : 1 | 4 | 8,

@@ -312,11 +312,15 @@ int emme_ctx_create_ex(const emme_params_t* p, int device, const emme_options_t*
     c->npairs_half = (int)half.size();
     // Mirror-image pairs share their integral where the grid is symmetric (theta = 0): eta, g odd and b even to 1e-13
     // of the table's largest value -- 30 times the rounding of the tables themselves (3e-15), nine orders below a real
-    // asymmetry (theta = 0.3: 3e-2).  Only the electrostatic GK15 dense fill writes mirrors (mirror_wanted: and only
-    // on the tiled layout, which emme_ctx_set_options may still change while no cache exists).
-    c->mirror_ok = c->nm == 1 && p->integration_start_points == 15 && grid_is_mirror_symmetric(tab.data(), N, 1e-13);
+    // asymmetry (theta = 0.3: 3e-2).  Which shapes then mirror is mirror_wanted's rule (electrostatic GK15, or every
+    // shape under EMME_MIRROR_SHAPES_ALL: and only on the tiled layout, which emme_ctx_set_options may still change
+    // while no cache exists).
+    c->mirror_ok = grid_is_mirror_symmetric(tab.data(), N, 1e-13);
     // (developer override, read once per context: EMME_MIRROR=0 is emme_ctx_set_mirror_pairs(0))
     if (const char* v = std::getenv("EMME_MIRROR")) c->mirror_opt = std::atoi(v) != 0;
+    // (and EMME_MIRROR_SHAPES=1 is emme_ctx_set_mirror_shapes(EMME_MIRROR_SHAPES_ALL))
+    if (const char* v = std::getenv("EMME_MIRROR_SHAPES"))
+        c->mirror_shapes = std::atoi(v) == EMME_MIRROR_SHAPES_ALL ? EMME_MIRROR_SHAPES_ALL : EMME_MIRROR_SHAPES_ES15;
     // (the same for the folded trace-secant step, DESIGN.md 5.4c: EMME_LU_FOLD=0 is emme_ctx_set_lu_fold(0))
     if (const char* v = std::getenv("EMME_LU_FOLD")) c->lu_fold = std::atoi(v) != 0;
     // (and for the folded secant eigenpair step, DESIGN.md 14.2: EMME_EIGPAIR_FOLD=1 is emme_ctx_set_eigpair_fold(1))
@@ -416,6 +420,25 @@ int emme_ctx_get_mirror_pairs(const emme_ctx_t* c) {
     if (!c) return EMME_EINVAL;
     return (c->cache[0].recs || c->cache[1].recs) ? (int)c->mirror : (int)mirror_wanted(c);
 }
+
+int emme_ctx_set_mirror_shapes(emme_ctx_t* c, int shapes) {
+    if (!c) {
+        set_error("emme_ctx_set_mirror_shapes: NULL context");
+        return EMME_EINVAL;
+    }
+    if (shapes != EMME_MIRROR_SHAPES_ES15 && shapes != EMME_MIRROR_SHAPES_ALL) {
+        set_error("emme_ctx_set_mirror_shapes: value out of range (EMME_MIRROR_SHAPES_ES15, EMME_MIRROR_SHAPES_ALL)");
+        return EMME_EINVAL;
+    }
+    if (c->cache[0].recs || c->cache[1].recs) {
+        set_error("emme_ctx_set_mirror_shapes: the pair list fixes the layout of the node cache, which exists already");
+        return EMME_EINVAL;
+    }
+    c->mirror_shapes = shapes;
+    return EMME_OK;
+}
+
+int emme_ctx_get_mirror_shapes(const emme_ctx_t* c) { return c ? c->mirror_shapes : EMME_EINVAL; }
 
 int emme_ctx_set_lu_fold(emme_ctx_t* c, int on) {
     if (!c) {

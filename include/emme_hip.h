@@ -211,7 +211,8 @@ int emme_ctx_set_deriv_cache_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL
 int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
 /* Mirror-image pairs (additions within version 4, found by symbol lookup).  On a grid that is symmetric
  * under i -> N-1-i (eta and g odd, b even to 1e-13 of the table's largest value: theta = 0) the integral of pair (i, j)
- * is that of (N-1-j, N-1-i).  An electrostatic GK15 context on the tiled layout then lays its node cache out over one
+ * is that of (N-1-j, N-1-i).  An electrostatic GK15 context on the tiled layout -- with EMME_MIRROR_SHAPES_ALL (below)
+ * an electromagnetic or GK31 one as well -- then lays its node cache out over one
  * pair of every such couple -- half the cache, half the integrals of the dense fill and of its deferred pass -- and
  * writes both entries, each under its own SingularityHandler weight; interval counts stay those of the full pair list.
  * The two entries agree to the rounding noise of the reference's own mirror pairs.  On by default (EMME_MIRROR=0, read
@@ -221,11 +222,27 @@ int emme_ctx_get_deriv_cache_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_E
  * list, or before it exists whether it would be; 0 on every context that is not eligible. */
 int emme_ctx_set_mirror_pairs(emme_ctx_t* ctx, int on); /* EMME_EINVAL: NULL ctx, value not 0 / 1, cache exists */
 int emme_ctx_get_mirror_pairs(const emme_ctx_t* ctx);   /* 0 / 1; < 0: EMME_EINVAL for NULL */
+/* Which shapes run mirrored (additions within version 4, found by symbol lookup).  The symmetry above
+ * holds for all three velocity moments of an electromagnetic context (kappa_e reads a pair through eta_i - eta_j and
+ * g_i - g_j alone, and the mirror image keeps i < j, so block B keeps its signs) and for the 31-point rule.  With
+ * EMME_MIRROR_SHAPES_ALL, electromagnetic and GK31 contexts on a symmetric grid mirror exactly as electrostatic GK15
+ * does: the half pair list under the tiled cache, the dense fill k_assemble_dense<1, PTS, NM> and its deferred pass,
+ * each integral stored to its mirror-image entries in the block of its moment.  Everything else of
+ * emme_ctx_set_mirror_pairs holds unchanged (deriv_cached, cached derivative requests, the region searches).  A
+ * mirrored electrostatic GK31 context takes the folded steps below under their own rules; a mirrored electromagnetic
+ * context never folds -- its matrix is a 2 x 2 block matrix of centrosymmetric blocks, not centrosymmetric itself.
+ * Default EMME_MIRROR_SHAPES_ES15: every context behaves bit for bit as without this setting.  EMME_MIRROR_SHAPES, read
+ * at creation, overrides the default.  A layout setting: EMME_EINVAL once the node cache exists. */
+#define EMME_MIRROR_SHAPES_ES15 0 /* default: only electrostatic GK15 contexts mirror */
+#define EMME_MIRROR_SHAPES_ALL  1 /* electromagnetic and GK31 contexts on a symmetric grid mirror as well */
+int emme_ctx_set_mirror_shapes(emme_ctx_t* ctx, int shapes); /* EMME_EINVAL: NULL ctx, value out of range, cache exists */
+int emme_ctx_get_mirror_shapes(const emme_ctx_t* ctx);       /* < 0: EMME_EINVAL for NULL */
 /* The folded trace-secant step (additions within version 4, found by symbol lookup).  Where a context
  * runs mirrored (above) its matrix is symmetric and, apart from the SingularityHandler's rule for the last row and
  * column, centrosymmetric: a trace-secant step of emme_solve_roots whose two fills both ran mirrored for every live
  * chain, on an even order, factors the even and the odd block of order dim / 2 instead of the matrix and adds the
- * exact rank-2 correction of that rule.  Every other step -- odd order, theta != 0, electromagnetic and GK31 contexts,
+ * exact rank-2 correction of that rule.  Every other step -- odd order, theta != 0, electromagnetic contexts (mirrored
+ * or not), GK31 contexts that do not mirror (EMME_MIRROR_SHAPES_ES15),
  * the QR method, the Newton, eigenpair, sets and region searches, the step-level entry points -- is what it was.
  * Option lu_fold: 1 = on, 0 = the unfolded step bit for bit; EMME_LU_FOLD, read at creation, overrides the default.
  * (emme_options_t has no room left for a field that keeps its size: the option is a setter, as mirror_pairs is.)
